@@ -130,6 +130,33 @@ def cpu_baseline_embed(sd, budget_s=12.0):
             "distmat_1024_ms": round(dist_ms, 2)}
 
 
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs: array bytes of one run together (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs DIR: what the timed path handed back in its last step, as DIR/<name>.npy (fp32 as is, int32 indices as fp64),
+    for comparing two builds output for output.  `outputs` maps a name to a DevArray.  Smallest first, each array gets an equal
+    share of what is left of DUMP_BUDGET_BYTES; one larger than its share is written as a fixed sample of its rows
+    (numpy default_rng(0), in row order), so the same arguments write the same rows every run."""
+    os.makedirs(dirname, exist_ok=True)
+    out_dtype = lambda a: np.dtype(np.float32 if a.dtype == np.float32 else np.float64)
+    row_bytes = lambda a: int(np.prod(a.shape[1:])) * out_dtype(a).itemsize
+    left = DUMP_BUDGET_BYTES
+    items = sorted(outputs.items(), key=lambda kv: kv[1].shape[0] * row_bytes(kv[1]))
+    for i, (name, arr) in enumerate(items):
+        rows = min(arr.shape[0], (left // (len(items) - i)) // row_bytes(arr))
+        if rows == arr.shape[0]:
+            host = arr.numpy()
+        else:
+            keep = np.sort(np.random.default_rng(0).choice(arr.shape[0], rows, replace=False))
+            host = np.empty((rows,) + arr.shape[1:], arr.dtype)
+            for j, r in enumerate(keep):
+                arr.engine.d2h(host[j], arr.row_ptr(r))
+        host = host.astype(out_dtype(arr))
+        np.save(os.path.join(dirname, name + ".npy"), host)
+        left -= host.nbytes
+
+
 class Job:
     """Engine + stream + communicator of this rank, and the timing protocol of the bench contract.  Device, stream and every
     synchronisation go through the C ABI (reid_ctx_create on LOCAL_RANK's device, the context's own non-blocking HIP stream,
@@ -217,10 +244,12 @@ def run_embed(job, args):
         parallel.embed_sharded_dev(eng, comm, crops.ptr, n, n * world, emb_all, emb_local.ptr)
         parallel.distmat_row_block(eng, emb_all, lo, hi, _ffi.METRIC_L2, distmat)
 
-    def run(precision, steps, warmup):
+    def run(precision, steps, warmup, dump=None):
         """Timed region per the bench contract + a profiled repeat of the same steps for the roofline object."""
         eng.set_precision({"f32": 0, "f16": 1, "f16x3": 2}[precision])
         elapsed = job.timed(step, steps, warmup)
+        if dump and rank == 0:
+            dump_outputs(dump, {"embeddings": emb_all, "distmat": distmat})
         # split of one step (embed / all-gather+distmat), HIP events on the launch stream
         eng.timer_start()
         parallel.embed_sharded_dev(eng, comm, crops.ptr, n, n * world, emb_all, emb_local.ptr)
@@ -272,7 +301,7 @@ def run_embed(job, args):
             },
         }
 
-    main_res = run(args.precision, args.steps, args.warmup)
+    main_res = run(args.precision, args.steps, args.warmup, args.dump_outputs)
     others = {} if args.single else {o: run(o, max(1, min(3, args.steps)), 1) for o in ("f32", "f16x3", "f16") if o != args.precision}
     sustained = sustained_mfma(eng)
     if sustained is not None:
@@ -354,9 +383,11 @@ def run_swin(job, args):
         eng.swin_embed_dev(x.ptr, n, 224, 224, emb_local.ptr)
         comm.all_gather(emb_local.ptr, emb_all.ptr, n * 96 * 4)
 
-    def run(precision, steps, warmup):
+    def run(precision, steps, warmup, dump=None):
         eng.set_precision({"f32": 0, "f16": 1, "f16x3": 2}[precision])
         elapsed = job.timed(step, steps, warmup)
+        if dump and rank == 0:
+            dump_outputs(dump, {"embeddings": emb_all})
         eng.profile_reset()
         eng.profile(True)
         for _ in range(steps):
@@ -391,7 +422,7 @@ def run_swin(job, args):
                 "other_kernels": {"elementwise_attention_norm": {"ms_per_step": round(e["ms"] / steps, 3)}}}
 
     main_prec = args.precision
-    main_res = run(main_prec, args.steps, args.warmup)
+    main_res = run(main_prec, args.steps, args.warmup, args.dump_outputs)
     # what was timed is checked before it is printed: the embeddings of the timed configuration (passes of up to 1024 images) are
     # finite, and six of them agree with the exact-fp32 mode's on the same images (images are independent,
     # swin_transformer.py:191-232,248-260; the GPU tests hold exact fp32 to the reference's vectors)
@@ -745,6 +776,8 @@ def run_market(job, args):
         parallel.knn_gallery_sharded_dev(eng, dq.ptr, nq, dg.ptr, hi - lo, lo, d, k, dD.ptr, dI.ptr, world)
 
     elapsed = job.timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"distmat": dist, "knn_dist": dD, "knn_index": dI})
     eng.timer_start()
     if hi > lo:
         eng.distmat_dev(dq.ptr, nq, dg.ptr, hi - lo, d, _ffi.METRIC_L2, dist.ptr)
@@ -855,6 +888,7 @@ def run_all(job, args):
 
     def sub(name, fn, limit_s, **over):
         a = copy.copy(args)
+        a.dump_outputs = None                 # --dump-outputs: the headline's timed path only
         for k, v in over.items():
             setattr(a, k, v)
         state["current"], state["deadline"] = name, time.monotonic() + limit_s * float(os.environ.get("REID_BENCH_LIMIT_SCALE", "1"))
@@ -1049,9 +1083,19 @@ def main(argv=None):
                          "exact-fp32 mode's parity bar (stage taps < 2e-5 of the reference, 1 - cos < 1e-5, no arg-min differs where the "
                          "reference's top-2 gap exceeds 2e-6 and none at all on the realistic config-1 set: tests/test_gpu_parity.py); f32 = exact fp32 MFMA (side run f32_path); f16 = fp16 storage / "
                          "fp32 accumulate (side run f16_path, north_star's 1e-3 cosine tolerance)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (fp32 / fp64, "
+                         "at most 64 MB in all: a larger output as a fixed sample of its rows); default line: the headline's "
+                         "embeddings and distance matrix.  Not for --workload tracking")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.workload == "tracking":
+        ap.error("--dump-outputs: not available for --workload tracking")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(argv, args.gpus)
     if args.workload == "batch256":

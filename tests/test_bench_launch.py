@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,3 +63,59 @@ def test_lost_sub_workload_ends_the_job_with_a_nonzero_exit_code(gpus, rank0_del
     assert out["value"] > 0 and "error" in out["batch256"]
     if gpus == 1:
         assert r.returncode == 3
+
+
+@pytest.mark.timeout(300)
+def test_bench_dumps_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: the headline's embeddings and distance matrix of the last timed step, fp32, from the seeded crops of the
+    run (here through the stand-in network, so the files can be recomputed on the host)."""
+    from oracle import matching
+    from reid_amd import synth
+    from standin_lib import _embed_rows
+    r = _bench(["--gpus", "1", "--workload", "embed", "--dump-outputs", str(tmp_path / "out"),
+                "--crops", "8", "--steps", "3", "--warmup", "0", "--no-cpu", "--single"], 280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _one_line(r)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "out")) == ["distmat.npy", "embeddings.npy"]
+    emb, dist = np.load(tmp_path / "out" / "embeddings.npy"), np.load(tmp_path / "out" / "distmat.npy")
+    assert emb.dtype == np.float32 and dist.dtype == np.float32
+    np.testing.assert_array_equal(emb, _embed_rows(list(synth.crops_u8(8, seed=1))))
+    np.testing.assert_allclose(dist, matching.euclidean_dist(emb, emb), rtol=1e-6, atol=1e-6)
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_row_sample(tmp_path, monkeypatch):
+    """An output larger than its share of the budget is written as the same sorted, seeded sample of rows in every run; int32
+    outputs become fp64, fp32 stays fp32."""
+    import bench
+
+    class Host:
+        """What dump_outputs needs of a DevArray, over host memory (a device pointer is the row index)."""
+        def __init__(self, a):
+            self.a, self.shape, self.dtype, self.nbytes = a, a.shape, a.dtype, a.nbytes
+            self.engine = self
+
+        def numpy(self):
+            return self.a.copy()
+
+        def row_ptr(self, r):
+            return int(r)
+
+        def d2h(self, out, r):
+            out[...] = self.a[r]
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 40 * 1024)
+    rng = np.random.default_rng(5)
+    small = rng.normal(size=(4, 8)).astype(np.float32)
+    big = rng.normal(size=(300, 64)).astype(np.float32)          # 76.8 kB: more than the 39 kB the other two leave
+    idx = rng.integers(0, 1 << 30, size=(10, 20)).astype(np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": Host(big), "small": Host(small), "idx": Host(idx)})
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("big", "small", "idx")}
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in got) <= 40 * 1024 + 3 * 128
+    np.testing.assert_array_equal(got["small"], small)
+    assert got["idx"].dtype == np.float64 and (got["idx"] == idx).all()
+    assert got["big"].dtype == np.float32 and 0 < len(got["big"]) < len(big)
+    rows = [int(np.flatnonzero((big == row).all(1))[0]) for row in got["big"]]
+    assert rows == sorted(rows) and len(set(rows)) == len(rows)
+    np.testing.assert_array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
