@@ -80,6 +80,11 @@ __global__ void bank_set_count_kernel(const int32_t* __restrict__ slots, const i
     if (i < n) count[slots[i]] = values[i];
 }
 
+// A sample whose cost is NaN (non-finite input; a zero norm under the cosine metric) is left out of the minimum by fminf, so a track or
+// detection made only of such rows matches nothing (reid_bank_cost).  The euclidean clamp must let NaN through for that: fmaxf(NaN, 0)
+// is 0, a perfect match.
+__device__ __forceinline__ float clamp0(float c) { return c < 0.f ? 0.f : c; }
+
 // metric 0: cosine, 1: squared euclidean.  gate < 0: no clamp.  NW waves per block share a track's samples: a tracking frame
 // launches only tracks x ceil(dets / 16) blocks (80 for 40 x 30), so the per-block latency - budget / NW samples per wave - is
 // the kernel's time; 16 waves instead of 4 cut it ~4x.
@@ -128,7 +133,7 @@ __global__ __launch_bounds__(NW * 64) void bank_cost_kernel(const float* __restr
             for (int off = 32; off; off >>= 1) a += __shfl_xor(a, off);
             float c;
             if (metric == 0) c = 1.f - a / (sqrtf(ssq) * sqrtf(det_sq[j]));
-            else c = fmaxf(ssq + det_sq[j] - 2.f * a, 0.f);
+            else c = clamp0(ssq + det_sq[j] - 2.f * a);
             best[j] = fminf(best[j], c);
         }
     }
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(NW5 * 64) void bank_cost512_kernel(const float* __r
         const float dot = butterfly16(tmp, lane);
         float c;
         if (metric == 0) c = 1.f - dot / (sqrtf(ssq) * sqrtf(dsq));
-        else c = fmaxf(ssq + dsq - 2.f * dot, 0.f);
+        else c = clamp0(ssq + dsq - 2.f * dot);
         best = fminf(best, c);
     }
     if (lane < 16) best_sh[wave][jl] = best;
@@ -237,6 +242,27 @@ __global__ __launch_bounds__(NW5 * 64) void bank_cost512_kernel(const float* __r
 
 }  // namespace
 
+// The match stream (opt-in, reid_frame_match_stream): cost and update stages run there, ordered against the forwards by two events per
+// slot.  While a stage is queued the context's stream pointer is swapped, so the launchers it calls need not know.  The bank's other
+// entry points (host / device features in, costs out) run there too, so that every access to a bank is ordered on ONE stream: `join`
+// puts them behind what the compute stream holds so far (the caller's device operands), `rejoin` makes the compute stream wait for
+// them (device results the caller goes on to use).
+struct MatchStream {
+    reid_ctx* ctx;
+    hipStream_t saved;
+    bool rejoin;
+    explicit MatchStream(reid_ctx* c, bool join = false, bool rejoin_ = false) : ctx(c), saved(c->stream), rejoin(rejoin_) {
+        if (!on()) return;
+        if (join && hipEventRecord(c->join_ev, saved) == hipSuccess) hipStreamWaitEvent(c->match_stream, c->join_ev, 0);
+        c->stream = c->match_stream;
+    }
+    ~MatchStream() {
+        ctx->stream = saved;
+        if (on() && rejoin && hipEventRecord(ctx->join_ev, ctx->match_stream) == hipSuccess) hipStreamWaitEvent(saved, ctx->join_ev, 0);
+    }
+    bool on() const { return ctx->match_async && ctx->match_stream; }
+};
+
 extern "C" int reid_bank_create(reid_ctx* ctx, int max_tracks, int budget, int d, reid_bank** out) {
     ARG_CHECK(ctx && out && max_tracks >= 1 && budget >= 1 && d >= 1 && d <= 2048);
     CTX_GUARD(ctx);
@@ -251,7 +277,12 @@ extern "C" int reid_bank_create(reid_ctx* ctx, int max_tracks, int budget, int d
     HIP_TRY(hipMalloc((void**)&b->feat, (size_t)max_tracks * budget * d * 4));
     HIP_TRY(hipMalloc((void**)&b->sq, (size_t)max_tracks * budget * 4));
     HIP_TRY(hipMalloc((void**)&b->count, (size_t)max_tracks * 4));
-    HIP_TRY(hipMemsetAsync(b->count, 0, (size_t)max_tracks * 4, ctx->stream));
+    {
+        // on the bank's stream like every later access to it: a bank created inside a tracker's first step() is first fed by
+        // update stages of the match stream, which wait for the slot's forward only - not for this stream's work queued after it
+        MatchStream ms(ctx, true, true);
+        HIP_TRY(hipMemsetAsync(b->count, 0, (size_t)max_tracks * 4, ctx->stream));
+    }
     *out = b;
     return REID_OK;
 }
@@ -344,27 +375,6 @@ static int bank_update_impl(reid_ctx* ctx, reid_bank* b, const float* d_feats, c
     return REID_OK;
 }
 
-// The match stream (opt-in, reid_frame_match_stream): cost and update stages run there, ordered against the forwards by two events per
-// slot.  While a stage is queued the context's stream pointer is swapped, so the launchers it calls need not know.  The bank's other
-// entry points (host / device features in, costs out) run there too, so that every access to a bank is ordered on ONE stream: `join`
-// puts them behind what the compute stream holds so far (the caller's device operands), `rejoin` makes the compute stream wait for
-// them (device results the caller goes on to use).
-struct MatchStream {
-    reid_ctx* ctx;
-    hipStream_t saved;
-    bool rejoin;
-    explicit MatchStream(reid_ctx* c, bool join = false, bool rejoin_ = false) : ctx(c), saved(c->stream), rejoin(rejoin_) {
-        if (!on()) return;
-        if (join && hipEventRecord(c->join_ev, saved) == hipSuccess) hipStreamWaitEvent(c->match_stream, c->join_ev, 0);
-        c->stream = c->match_stream;
-    }
-    ~MatchStream() {
-        ctx->stream = saved;
-        if (on() && rejoin && hipEventRecord(ctx->join_ev, ctx->match_stream) == hipSuccess) hipStreamWaitEvent(saved, ctx->join_ev, 0);
-    }
-    bool on() const { return ctx->match_async && ctx->match_stream; }
-};
-
 extern "C" int reid_bank_update_dev(reid_ctx* ctx, reid_bank* b, const float* d_feats, const int32_t* slots, int n) {
     ARG_CHECK(ctx && b && b->ctx == ctx && n >= 0 && (n == 0 || (d_feats && slots)));
     CTX_GUARD(ctx);
@@ -434,7 +444,8 @@ static int bank_cost_impl(reid_ctx* ctx, reid_bank* b, const int32_t* slots, int
     return bank_cost_launch(ctx, b, d_slots, t, d_dets, m, metric, max_dist, d_out);
 }
 
-// cost[t][m]; metric REID_METRIC_COS (1 - cosine) or REID_METRIC_L2SQR; max_dist < 0: raw, else cost > max_dist -> max_dist + 1e-5
+// cost[t][m]; metric REID_METRIC_COS (1 - cosine) or REID_METRIC_L2SQR; max_dist < 0: raw, else cost > max_dist -> max_dist + 1e-5.
+// A track without samples, or whose every sample gives a NaN cost against a detection, has no match there: inf raw, max_dist + 1e-5 gated.
 extern "C" int reid_bank_cost_dev(reid_ctx* ctx, reid_bank* b, const int32_t* slots, int t, const float* d_dets, int m,
                                   int metric, float max_dist, float* d_out) {
     ARG_CHECK(ctx && b && b->ctx == ctx && t >= 0 && m >= 0);

@@ -91,7 +91,13 @@ class NearestNeighborDistanceMetric:
 
     def distance(self, features, targets, max_distance=None):
         """cost[len(targets), len(features)] (float64 array holding float32 values, like the reference's np.zeros fill).
-        ``max_distance`` additionally applies min_cost_matching's gate on the device."""
+        ``max_distance`` additionally applies min_cost_matching's gate on the device.
+
+        Non-finite and zero-norm input, on purpose: a stored sample whose cost against a detection is NaN (a NaN in either row, or
+        a zero norm under the cosine metric) takes no part in that entry's minimum, and an entry with no other sample is "no
+        match" - inf without ``max_distance``, max_distance + 1e-5 with it - where the reference's float arithmetic would give
+        NaN.  Such a row never reaches the assignment as a match and never as NaN.  A target that holds no sample at all is "no
+        match" as well (the reference raises KeyError)."""
         targets = list(targets)
         features = np.ascontiguousarray(features, dtype=np.float32)
         m = features.shape[0] if features.ndim == 2 else 0

@@ -979,8 +979,9 @@ def test_f16_path_small_and_odd_batches(eng_w0, n):
 # reference's own batch-size instability; which of its two candidates a kernel picks is a property of its summation order.
 #   (0, 1024): exact fp32, the 256 crops as ONE pass - found when this list was introduced (round 6; rounds 2-5 printed it: the exact-fp32
 #              kernels did not change in round 6, the pass of 256 splits its K loops differently from four passes of 64)
-#   (2, 64):   fp32-class, passes of 64 crops - since round 6 layers 3-4 of such a pass run conv3x3_x3.hip's split-K forms (another
-#              summation order than conv3x3_f16.hip's 12-wave kernel that served them before)
+#   (2, 1024): fp32-class, the 256 crops as ONE pass - row 180, reference gap 6e-8 (one ulp of the distance).  (2, 64) held row 84
+#              while layers 3-4 of such a pass ran conv3x3_x3.hip's split-K forms; it left the list when conv_x3s_kernel took the
+#              strided / 1x1 convolutions (round 6).
 # Every other combination reproduces all 256 rows.
 CONFIG1_RAND0_KNOWN_SUBNOISE_ROWS = {(0, 1024): {84}, (2, 1024): {180}}   # (2, 64): {84} until conv_x3s_kernel took the strided / 1x1 convolutions (round 6); row 180: gap 6e-8 = one ulp
 @pytest.mark.parametrize("chunk", [40, 64, 130, 1024])   # passes of 40 (+ 16) and 130 + 126 crops: the small- and mid-size launch rules of round 6; four passes of 64 (the library default of rounds 1-3); one pass of 256
@@ -1029,8 +1030,8 @@ def test_config1_against_reference_vectors(eng_w0, golden_dir, precision, tag, c
             assert len(flips) == 0, (flips, gap[flips])
         else:
             # The published claim (README, DESIGN section 2, bench.py --precision help) is "0 of 256 rows differ on the noise set too,
-            # at HEAD".  That claim is ENFORCED here through an explicit allowlist - empty today: a kernel change that flips a
-            # sub-noise row fails this test until the row is recorded below (with the commit that moved it) and the published
+            # at HEAD".  That claim is ENFORCED here through an explicit allowlist (CONFIG1_RAND0_KNOWN_SUBNOISE_ROWS): a kernel change that flips a
+            # sub-noise row fails this test until the row is recorded in it (with the commit that moved it) and the published
             # sentence is reworded in the same commit.  Rows above the noise can never be listed: they failed the assertion above.
             if len(flips):
                 print("config1 rand0 precision %d chunk %d: sub-noise rows that differ (row, reference gap): %s"
