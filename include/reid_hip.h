@@ -272,7 +272,9 @@ int reid_frame_update(reid_ctx* ctx, int slot, reid_bank* bank, const int32_t* r
 int reid_frame_match_stream(reid_ctx* ctx, int on);
 /* retrieval evaluation, reid/evaluate.py:33-105: for every query the ranks of its good gallery items among
  * non-junk items (descending similarity gf@q).  cmc_sum int32[ng] = sum over valid queries of the CMC step,
- * ap double[nq], valid int32[nq] (0 when the query has no good item). */
+ * ap double[nq], valid int32[nq] (0 when the query has no good item).  Order: np.argsort(score, kind="stable")[::-1] (NaN
+ * first, equal scores by higher gallery index first).  REID_ERR_ARG for a query with more than 2048 good items, and for a query
+ * labelled -1 while gallery items labelled -1 lie in other cameras. */
 int reid_rank_eval(reid_ctx* ctx, const float* qf, const int64_t* ql, const int64_t* qc, int nq,
                    const float* gf, const int64_t* gl, const int64_t* gc, int ng, int d,
                    int32_t* cmc_sum, double* ap, int32_t* valid);

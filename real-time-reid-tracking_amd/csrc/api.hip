@@ -1679,6 +1679,24 @@ extern "C" int reid_rank_eval_dev(reid_ctx* ctx, const float* d_qf, const int64_
                                   double* ap, int32_t* valid) {
     ARG_CHECK(ctx && d_qf && ql && qc && d_gf && gl && gc && cmc_sum && ap && valid && nq >= 1 && ng >= 1 && d >= 1);
     CTX_GUARD(ctx);
+    // a query labelled -1 and gallery items labelled -1 in other cameras: those items are good and junk at once (the reference's
+    // compute_mAP finds no good row and raises IndexError).  Cameras of the -1 gallery items: none, one (neg_cam) or several.
+    int64_t neg_cam = 0;
+    int neg_cams = 0;
+    for (int j = 0; j < ng && neg_cams < 2; ++j)
+        if (gl[j] == -1) {
+            if (neg_cams == 0) {
+                neg_cam = gc[j];
+                neg_cams = 1;
+            } else if (gc[j] != neg_cam) {
+                neg_cams = 2;
+            }
+        }
+    for (int q = 0; q < nq; ++q)
+        if (ql[q] == -1 && (neg_cams == 2 || (neg_cams == 1 && qc[q] != neg_cam))) {
+            reid_set_error("reid_rank_eval: query %d is labelled -1 and gallery items labelled -1 lie in other cameras", q);
+            return REID_ERR_ARG;
+        }
     long long *dql, *dqc, *dgl, *dgc;
     int32_t *dhist, *dvalid;
     double* dap;

@@ -24,6 +24,7 @@ const Switch kSwitches[] = {
     {"f16_se_tail", &reid_ctx::f16_se_tail}, {"f16_c64", &reid_ctx::f16_c64}, {"swin_chunk_cap", &reid_ctx::swin_chunk_cap},
     {"split_x3", &reid_ctx::split_x3}, {"x3_ablate", &reid_ctx::x3_ablate}, {"x3_unroll", &reid_ctx::x3_unroll}, {"x3_narrow", &reid_ctx::x3_narrow}, {"conv_x3s", &reid_ctx::conv_x3s}, {"x3s_sk_cap", &reid_ctx::x3s_sk_cap}, {"x3_l4_narrow_nmt", &reid_ctx::x3_l4_narrow_nmt}, {"split_x3_small", &reid_ctx::split_x3_small}, {"split_x3_min_blocks", &reid_ctx::split_x3_min_blocks}, {"f32_dist_bk16", &reid_ctx::f32_dist_bk16}, {"lin_x3", &reid_ctx::lin_x3},
     {"host_pipeline", &reid_ctx::host_pipeline}, {"x3_sk_cap", &reid_ctx::x3_sk_cap}, {"chain", &reid_ctx::chain}, {"split_gemm_min_tiles", &reid_ctx::split_gemm_min_tiles},
+    {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc},
 };
 }  // namespace
 

@@ -410,6 +410,7 @@ struct reid_ctx {
     int select_exp = 0;      // experiments only (reid_debug_select_exp, debug.hip): 1 / 2 skip phases of the fused selection (results
                              // are then incomplete), 4 prints candidate-list statistics
     int select_two_pass = 0; // REID_SELECT_TWO_PASS=1: arg-min / k-NN through the full distance matrix (A/B against dist_select.hip)
+    int rerank_hbm_acc = 0;  // tests (debug switch): 1 = re-ranking's query-expansion and Jaccard accumulators in HBM scratch at every n
     int swin_stop = -1;      // diagnostics (REID_SWIN_STOP = block * 10 + phase): skip the rest of the Swin blocks after that point
     int swin_fold = 1;       // Swin, fp16-storage mode: to_out and post_proj folded into one Linear (REID_SWIN_FOLD=0: two launches)
     int swin_two_linear = 1; // Swin, fp32-class mode, C = 96: to_out -> post_proj and fc1 -> GELU -> fc2 as one launch each, the hidden

@@ -286,7 +286,7 @@ extern "C" int reid_rerank_jaccard_dev(reid_ctx* ctx, const float* d_x, int n, i
     const int kh1 = kh + 1 < k1 ? kh + 1 : k1;
     const int k2e = k2 < k1 ? k2 : k1;         // initial_rank[i, :k2] has at most k1 columns
     const int w1 = k1 + k1 * kh1;
-    const long long w2l = k2e == 1 ? w1 : (long long)k2e * w1;
+    const long long w2l = (long long)k2e * w1;
     const int w2 = (int)(w2l < n ? w2l : n);
     hipStream_t st = ctx->stream;
 
@@ -329,12 +329,14 @@ extern "C" int reid_rerank_jaccard_dev(reid_ctx* ctx, const float* d_x, int n, i
     const int grid = n < 2 * cus ? n : 2 * cus;
     float* scratch = nullptr;
     const size_t acc_b = (size_t)n * 4;
-    if (k2e != 1) {
+    // accumulators in LDS while they fit in 150 KB, else in a per-block HBM scratch row (and always with the debug switch
+    // rerank_hbm_acc, so that tests reach the scratch path at small n)
+    if (k2 != 1) {   // k2 > k1 = 1 still expands: V_qe[i] = V[rank[i][0]], which is V[i] only when i is its own nearest neighbour
         REID_TRY(ctx_ws(ctx, "rr.qi", (size_t)n * w2 * 4, (void**)&q_idx));
         REID_TRY(ctx_ws(ctx, "rr.qv", (size_t)n * w2 * 4, (void**)&q_val));
         REID_TRY(ctx_ws(ctx, "rr.qc", (size_t)n * 4, (void**)&q_cnt));
         const size_t list_b = (size_t)w2 * 4;
-        if (list_b + acc_b <= 150 * 1024) {
+        if (!ctx->rerank_hbm_acc && list_b + acc_b <= 150 * 1024) {
             const size_t sh = list_b + acc_b;
             if (sh > 48 * 1024)
                 HIP_TRY(hipFuncSetAttribute((const void*)qe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
@@ -355,7 +357,7 @@ extern "C" int reid_rerank_jaccard_dev(reid_ctx* ctx, const float* d_x, int n, i
         q_val = v_val;
         q_cnt = v_cnt;
     }
-    const int w = k2e != 1 ? w2 : w1;
+    const int w = k2 != 1 ? w2 : w1;
     REID_TRY(ctx_ws(ctx, "rr.cr", (size_t)n * w * 4, (void**)&col_row));
     REID_TRY(ctx_ws(ctx, "rr.cv", (size_t)n * w * 4, (void**)&col_val));
     HIP_TRY(hipMemsetAsync(col_cnt, 0, (size_t)n * 4, st));
@@ -367,7 +369,7 @@ extern "C" int reid_rerank_jaccard_dev(reid_ctx* ctx, const float* d_x, int n, i
     hipLaunchKernelGGL(col_fill_kernel, dim3(n), dim3(256), 0, st, q_idx, q_val, q_cnt, n, w, col_start, col_cur, col_row,
                        col_val);
     LAUNCH_CHECK();
-    if (acc_b <= 150 * 1024) {
+    if (!ctx->rerank_hbm_acc && acc_b <= 150 * 1024) {
         if (acc_b > 48 * 1024)
             HIP_TRY(hipFuncSetAttribute((const void*)jaccard_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)acc_b));
         hipLaunchKernelGGL(jaccard_kernel<true>, dim3(grid), dim3(512), acc_b, st, n, w, q_idx, q_val, q_cnt, col_start, col_row,

@@ -123,6 +123,16 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
 // Order = descending score (ties: higher gallery index first = reversed stable ascending argsort).  For every good
 // item: rank among non-junk items and rank among good items, then AP in the reference's own summation order (fp64).
 constexpr int MAX_GOOD = 2048;
+
+// "gallery item j comes before item gi" in the reversed stable ascending argsort: NaN > +inf > finite > -inf, equal values
+// (NaN with NaN, -0 with +0) by higher index first.  A strict total order, so the good items' ranks among themselves are a
+// permutation of 0..ngood-1.  Not pack_key: that orders -0 below +0, numpy does not.
+__device__ __forceinline__ bool rank_ahead(float sj, int j, float sg, int gi) {
+    const bool nan_j = sj != sj, nan_g = sg != sg;
+    if (nan_j || nan_g) return nan_j && (!nan_g || j > gi);
+    return sj > sg || (sj == sg && j > gi);
+}
+
 __global__ __launch_bounds__(256) void rank_eval_kernel(const float* __restrict__ score, int ng, long long ld,
                                                         const long long* __restrict__ ql, const long long* __restrict__ qc,
                                                         const long long* __restrict__ gl, const long long* __restrict__ gc,
@@ -159,8 +169,7 @@ __global__ __launch_bounds__(256) void rank_eval_kernel(const float* __restrict_
         int before = 0, before_good = 0;
         for (int j = tid; j < ng; j += 256) {
             const float sj = row[j];
-            const bool ahead = (sj > sg) || (sj == sg && j > gi);
-            if (!ahead) continue;
+            if (!rank_ahead(sj, j, sg, gi)) continue;
             const bool same = gl[j] == pid;
             const bool junk = gl[j] == -1 || (same && gc[j] == cam);
             if (junk) continue;
@@ -172,7 +181,9 @@ __global__ __launch_bounds__(256) void rank_eval_kernel(const float* __restrict_
         if (lane == 0) { atomicAdd(&rank_all[g], before); atomicAdd(&rank_good[g], before_good); }
     }
     __syncthreads();
-    for (int g = tid; g < ngood; g += 256) slot_rank[rank_good[g]] = rank_all[g];  // rank_good is a permutation of 0..ngood-1
+    // rank_good is a permutation of 0..ngood-1: rank_ahead is a strict total order, and no good item is junk
+    // (reid_rank_eval_dev refuses a query labelled -1 that has -1 items in other cameras)
+    for (int g = tid; g < ngood; g += 256) slot_rank[rank_good[g]] = rank_all[g];
     __syncthreads();
     if (tid == 0) {
         double a = 0.0;

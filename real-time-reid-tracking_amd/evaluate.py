@@ -2,8 +2,13 @@
 
 The reference loops over queries on the host: one GEMV, one D2H copy and one full argsort of the gallery per
 query (evaluate.py:58-63).  Here one GEMM produces every similarity row and a rank-counting kernel finds, for
-each good gallery item, its position among the non-junk items - no sort, no per-query copy.  Order of equal
-scores: higher gallery index first (the reference's np.argsort default is not stable, so ties are undefined there).
+each good gallery item, its position among the non-junk items - no sort, no per-query copy.
+
+Order: the reversed stable ascending argsort of the scores, ``np.argsort(score, kind="stable")[::-1]``.  So NaN comes first,
+then +inf, the finite scores in descending order, and -inf last; equal scores (NaN with NaN, -0 with +0 included) go by
+higher gallery index first.  The reference's np.argsort default is not stable, so ties are undefined there.
+Refused (ReidHipError naming the query): a query labelled -1 while gallery items labelled -1 lie in other cameras (they
+would be good and junk at once; the reference raises IndexError), and a query with more than 2048 good gallery items.
 """
 import numpy as np
 
