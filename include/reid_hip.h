@@ -309,7 +309,8 @@ int reid_knn_gallery_sharded_dev(reid_ctx* ctx, const float* d_xq, int nq, const
                                  int index_base, int d, int k, float* d_D, int32_t* d_I);
 
 /* ---- single operators (unit tests and reuse by other backbones) --------------------------- */
-/* NHWC convolution, weights [Cout][R][S][Cin], optional per-channel scale/shift, residual (same shape as out), ReLU */
+/* NHWC convolution, weights [Cout][R][S][Cin], optional per-channel scale/shift, residual (same shape as out), ReLU.  In mode 2
+ * weights with |w| 2^11 >= 65504 are refused (REID_ERR_ARG); the context's fault status is returned after the call. */
 int reid_conv2d_nhwc(reid_ctx* ctx, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int r,
                      int s, int stride, int pad, const float* scale, const float* shift, const float* residual,
                      int relu, float* out);

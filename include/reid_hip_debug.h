@@ -41,6 +41,17 @@ int reid_debug_linear(reid_ctx* ctx, int m, int n, int k, int mode, int iters, f
  * output (+ res) through the buffer-store epilogue. */
 int reid_debug_linear_rows(reid_ctx* ctx, const float* x, const float* w, const float* bias, const float* res, int m, int n, int k,
                            int mode, int flags, float* out);
+/* One convolution of the ResNet trunk through the launcher the forward uses (correctness harness, tests/test_gpu_conv.py): x fp32 NHWC
+ * [n][h][w][cin], wgt [cout][r][r][cin]; out = relu_from-on ReLU (if relu) of conv * scale + shift (+ residual), fp32 [m][cout] with
+ * m = n ho wo.  The context's precision and switches pick the kernel.  pack_from >= 0 asks for the [yh | yl'] f16 store of the
+ * columns from pack_from on (raw f16 bits, [m][2 cout]; the fp32 output of those columns is then not written); *packed_written says
+ * whether the launch made it.  want_stats: per-128-row column sums [m / 128][cout][2] (sum, sum of squares) of the output.
+ * a_scale / a_shift [n][cin] (+ a_relu): the exact-fp32 loader's input affine.  Every output the launch leaves alone reads as NaN
+ * (0xffff).  Drops the split weights cached for its weight buffer first; returns the context's fault status. */
+int reid_debug_conv_layer(reid_ctx* ctx, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int r, int stride,
+                          int pad, const float* scale, const float* shift, const float* residual, int relu, int relu_from, int pack_from,
+                          int want_stats, const float* a_scale, const float* a_shift, int a_relu, float* out, uint16_t* packed,
+                          float* stats, int* packed_written);
 /* Timing experiments on that kernel (WRONG results while set): bit 0 = no weight refills after the first two steps, bit 1 = no block
  * barriers.  0 restores the product behaviour. */
 int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits);

@@ -692,6 +692,30 @@ int conv_gemm(reid_ctx* ctx, int amode, const void* x, int n, int H, int W, int 
     return launch_gemm_f32(ctx, amode, E_CONV, p, REID_K_CONV_GEMM, flops, bytes);
 }
 
+// Entry points that copy caller weights into a reused workspace: the split form cached under that address (conv_gemm) belongs to
+// the previous call's weights, so it goes before every call
+int conv_weights_fresh(reid_ctx* ctx, const float* d_w) {
+    auto it = ctx->split_w.find(d_w);
+    if (it != ctx->split_w.end()) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        (void)hipFree(it->second);
+        ctx->split_w.erase(it);
+    }
+    return REID_OK;
+}
+
+// ... and such weights get the range check reid_seres18_load gives a checkpoint's: in mode 2 [wh 2^11 | wh | wl'] needs |w| 2^11 < 65504
+int conv_weights_splittable(reid_ctx* ctx, const float* h_w, size_t count, const char* who) {
+    if (ctx->precision != 2) return REID_OK;
+    for (size_t i = 0; i < count; ++i)
+        if (!(fabsf(h_w[i]) * 2048.0f < 65504.0f)) {
+            reid_set_error("%s: weight %zu (%g) is outside the range the fp32-class arithmetic (reid_ctx_set_precision 2) can split "
+                           "(|w| 2^11 < 65504); use mode 0", who, i, (double)h_w[i]);
+            return REID_ERR_ARG;
+        }
+    return REID_OK;
+}
+
 // precision 2: the [wh 2^11 | wh | wl'] f16 form of a convolution's weights (made once per checkpoint, cached by the blob address)
 static int split_weights_of(reid_ctx* ctx, const float* wgt, int Cout, int taps, int Cin, const _Float16** out) {
     auto it = ctx->split_w.find(wgt);
@@ -1748,6 +1772,7 @@ extern "C" int reid_conv2d_nhwc(reid_ctx* ctx, const float* x, int n, int h, int
     CTX_GUARD(ctx);
     const int ho = (h + 2 * pad - r) / stride + 1, wo = (w + 2 * pad - s) / stride + 1;
     const size_t nin = (size_t)n * h * w * cin, nw = (size_t)cout * r * s * cin, nout = (size_t)n * ho * wo * cout;
+    REID_TRY(conv_weights_splittable(ctx, wgt, nw, "reid_conv2d_nhwc"));
     float *dx, *dw, *dout, *dsc = nullptr, *dsh = nullptr, *dres = nullptr;
     REID_TRY(ctx_ws(ctx, "op.x", nin * 4, (void**)&dx));
     REID_TRY(ctx_ws(ctx, "op.w", nw * 4, (void**)&dw));
@@ -1764,11 +1789,12 @@ extern "C" int reid_conv2d_nhwc(reid_ctx* ctx, const float* x, int n, int h, int
         REID_TRY(ctx_ws(ctx, "op.res", nout * 4, (void**)&dres));
         HIP_TRY(hipMemcpyAsync(dres, residual, nout * 4, hipMemcpyHostToDevice, ctx->stream));
     }
+    REID_TRY(conv_weights_fresh(ctx, dw));
     REID_TRY(conv_gemm(ctx, A_IM2COL, dx, n, h, w, cin, dw, cout, r, s, stride, pad, r * s * cin, nullptr, nullptr, 0, dsc, dsh,
                        dres, relu, nullptr, dout));
     HIP_TRY(hipMemcpyAsync(out, dout, nout * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return REID_OK;
+    return ctx_fault_status(ctx);
 }
 
 extern "C" int reid_gemm_nt(reid_ctx* ctx, const float* a, int m, const float* b, int n, int k, const float* bias, float* c) {

@@ -456,6 +456,67 @@ extern "C" int reid_debug_linear_rows(reid_ctx* ctx, const float* x, const float
     return REID_OK;
 }
 
+// One convolution of the ResNet trunk through conv_gemm - the launch the forward makes, on host operands (include/reid_hip_debug.h).
+// The context's precision and switches pick the kernel; outputs the epilogue does not write keep the NaN fill put there first.
+extern "C" int reid_debug_conv_layer(reid_ctx* ctx, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int r,
+                                     int stride, int pad, const float* scale, const float* shift, const float* residual, int relu,
+                                     int relu_from, int pack_from, int want_stats, const float* a_scale, const float* a_shift, int a_relu,
+                                     float* out, uint16_t* packed, float* stats, int* packed_written) {
+    ARG_CHECK(ctx && x && wgt && out && n >= 1 && h >= 1 && w >= 1 && cin >= 1 && cout >= 1 && r >= 1 && stride >= 1 && pad >= 0);
+    ARG_CHECK((scale == nullptr) == (shift == nullptr) && (a_scale == nullptr) == (a_shift == nullptr) && (!want_stats || stats) &&
+              (pack_from < 0 || (packed && packed_written)));
+    CTX_ENTER(ctx);
+    const int ho = (h + 2 * pad - r) / stride + 1, wo = (w + 2 * pad - r) / stride + 1;
+    ARG_CHECK(ho >= 1 && wo >= 1);
+    const long long m = (long long)n * ho * wo;
+    ARG_CHECK(!want_stats || m % 128 == 0);
+    const size_t nin = (size_t)n * h * w * cin, nw = (size_t)cout * r * r * cin, nout = (size_t)m * cout;
+    const size_t nstats = want_stats ? (size_t)(m / 128) * cout * 2 : 0;
+    REID_TRY(conv_weights_splittable(ctx, wgt, nw, "reid_debug_conv_layer"));
+    float *dx, *dw, *dout, *dsc = nullptr, *dsh = nullptr, *dres = nullptr, *dasc = nullptr, *dash = nullptr, *dstats = nullptr;
+    _Float16* dpk = nullptr;
+    REID_TRY(ctx_ws(ctx, "dbgc.x", nin * 4, (void**)&dx));
+    REID_TRY(ctx_ws(ctx, "dbgc.w", nw * 4, (void**)&dw));
+    REID_TRY(ctx_ws(ctx, "dbgc.out", nout * 4, (void**)&dout));
+    HIP_TRY(hipMemcpyAsync(dx, x, nin * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dw, wgt, nw * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(dout, 0xff, nout * 4, ctx->stream));
+    if (scale) {
+        REID_TRY(ctx_ws(ctx, "dbgc.scale", (size_t)cout * 4, (void**)&dsc));
+        REID_TRY(ctx_ws(ctx, "dbgc.shift", (size_t)cout * 4, (void**)&dsh));
+        HIP_TRY(hipMemcpyAsync(dsc, scale, (size_t)cout * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(dsh, shift, (size_t)cout * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (residual) {
+        REID_TRY(ctx_ws(ctx, "dbgc.res", nout * 4, (void**)&dres));
+        HIP_TRY(hipMemcpyAsync(dres, residual, nout * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (a_scale) {   // the loader's input affine, per (image, input channel)
+        REID_TRY(ctx_ws(ctx, "dbgc.ascale", (size_t)n * cin * 4, (void**)&dasc));
+        REID_TRY(ctx_ws(ctx, "dbgc.ashift", (size_t)n * cin * 4, (void**)&dash));
+        HIP_TRY(hipMemcpyAsync(dasc, a_scale, (size_t)n * cin * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(dash, a_shift, (size_t)n * cin * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (want_stats) {
+        REID_TRY(ctx_ws(ctx, "dbgc.stats", nstats * 4, (void**)&dstats));
+        HIP_TRY(hipMemsetAsync(dstats, 0xff, nstats * 4, ctx->stream));
+    }
+    if (pack_from >= 0) {
+        REID_TRY(ctx_ws(ctx, "dbgc.packed", nout * 2 * 2, (void**)&dpk));
+        HIP_TRY(hipMemsetAsync(dpk, 0xff, nout * 2 * 2, ctx->stream));
+    }
+    REID_TRY(conv_weights_fresh(ctx, dw));
+    bool written = false;
+    REID_TRY(conv_gemm(ctx, A_IM2COL, dx, n, h, w, cin, dw, cout, r, r, stride, pad, r * r * cin, dasc, dash, a_relu, dsc, dsh, dres, relu,
+                       dstats, dout, relu_from, nullptr, dpk, pack_from < 0 ? 0 : pack_from, pack_from < 0 ? nullptr : &written));
+    HIP_TRY(hipMemcpyAsync(out, dout, nout * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (want_stats) HIP_TRY(hipMemcpyAsync(stats, dstats, nstats * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (dpk) HIP_TRY(hipMemcpyAsync(packed, dpk, nout * 2 * 2, hipMemcpyDeviceToHost, ctx->stream));
+    if (packed_written) *packed_written = written ? 1 : 0;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 // Timing experiments on the fused pair of linears: bit 0 = no weight refills after the first two steps, bit 1 = no block barriers.
 // The results are WRONG while a bit is set (which is why this lives here and not behind an environment variable of the library).
 extern "C" int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits) {

@@ -521,6 +521,8 @@ int conv_gemm(reid_ctx* ctx, int amode, const void* x, int n, int H, int W, int 
               const float* col_scale, const float* col_shift, const float* residual, int relu, float* stats, float* out,
               int relu_from = 0, const _Float16* x_packed = nullptr,
               _Float16* out_packed = nullptr, int pack_from = 0, bool* packed_written = nullptr);   // x_packed (precision 2): x already as [xh | xl']
+int conv_weights_fresh(reid_ctx* ctx, const float* d_w);   // drops the cached split form of a reused weight workspace (api.hip)
+int conv_weights_splittable(reid_ctx* ctx, const float* h_w, size_t count, const char* who);   // precision 2: host weights inside the split range
 int conv_gemm16(reid_ctx* ctx, int amode, const _Float16* x, int n, int H, int W, int Cin, const _Float16* wgt, int Cout,
                 int R, int S, int stride, int pad, int K, const float* col_scale, const float* col_shift,
                 const _Float16* residual, int relu, float* stats, _Float16* out, int Hp = 0, int Wp = 0);

@@ -445,6 +445,31 @@ class Engine:
         assert cnt.value == out.size
         return out
 
+    def debug_conv_layer(self, x, w, stride=1, pad=0, scale=None, shift=None, residual=None, relu=False, relu_from=0, pack_from=-1,
+                         stats=False, a_scale=None, a_shift=None, a_relu=False):
+        """One ResNet-trunk convolution through the forward's launcher (libreid_hip_debug.so reid_debug_conv_layer) in this context's
+        precision and switches.  x [n,h,w,cin], w [cout,r,r,cin] fp32.  Returns (out [n,ho,wo,cout] fp32, packed [m, 2 cout] uint16
+        f16 bits or None, stats [m / 128, cout, 2] or None); packed is None unless pack_from >= 0 and the launch wrote that form.
+        What the launch does not write reads as NaN."""
+        x, w = _f32(x), _f32(w)
+        n, h, ww, cin = x.shape
+        cout, r, s, wc = w.shape
+        if r != s or wc != cin:
+            raise ValueError("debug_conv_layer expects w[cout, r, r, cin] matching x")
+        ho, wo = (h + 2 * pad - r) // stride + 1, (ww + 2 * pad - r) // stride + 1
+        m = n * ho * wo
+        out = np.empty((n, ho, wo, cout), np.float32)
+        pk = np.empty((m, 2 * cout), np.uint16) if pack_from >= 0 else None
+        st = np.empty((m // 128, cout, 2), np.float32) if stats else None
+        opt = [_f32(a) if a is not None else None for a in (scale, shift, residual, a_scale, a_shift)]
+        written = C.c_int(0)
+        check(_ffi.debug_lib().reid_debug_conv_layer(
+            self.h, _ptr(x), C.c_int(n), C.c_int(h), C.c_int(ww), C.c_int(cin), _ptr(w), C.c_int(cout), C.c_int(r), C.c_int(stride),
+            C.c_int(pad), _ptr(opt[0]), _ptr(opt[1]), _ptr(opt[2]), C.c_int(int(bool(relu))), C.c_int(int(relu_from)),
+            C.c_int(int(pack_from)), C.c_int(int(bool(stats))), _ptr(opt[3]), _ptr(opt[4]), C.c_int(int(bool(a_relu))), _ptr(out),
+            _ptr(pk), _ptr(st), C.byref(written)))
+        return out, (pk if written.value else None), st
+
     def debug_swin_stage(self, stage, n, h=224, w=224):
         """Stage activations of the last Swin pass as NHWC arrays (0 sfe, 1..4 stage outputs, 5 GeM output [n,96])."""
         if stage == 5:
