@@ -52,6 +52,25 @@ int reid_debug_conv_layer(reid_ctx* ctx, const float* x, int n, int h, int w, in
                           int pad, const float* scale, const float* shift, const float* residual, int relu, int relu_from, int pack_from,
                           int want_stats, const float* a_scale, const float* a_shift, int a_relu, float* out, uint16_t* packed,
                           float* stats, int* packed_written);
+/* The kernels that finish a residual block and the neck (correctness harness, tests/test_gpu_tail.py), each through the launcher the
+ * forward calls, on host operands.  stats [n][tiles][c][2] (per-group sum, sum of squares), activations NHWC [n][hw][c]; f16 operands
+ * and results are raw f16 bits.  Every output the launch leaves alone reads as NaN (0xffff); each call returns the context's fault status.
+ * norm_finish: IBN finish of conv1, channels [0, half) InstanceNorm (in_gamma / in_beta [half]), [half, c) BatchNorm (bn_scale /
+ * bn_shift [c - half]).  form 0 norm_finalize -> a_scale / a_shift [n][c]; 1 in_apply on fp32 x -> out; 2 / 3 in_apply_pack with in_only
+ * 0 / 1 -> out16 [n hw][2c] ([xh | xl']) and out (x after the launch); 4 norm_apply_f16 on f16 x -> out16; 5 norm_finalize +
+ * affine_relu_f16 -> out16, a_scale, a_shift. */
+int reid_debug_norm_finish(reid_ctx* ctx, int form, int n, int hw, int c, int half, int tiles, const void* x, const float* stats,
+                           const float* in_gamma, const float* in_beta, const float* bn_scale, const float* bn_shift, float* out,
+                           uint16_t* out16, float* a_scale, float* a_shift);
+/* se_tail: SE gate + combine, out = relu(sigmoid(w2t^T relu(w1 pooled)) y + shortcut), w1 / w2t [mid][c].  form 0 se_finalize +
+ * se_combine -> out, gate [n][c]; 1-3 launch_se_tail's rule, 4-6 se_tail_kernel<false>, 7-9 se_tail_kernel<true>, each with fp32 out
+ * only / packed [n hw][2c] out16 only / both; 10 se_tail_f16 and 11 se_finalize + se_combine_f16 on f16 y / shortcut -> out16 (and
+ * gate for 11). */
+int reid_debug_se_tail(reid_ctx* ctx, int form, int n, int hw, int c, int mid, int tiles, const float* stats, const float* w1,
+                       const float* w2t, const void* y, const void* shortcut, float* out, uint16_t* out16, float* gate);
+/* gem_neck: GeM (exponent p) + BNNeck, emb = gem * scale + shift, on fp32 x (f16 = 0) or f16 x (f16 = 1); gem_out may be null. */
+int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale, const float* shift,
+                        float* gem_out, float* emb);
 /* Timing experiments on that kernel (WRONG results while set): bit 0 = no weight refills after the first two steps, bit 1 = no block
  * barriers.  0 restores the product behaviour. */
 int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits);

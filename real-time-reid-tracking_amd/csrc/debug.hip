@@ -517,6 +517,144 @@ extern "C" int reid_debug_conv_layer(reid_ctx* ctx, const float* x, int n, int h
     return ctx_fault_status(ctx);
 }
 
+// ------------------------------------------------------------------------------------------------ block tails (tests/test_gpu_tail.py)
+// The kernels that finish a residual block and the neck, each through the launcher the forward calls, on host operands.  Outputs are
+// set to 0xff bytes first (NaN / 0xffff where a launch leaves them alone); every call returns the context's fault status.
+namespace {
+template <class T>
+int dbg_upload(reid_ctx* ctx, const char* name, const T* host, size_t count, T** dev) {
+    *dev = nullptr;
+    if (!host) return REID_OK;
+    REID_TRY(ctx_ws(ctx, name, count * sizeof(T), (void**)dev));
+    HIP_TRY(hipMemcpyAsync(*dev, host, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    return REID_OK;
+}
+template <class T>
+int dbg_output(reid_ctx* ctx, const char* name, size_t count, T** dev) {
+    REID_TRY(ctx_ws(ctx, name, count * sizeof(T), (void**)dev));
+    HIP_TRY(hipMemsetAsync(*dev, 0xff, count * sizeof(T), ctx->stream));
+    return REID_OK;
+}
+template <class T>
+int dbg_download(reid_ctx* ctx, T* host, const T* dev, size_t count) {
+    if (host) HIP_TRY(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    return REID_OK;
+}
+}  // namespace
+
+extern "C" int reid_debug_norm_finish(reid_ctx* ctx, int form, int n, int hw, int c, int half, int tiles, const void* x, const float* stats,
+                                      const float* in_gamma, const float* in_beta, const float* bn_scale, const float* bn_shift, float* out,
+                                      uint16_t* out16, float* a_scale, float* a_shift) {
+    ARG_CHECK(ctx && form >= 0 && form <= 5 && n >= 1 && hw >= 1 && c >= 4 && half >= 4 && half <= c && tiles >= 1 && stats && in_gamma &&
+              in_beta);
+    ARG_CHECK((form == 0 || x) && (form != 1 || out) && (form < 2 || form > 5 || out16) && (form != 0 || (a_scale && a_shift)));
+    ARG_CHECK((form != 0 && form < 4) || half == c || (bn_scale && bn_shift));
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)n * hw * c, nab = (size_t)n * c, cb = (size_t)(c - half);
+    float *dst, *dg, *db, *dbs = nullptr, *dbh = nullptr, *dx = nullptr, *da = nullptr, *dbb = nullptr;
+    _Float16* dh = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgt.stats", stats, (size_t)n * tiles * c * 2, &dst));
+    REID_TRY(dbg_upload(ctx, "dbgt.gamma", in_gamma, (size_t)half, &dg));
+    REID_TRY(dbg_upload(ctx, "dbgt.beta", in_beta, (size_t)half, &db));
+    if (cb) {
+        REID_TRY(dbg_upload(ctx, "dbgt.bns", bn_scale, cb, &dbs));
+        REID_TRY(dbg_upload(ctx, "dbgt.bnh", bn_shift, cb, &dbh));
+    }
+    if (form == 0 || form == 5) {
+        REID_TRY(dbg_output(ctx, "dbgt.a", nab, &da));
+        REID_TRY(dbg_output(ctx, "dbgt.b", nab, &dbb));
+    }
+    if (form >= 1 && form <= 3) REID_TRY(dbg_upload(ctx, "dbgt.x", (const float*)x, nx, &dx));
+    if (form >= 4) REID_TRY(dbg_upload(ctx, "dbgt.x16", (const _Float16*)x, nx, &dh));
+    if (form == 2 || form == 3) REID_TRY(dbg_output(ctx, "dbgt.pk", nx * 2, &dh));
+    switch (form) {
+    case 0: REID_TRY(launch_norm_finalize(ctx, dst, n, tiles, c, half, hw, dg, db, dbs, dbh, da, dbb)); break;
+    case 1: REID_TRY(launch_in_apply(ctx, dx, dst, n, tiles, c, half, hw, dg, db)); break;
+    case 2:
+    case 3: REID_TRY(launch_in_apply_pack(ctx, dx, dst, n, tiles, c, half, hw, dg, db, dh, form == 3)); break;
+    case 4: REID_TRY(launch_norm_apply_f16(ctx, dh, dst, n, tiles, c, half, hw, dg, db, dbs, dbh)); break;
+    case 5:
+        REID_TRY(launch_norm_finalize(ctx, dst, n, tiles, c, half, hw, dg, db, dbs, dbh, da, dbb));
+        REID_TRY(launch_affine_relu_f16(ctx, dh, da, dbb, n, hw, c));
+        break;
+    }
+    if (dx) REID_TRY(dbg_download(ctx, out, dx, nx));
+    if (dh) REID_TRY(dbg_download(ctx, (_Float16*)out16, dh, form == 2 || form == 3 ? nx * 2 : nx));
+    if (da) {
+        REID_TRY(dbg_download(ctx, a_scale, da, nab));
+        REID_TRY(dbg_download(ctx, a_shift, dbb, nab));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_se_tail(reid_ctx* ctx, int form, int n, int hw, int c, int mid, int tiles, const float* stats, const float* w1,
+                                  const float* w2t, const void* y, const void* shortcut, float* out, uint16_t* out16, float* gate) {
+    ARG_CHECK(ctx && form >= 0 && form <= 11 && n >= 1 && hw >= 1 && c >= 4 && mid >= 1 && tiles >= 1 && stats && w1 && w2t && y && shortcut);
+    const bool f16 = form >= 10, tail = form >= 1 && form <= 9;
+    const bool want_out = !f16 && (!tail || ((form - 1) % 3 != 1)), want_pk = tail && (form - 1) % 3 != 0;
+    ARG_CHECK((!want_out || out) && ((!want_pk && !f16) || out16) && ((form != 0 && form != 11) || gate));
+    CTX_ENTER(ctx);
+    const size_t ny = (size_t)n * hw * c;
+    float *dst, *dw1, *dw2, *dy = nullptr, *dsc = nullptr, *dout = nullptr, *dgate = nullptr;
+    _Float16 *dy16 = nullptr, *dsc16 = nullptr, *dh = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgt.stats", stats, (size_t)n * tiles * c * 2, &dst));
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", w1, (size_t)mid * c, &dw1));
+    REID_TRY(dbg_upload(ctx, "dbgt.w2", w2t, (size_t)mid * c, &dw2));
+    if (f16) {
+        REID_TRY(dbg_upload(ctx, "dbgt.x16", (const _Float16*)y, ny, &dy16));
+        REID_TRY(dbg_upload(ctx, "dbgt.sc16", (const _Float16*)shortcut, ny, &dsc16));
+        REID_TRY(dbg_output(ctx, "dbgt.pk", ny, &dh));
+    } else {
+        REID_TRY(dbg_upload(ctx, "dbgt.x", (const float*)y, ny, &dy));
+        REID_TRY(dbg_upload(ctx, "dbgt.sc", (const float*)shortcut, ny, &dsc));
+        if (want_out) REID_TRY(dbg_output(ctx, "dbgt.out", ny, &dout));
+        if (want_pk) REID_TRY(dbg_output(ctx, "dbgt.pk", ny * 2, &dh));
+    }
+    if (form == 0 || form == 11) REID_TRY(dbg_output(ctx, "dbgt.a", (size_t)n * c, &dgate));
+    if (form == 0) {
+        REID_TRY(launch_se_finalize(ctx, dst, n, tiles, c, mid, hw, dw1, dw2, dgate));
+        REID_TRY(launch_se_combine(ctx, dy, dsc, dgate, n, hw, c, dout));
+    } else if (tail) {   // 1-3 the launcher's rule, 4-6 se_tail_kernel<false>, 7-9 <true>: fp32 out, packed, both
+        REID_TRY(launch_se_tail_form(ctx, (form - 1) / 3 - 1, dst, n, tiles, c, mid, hw, dw1, dw2, dy, dsc, dout, dh));
+    } else if (form == 10) {
+        REID_TRY(launch_se_tail_f16(ctx, dst, n, tiles, c, mid, hw, dw1, dw2, dy16, dsc16, dh));
+    } else {
+        REID_TRY(launch_se_finalize(ctx, dst, n, tiles, c, mid, hw, dw1, dw2, dgate));
+        REID_TRY(launch_se_combine_f16(ctx, dy16, dsc16, dgate, n, hw, c, dh));
+    }
+    if (dout) REID_TRY(dbg_download(ctx, out, dout, ny));
+    if (dh) REID_TRY(dbg_download(ctx, (_Float16*)out16, dh, f16 ? ny : ny * 2));
+    if (dgate) REID_TRY(dbg_download(ctx, gate, dgate, (size_t)n * c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale,
+                                   const float* shift, float* gem_out, float* emb) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && x && scale && shift && emb);
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)n * hw * c, ne = (size_t)n * c;
+    float *dx = nullptr, *dp, *dsc, *dsh, *dg = nullptr, *de;
+    _Float16* dh = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgt.p", &p, 1, &dp));
+    REID_TRY(dbg_upload(ctx, "dbgt.bns", scale, (size_t)c, &dsc));
+    REID_TRY(dbg_upload(ctx, "dbgt.bnh", shift, (size_t)c, &dsh));
+    if (gem_out) REID_TRY(dbg_output(ctx, "dbgt.a", ne, &dg));
+    REID_TRY(dbg_output(ctx, "dbgt.b", ne, &de));
+    if (f16) {
+        REID_TRY(dbg_upload(ctx, "dbgt.x16", (const _Float16*)x, nx, &dh));
+        REID_TRY(launch_gem_neck_f16(ctx, dh, n, hw, c, dp, dsc, dsh, dg, de));
+    } else {
+        REID_TRY(dbg_upload(ctx, "dbgt.x", (const float*)x, nx, &dx));
+        REID_TRY(launch_gem_neck(ctx, dx, n, hw, c, dp, dsc, dsh, dg, de));
+    }
+    if (dg) REID_TRY(dbg_download(ctx, gem_out, dg, ne));
+    REID_TRY(dbg_download(ctx, emb, de, ne));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 // Timing experiments on the fused pair of linears: bit 0 = no weight refills after the first two steps, bit 1 = no block barriers.
 // The results are WRONG while a bit is set (which is why this lives here and not behind an environment variable of the library).
 extern "C" int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits) {

@@ -405,8 +405,13 @@ __global__ __launch_bounds__(256) void gem_neck_kernel(const float* __restrict__
     const float* xi = x + (long long)img * hw * c + c0 + quad * 4;
     // x^p for a trained p (GeM's p is a parameter, initialised to 3: attention_pooling.py:58-60): exp2(p log2 x) on the transcendental
     // unit.  ocml's powf is ~50 instructions per element - 246 us per 1024-crop pass against 53 us for the p = 3 form; x >= 1e-6 and
-    // p in the low single digits keep both steps in their normal range, the error (~1e-6 of a term) is below the fp32 sum's own.
-    auto powp = [&](float f) { return __builtin_amdgcn_exp2f(p * __builtin_amdgcn_logf(f)); };
+    // p in the low single digits keep the logarithm in its normal range, the error (~1e-6 of a term) is below the fp32 sum's own.
+    // v_exp_f32 flushes a subnormal result to 0: below 2^-126 (a clamped 1e-6 at p > 6.3, where torch's pow keeps ~1e-39) the exponent
+    // is raised by 64 and the result scaled back, one rounding into the subnormal range.  At or above 2^-126 the bits are unchanged.
+    auto powp = [&](float f) {
+        const float e = p * __builtin_amdgcn_logf(f);
+        return e < -126.f ? __builtin_amdgcn_exp2f(e + 64.f) * 0x1p-64f : __builtin_amdgcn_exp2f(e);
+    };
     int px = pg;
     for (; px + 7 * 16 < hw; px += 8 * 16) {
         f32x4 v[8];
@@ -559,12 +564,17 @@ int tail_slices(int n_img, int hw) {
 
 int launch_se_tail(reid_ctx* ctx, const float* stats, int n_img, int tiles, int c, int mid, int hw, const float* w1, const float* w2,
                    const float* y, const float* sc, float* out, _Float16* packed) {
-    ARG_CHECK(c % 4 == 0 && c <= 512 && mid <= 64 && (out || packed));
+    return launch_se_tail_form(ctx, -1, stats, n_img, tiles, c, mid, hw, w1, w2, y, sc, out, packed);
+}
+
+int launch_se_tail_form(reid_ctx* ctx, int form, const float* stats, int n_img, int tiles, int c, int mid, int hw, const float* w1,
+                        const float* w2, const float* y, const float* sc, float* out, _Float16* packed) {
+    ARG_CHECK(c % 4 == 0 && c <= 512 && mid <= 64 && (out || packed) && form >= -1 && form <= 1 && (form != 1 || mid <= 32));
     const int slices = tail_slices(n_img, hw);
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n_img * hw * c * 12.0);
     // a tracking frame, layer 4 (64 KB of w1 + 64 KB of w2 per gate): the gate's weights requested up front, 18 -> 14 us per launch;
     // the smaller layers' launches have more blocks than gate work and lose with it (layer 1: 16 -> 31 us)
-    if ((long long)slices * n_img <= 512 && c >= 512 && mid <= 32)
+    if (form < 0 ? (long long)slices * n_img <= 512 && c >= 512 && mid <= 32 : form == 1)
         hipLaunchKernelGGL(se_tail_kernel<true>, dim3(slices, n_img), dim3(256), 0, ctx->stream, stats, tiles, c, mid, hw, w1, w2, y, sc,
                            hw / slices, out, packed, ctx->fault);
     else

@@ -264,6 +264,10 @@ int launch_se_finalize(reid_ctx*, const float* stats, int n_img, int tiles, int 
 int tail_slices(int n_img, int hw);   // elementwise.hip: blocks per image of the fused tail kernels
 int launch_se_tail(reid_ctx*, const float* stats, int n_img, int tiles, int c, int mid, int hw, const float* w1, const float* w2,
                    const float* y, const float* sc, float* out, _Float16* packed = nullptr);   // packed: also [oh | ol'] f16 [.., 2c]
+// the same launch with its kernel chosen by the caller (correctness harness): form -1 = launch_se_tail's rule, 0 = se_tail_kernel<false>,
+// 1 = se_tail_kernel<true> (mid <= 32)
+int launch_se_tail_form(reid_ctx*, int form, const float* stats, int n_img, int tiles, int c, int mid, int hw, const float* w1,
+                        const float* w2, const float* y, const float* sc, float* out, _Float16* packed);
 int launch_se_combine(reid_ctx*, const float* y, const float* sc, const float* s, int n_img, int hw, int c, float* out);
 int launch_in_apply_pack(reid_ctx*, const float* x, const float* stats, int n_img, int tiles, int c, int half, int hw,
                          const float* in_gamma, const float* in_beta, _Float16* packed,   // precision 2: IBN finish -> [xh | xl']

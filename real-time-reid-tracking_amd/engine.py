@@ -470,6 +470,60 @@ class Engine:
             _ptr(pk), _ptr(st), C.byref(written)))
         return out, (pk if written.value else None), st
 
+    def debug_norm_finish(self, form, x, stats, in_gamma, in_beta, bn_scale=None, bn_shift=None, hw=None):
+        """The IBN finish of conv1 through the forward's launcher (libreid_hip_debug.so reid_debug_norm_finish).  x [n, hw, c] (fp32,
+        or uint16 f16 bits for forms 4 and 5) or None for form 0; stats [n, tiles, c, 2]; in_gamma / in_beta [half].  Returns
+        (out, out16, a_scale, a_shift), None where the form has no such output: out [n, hw, c] fp32 (forms 1-3), out16 [n hw, 2c]
+        (forms 2-3) or [n, hw, c] (forms 4-5) uint16, a_scale / a_shift [n, c] (forms 0, 5).  Form 0 takes the image size as hw.
+        Unwritten outputs read as NaN."""
+        stats = _f32(stats)
+        n, tiles, c, _ = stats.shape
+        half = int(np.asarray(in_gamma).size)
+        hw = int(hw) if x is None else x.shape[1]
+        xa = None if form == 0 else (np.ascontiguousarray(x, np.uint16) if form >= 4 else _f32(x))
+        out = np.empty((n, hw, c), np.float32) if 1 <= form <= 3 else None
+        o16 = np.empty((n * hw, 2 * c), np.uint16) if form in (2, 3) else (np.empty((n, hw, c), np.uint16) if form >= 4 else None)
+        ab = [np.empty((n, c), np.float32) for _ in range(2)] if form in (0, 5) else [None, None]
+        opt = [_f32(a) if a is not None else None for a in (in_gamma, in_beta, bn_scale, bn_shift)]
+        check(_ffi.debug_lib().reid_debug_norm_finish(
+            self.h, C.c_int(form), C.c_int(n), C.c_int(hw), C.c_int(c), C.c_int(half), C.c_int(tiles), _ptr(xa), _ptr(stats),
+            _ptr(opt[0]), _ptr(opt[1]), _ptr(opt[2]), _ptr(opt[3]), _ptr(out), _ptr(o16), _ptr(ab[0]), _ptr(ab[1])))
+        return out, o16, ab[0], ab[1]
+
+    def debug_se_tail(self, form, stats, w1, w2t, y, shortcut):
+        """The SE gate + combine through the forward's launchers (libreid_hip_debug.so reid_debug_se_tail; forms in
+        include/reid_hip_debug.h).  stats [n, tiles, c, 2], w1 / w2t [mid, c], y / shortcut [n, hw, c] (fp32, or uint16 f16 bits for
+        forms 10-11).  Returns (out [n, hw, c] fp32, out16 [n hw, 2c] packed or [n, hw, c] f16 bits, gate [n, c]), None where the form
+        has no such output.  Unwritten outputs read as NaN."""
+        stats = _f32(stats)
+        n, tiles, c, _ = stats.shape
+        mid = w1.shape[0]
+        hw = y.shape[1]
+        f16 = form >= 10
+        cv = (lambda a: np.ascontiguousarray(a, np.uint16)) if f16 else _f32
+        ya, sa = cv(y), cv(shortcut)
+        tail = 1 <= form <= 9
+        want_out = not f16 and (not tail or (form - 1) % 3 != 1)
+        want_pk = tail and (form - 1) % 3 != 0
+        out = np.empty((n, hw, c), np.float32) if want_out else None
+        o16 = np.empty((n, hw, c), np.uint16) if f16 else (np.empty((n * hw, 2 * c), np.uint16) if want_pk else None)
+        gate = np.empty((n, c), np.float32) if form in (0, 11) else None
+        check(_ffi.debug_lib().reid_debug_se_tail(
+            self.h, C.c_int(form), C.c_int(n), C.c_int(hw), C.c_int(c), C.c_int(mid), C.c_int(tiles), _ptr(stats), _ptr(_f32(w1)),
+            _ptr(_f32(w2t)), _ptr(ya), _ptr(sa), _ptr(out), _ptr(o16), _ptr(gate)))
+        return out, o16, gate
+
+    def debug_gem_neck(self, x, p, scale, shift, f16=False):
+        """GeM + BNNeck through the forward's launcher (libreid_hip_debug.so reid_debug_gem_neck).  x [n, hw, c] fp32 (or uint16 f16
+        bits with f16=True).  Returns (gem [n, c], emb [n, c])."""
+        x = np.ascontiguousarray(x, np.uint16) if f16 else _f32(x)
+        n, hw, c = x.shape
+        g, e = np.empty((n, c), np.float32), np.empty((n, c), np.float32)
+        check(_ffi.debug_lib().reid_debug_gem_neck(
+            self.h, C.c_int(int(bool(f16))), C.c_int(n), C.c_int(hw), C.c_int(c), C.c_float(p), _ptr(x), _ptr(_f32(scale)),
+            _ptr(_f32(shift)), _ptr(g), _ptr(e)))
+        return g, e
+
     def debug_swin_stage(self, stage, n, h=224, w=224):
         """Stage activations of the last Swin pass as NHWC arrays (0 sfe, 1..4 stage outputs, 5 GeM output [n,96])."""
         if stage == 5:
