@@ -5,18 +5,20 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Default = every BASELINE configuration in ONE JSON line: configs[1] is the headline (`value`, `roofline`, `cpu_baseline` at the
-top level, as the contract asks), configs[0]'s batch size / configs[2] / configs[4] / configs[3] follow as the sub-objects
-`batch256`, `swin`, `market`, `tracking`, each with its own `roofline` and bounded `cpu_baseline` (run_all).
+Default = the headline alone: set up, W warm-up steps, K timed steps, --dump-outputs if given, ONE JSON line (`value`,
+`ms_per_step`, the configuration).  --full = every BASELINE configuration in ONE JSON line: configs[1] is the headline (`value`,
+`roofline`, `cpu_baseline` at the top level, the other arithmetic modes as side runs), configs[0]'s batch size / configs[2] /
+configs[4] / configs[3] follow as the sub-objects `batch256`, `swin`, `market`, `tracking`, each with its own `roofline` and
+bounded `cpu_baseline` (run_all).
 Headline = BASELINE configs[1] on every rank: embed 4096 synthetic uint8 crops (128x256, already resident in HBM)
 with ResNet18-IBN-SE in fp32-class arithmetic (--precision f16x3, the default: fp32 storage, convolutions as three f16 matrix-core
-products per multiply on hi/lo-split operands, fp32 accumulate - held to the exact-fp32 mode's parity bar; the exact-fp32 and the
-fp16-storage modes are measured in the same run as `f32_path` / `f16_path`), [N>1: ONE RCCL all-gather of the 512-d embeddings, issued through
+products per multiply on hi/lo-split operands, fp32 accumulate - held to the exact-fp32 mode's parity bar; with --full the exact-fp32
+and the fp16-storage modes are measured in the same run as `f32_path` / `f16_path`), [N>1: ONE RCCL all-gather of the 512-d embeddings, issued through
 the C ABI - csrc/comm.hip, no torch.distributed on the data path], then the L2 distance matrix of this rank's 4096
 embeddings against all gathered ones.  Weak scaling: per-GPU work is fixed, value = crops of ALL ranks / max-over-ranks
 time.  Prints ONE JSON line on rank 0.
 
-One configuration alone, same launch line plus --workload (embed = the headline alone):
+One configuration alone, same launch line plus --full --workload (embed = the headline alone, also without --full):
     --workload swin      configs[2]: Swin-T v1, 4096 images 224x224 per rank (weak)
     --workload tracking  configs[3]: 600-frame detection stream, each frame's crops dealt round-robin to the ranks,
                          all-gather of the frame's embeddings, feature-bank cost + DIoU on every rank (strong)
@@ -245,11 +247,14 @@ def run_embed(job, args):
         parallel.distmat_row_block(eng, emb_all, lo, hi, _ffi.METRIC_L2, distmat)
 
     def run(precision, steps, warmup, dump=None):
-        """Timed region per the bench contract + a profiled repeat of the same steps for the roofline object."""
+        """Timed region per the bench contract; with --full, a profiled repeat of the same steps for the roofline object."""
         eng.set_precision({"f32": 0, "f16": 1, "f16x3": 2}[precision])
         elapsed = job.timed(step, steps, warmup)
         if dump and rank == 0:
             dump_outputs(dump, {"embeddings": emb_all, "distmat": distmat})
+        res = {"value": round(n * world * steps / elapsed, 1), "ms_per_step": round(elapsed * 1e3 / steps, 3)}
+        if not args.full:
+            return res
         # split of one step (embed / all-gather+distmat), HIP events on the launch stream
         eng.timer_start()
         parallel.embed_sharded_dev(eng, comm, crops.ptr, n, n * world, emb_all, emb_local.ptr)
@@ -274,8 +279,7 @@ def run_embed(job, args):
         # per ALGORITHMIC flop
         peak = PEAK_F16_MFMA_TFLOPS if f16 else PEAK_F16_MFMA_TFLOPS / 3.0 if x3 else PEAK_F32_MFMA_TFLOPS
         conv_tflops = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if conv["ms"] > 0 else 0.0
-        return {
-            "value": round(n * world * steps / elapsed, 1), "ms_per_step": round(elapsed * 1e3 / steps, 3),
+        res.update({
             "embed_ms": round(embed_ms, 3), "embed_crops_per_s_per_gpu": round(n / (embed_ms * 1e-3), 1),
             "distmat_ms": round(match_ms, 3),
             "whole_net_fraction_of_mfma_peak": round(FLOP_PER_CROP * n / (embed_ms * 1e-3) / 1e12 / peak, 4),
@@ -299,9 +303,36 @@ def run_embed(job, args):
                 "elementwise": {"ms_per_step": round(elt["ms"] / steps, 3),
                                 "gbs": round(elt["bytes"] / max(elt["ms"], 1e-9) / 1e6, 1)},
             },
-        }
+        })
+        return res
 
     main_res = run(args.precision, args.steps, args.warmup, args.dump_outputs)
+    arith = {"f32": "exact fp32 (v_mfma_f32_32x32x2_f32), the reference's arithmetic",
+             "f16": "fp16 storage, fp32 accumulate (north_star tolerance 1e-3 cosine; measured below)",
+             "f16x3": "fp32-class: fp32 storage; every convolution as three f16 matrix-core products per multiply on hi/lo-split "
+                      "operands, fp32 accumulate (held to the exact-fp32 mode's parity thresholds in tests/test_gpu_parity.py)"}
+    out = {
+        "metric": "crops/sec embedded + NxM distmat ms, ResNet18-SE 128x256",
+        "value": main_res["value"],
+        "unit": "crops/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": main_res["ms_per_step"],
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.precision,
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: ResNet18-SE embed %d distinct uint8 crops (128x256) per GPU + %dx%d L2 distmat"
+                               % (n, n, n * world),
+                   "crops_per_gpu": n, "embed_dim": d, "chunk": args.chunk,
+                   "arithmetic": arith[args.precision],
+                   "sharding": ("crops sharded by rank, one RCCL all-gather of [N,512] embeddings through the C ABI (reid_allgather_dev)"
+                                if world > 1 else "single GPU")},
+    }
+    if not args.full:                  # a plain run ends here: the side runs, roofline, parity and cpu_baseline are --full's
+        return out if rank == 0 else None
     others = {} if args.single else {o: run(o, max(1, min(3, args.steps)), 1) for o in ("f32", "f16x3", "f16") if o != args.precision}
     sustained = sustained_mfma(eng)
     if sustained is not None:
@@ -327,32 +358,8 @@ def run_embed(job, args):
     if rank != 0:
         return None
     f16 = args.precision == "f16"
-    arith = {"f32": "exact fp32 (v_mfma_f32_32x32x2_f32), the reference's arithmetic",
-             "f16": "fp16 storage, fp32 accumulate (north_star tolerance 1e-3 cosine; measured below)",
-             "f16x3": "fp32-class: fp32 storage; every convolution as three f16 matrix-core products per multiply on hi/lo-split "
-                      "operands, fp32 accumulate (held to the exact-fp32 mode's parity thresholds in tests/test_gpu_parity.py)"}
-    out = {
-        "metric": "crops/sec embedded + NxM distmat ms, ResNet18-SE 128x256",
-        "value": main_res["value"],
-        "unit": "crops/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": main_res["ms_per_step"],
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": args.precision,
-        "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: ResNet18-SE embed %d distinct uint8 crops (128x256) per GPU + %dx%d L2 distmat"
-                               % (n, n, n * world),
-                   "crops_per_gpu": n, "embed_dim": d, "chunk": args.chunk,
-                   "arithmetic": arith[args.precision],
-                   "sharding": ("crops sharded by rank, one RCCL all-gather of [N,512] embeddings through the C ABI (reid_allgather_dev)"
-                                if world > 1 else "single GPU")},
-        "f16_vs_f32_max_cosine_err": cos_err,
-        "f16x3_vs_f32": x3_err,
-    }
+    out["f16_vs_f32_max_cosine_err"] = cos_err
+    out["f16x3_vs_f32"] = x3_err
     out.update({k: v for k, v in main_res.items() if k not in ("value", "ms_per_step")})
     for o, r in others.items():
         r["arithmetic"] = arith[o]
@@ -827,7 +834,7 @@ SUB_KEYS = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "scalin
 
 
 def run_all(job, args):
-    """The default line: BASELINE configs[1] as the headline (value / roofline / cpu_baseline as before) plus the other
+    """The --full line: BASELINE configs[1] as the headline (value / roofline / cpu_baseline as before) plus the other
     configurations as sub-objects of the SAME JSON line, each with its own roofline and bounded cpu_baseline:
     `batch256` (configs[0]'s size: 256 crops + 256 x 256 distmat), `swin` (configs[2]), `market` (configs[4]), `tracking`
     (configs[3] stand-in, exact fp32 with the fp16-storage run nested as f16_path).  A sub-workload that raises is reported as
@@ -1064,19 +1071,23 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything, not only the headline: the other arithmetic modes, roofline and per-kernel "
+                         "figures, parity of the modes, cpu_baseline, and with --workload all the other configurations")
     ap.add_argument("--workload", choices=["all", "embed", "batch256", "swin", "tracking", "market", "host"], default="all",
-                    help="all (default) = BASELINE configs[1] as the headline + the other configurations as sub-objects of the same "
-                         "line; embed = configs[1] alone; batch256 / swin / tracking / market = that configuration as its own line; "
-                         "host = configs[1] in the headline arithmetic only + the host_path sub-object (Extractor on host crops)")
+                    help="all (default) = BASELINE configs[1] as the headline + (--full) the other configurations as sub-objects of "
+                         "the same line; embed = configs[1] alone; with --full only: batch256 / swin / tracking / market = that "
+                         "configuration as its own line; host = configs[1] in the headline arithmetic only + the host_path "
+                         "sub-object (Extractor on host crops)")
     ap.add_argument("--crops", type=int, default=4096, help="crops (images) per GPU per step (BASELINE config 2 / 3: 4096)")
     ap.add_argument("--frames", type=int, default=600, help="--workload tracking: frames of the stream")
     ap.add_argument("--match-stream", type=int, default=1,
                     help="tracking: 0 = cost / update stages of the frame pipeline on the compute stream (rounds 3-5) instead of a stream of their own; 2 = on their own stream even beside a communicator")
     ap.add_argument("--chunk", type=int, default=int(os.environ.get("REID_CHUNK", "1024")))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline legs")
     ap.add_argument("--cameras", type=int, default=2, help="--workload tracking, one GPU: also run this many concurrent camera streams")
     ap.add_argument("--no-pipeline", action="store_true", help="--workload tracking: one synchronous call per operation (A/B)")
-    ap.add_argument("--single", action="store_true", help="measure only --precision (skip the other arithmetic)")
+    ap.add_argument("--single", action="store_true", help="--full: measure only --precision (skip the other arithmetic)")
     ap.add_argument("--precision", choices=["f32", "f16", "f16x3"], default=os.environ.get("REID_PRECISION", "f16x3"),
                     help="arithmetic of the headline: f16x3 (default) = fp32-class - fp32 storage, every convolution as "
                          "three f16 matrix-core products per multiply on hi/lo-split operands with fp32 accumulation; it meets the "
@@ -1092,6 +1103,8 @@ def main(argv=None):
         ap.error("--gpus must be >= 1")
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if not args.full and args.workload not in ("all", "embed"):
+        ap.error("--workload %s: only with --full" % args.workload)
     if args.dump_outputs and args.workload == "tracking":
         ap.error("--dump-outputs: not available for --workload tracking")
     if args.dump_outputs:
@@ -1117,7 +1130,7 @@ def main(argv=None):
             if o is not None and job_.world == 1:
                 o["host_path"] = host_path(job_, o, a)
             return o
-        fn = {"all": run_all, "embed": run_embed, "batch256": run_embed, "swin": run_swin, "tracking": run_tracking,
+        fn = {"all": run_all if args.full else run_embed, "embed": run_embed, "batch256": run_embed, "swin": run_swin, "tracking": run_tracking,
               "market": run_market, "host": run_host}[args.workload]
         out = fn(job, args)
         if out is not None:

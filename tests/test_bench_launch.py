@@ -50,19 +50,38 @@ def test_bench_refuses_a_launcher_that_disagrees_with_gpus():
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("gpus,rank0_delay", [(1, 0.0), (2, 0.0), (2, 4.0)])
 def test_lost_sub_workload_ends_the_job_with_a_nonzero_exit_code(gpus, rank0_delay):
-    """batch256 (the second weight load of the default line) never returns on the last rank: the watchdog prints what the headline
+    """batch256 (the second weight load of the --full line) never returns on the last rank: the watchdog prints what the headline
     measured, with the failure recorded in the sub-object, and every rank leaves with status 3.  Every rank's watchdog fires on its
     own clock and the launcher takes the others down as soon as one has left - so a rank other than 0 waits for rank 0's "line is
     out" flag first (for what is left of the sub-workload's limit plus a margin).  The order that used to lose the line is FORCED
     once instead of hoped for in five repetitions: rank 0's watchdog is held back by 4 s (REID_BENCH_TEST_RANK0_WATCHDOG_DELAY), so
     rank 1 notices first, and the partial line must still come out."""
-    r = _bench(["--gpus", str(gpus)] + SMALL, 280, REID_STANDIN_HANG_AT_LOAD=2, REID_STANDIN_HANG_RANK=gpus - 1, REID_BENCH_LIMIT_SCALE=0.03,
+    r = _bench(["--gpus", str(gpus), "--full"] + SMALL, 280, REID_STANDIN_HANG_AT_LOAD=2, REID_STANDIN_HANG_RANK=gpus - 1, REID_BENCH_LIMIT_SCALE=0.03,
                REID_BENCH_TEST_RANK0_WATCHDOG_DELAY=rank0_delay)
     assert r.returncode != 0, (r.stdout, r.stderr[-3000:])
     out = _one_line(r)
     assert out["value"] > 0 and "error" in out["batch256"]
     if gpus == 1:
         assert r.returncode == 3
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_is_the_headline_alone():
+    """Without --full the line is the headline's timed steps and nothing else: no side runs of the other arithmetic modes, no
+    roofline or cpu_baseline, no sub-workloads; --full still adds them, and the other configurations are refused without it."""
+    head = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config"}
+    small = ["--crops", "8", "--steps", "2", "--warmup", "1"]
+    r = _bench(["--gpus", "1"] + small, 280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _one_line(r)
+    assert set(out) == head and out["steps"] == 2 and out["warmup"] == 1 and out["value"] > 0 and out["dtype"] == "f16x3"
+    r = _bench(["--gpus", "1", "--full", "--workload", "embed", "--no-cpu"] + small, 280)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _one_line(r)
+    assert head < set(out) and {"roofline", "f32_path", "f16_path", "f16x3_vs_f32"} <= set(out)
+    r = _bench(["--gpus", "1", "--workload", "swin"] + small, 60)
+    assert r.returncode == 2 and r.stdout.strip() == "" and "--full" in r.stderr
 
 
 @pytest.mark.timeout(300)

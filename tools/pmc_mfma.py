@@ -1,7 +1,7 @@
 """MFMA-pipe utilisation per kernel from one rocprofv3 PMC pass (SQ_VALU_MFMA_BUSY_CYCLES, SQ_BUSY_CYCLES, GRBM_GUI_ACTIVE, SQ_WAVES):
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d out -o p -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu --single
+    rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d out -o p -- python3 $REPO/bench.py --full --steps 1 --warmup 1 --no-cpu --single
     python3 tools/pmc_mfma.py out/p_results.db > profiles/rNN_mfma_util_<mode>.json
 
 Reading (MI355X_MICROARCH.md, cycle constants + DVFS give-back): SQ_VALU_MFMA_BUSY_CYCLES counts matrix-pipe cycles summed over the
