@@ -162,8 +162,12 @@ int reid_debug_stage(reid_ctx* ctx, int stage, float* out_host, size_t max_float
  * 5 = GeM_1D output [n][96]; valid after a reid_swin_embed_* call that ran as one pass (n <= min(chunk, 1024)) */
 int reid_debug_swin_stage(reid_ctx* ctx, int stage, float* out_host, size_t max_floats, size_t* count);
 
-/* ---- Swin-T backbone (reference "v1": reid/backbones/swin_transformer.py:339-427, swin_t :508-513) -------------------
- * Packed weights from reid_amd.weights.pack_swin.  Input: normalised float images fp32[n][3][h][w] NCHW with h, w multiples
+/* ---- Swin-T backbone (reference: reid/backbones/swin_transformer.py:339-427, swin_t :508-513; versions "v1" and "v2") ----
+ * Packed weights from reid_amd.weights.pack_swin.  The manifest says which version the blob holds: the entry `swin.version` (one
+ * float, 1 or 2; absent = 1).  v1 blocks (pre-norm, q.k / sqrt(32) + a 13x13 position table: `.pos`) or v2 blocks (:140-149,205-209,
+ * 238-246: post-norm, cosine attention times a scale per head, plus a position bias per head - `.scale` [heads] already clamped and
+ * exponentiated, `.bias` [heads][49][49] = meta_mlp evaluated by the packer).  reid_swin_load reads it; the embed calls, the mode-2
+ * weight-range refusal and reid_ctx_precision_ok(ctx, 1, mode) serve both versions.  Input: normalised float images fp32[n][3][h][w] NCHW with h, w multiples
  * of 224 (the reference rejects 128x256); output: 96-d BatchNorm'd embedding (x_norm, :421) and logits. */
 int reid_swin_load(reid_ctx* ctx, const float* blob, size_t n_floats, const char* manifest);
 int reid_swin_dims(reid_ctx* ctx, int* embed_dim, int* num_class);

@@ -71,6 +71,17 @@ int reid_debug_se_tail(reid_ctx* ctx, int form, int n, int hw, int c, int mid, i
 /* gem_neck: GeM (exponent p) + BNNeck, emb = gem * scale + shift, on fp32 x (f16 = 0) or f16 x (f16 = 1); gem_out may be null. */
 int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale, const float* shift,
                         float* gem_out, float* emb);
+/* The two kernels of the Swin "v2" blocks alone (csrc/swin_v2.hip; correctness harnesses, tests/test_gpu_swin_v2.py), each through the
+ * launcher the forward calls, on host operands; f16 results are raw f16 bits; each call returns the context's fault status.
+ * window_attn_cos: cosine window attention of n maps of h x w tokens (multiples of 7), qkv fp32 [n h w][3 heads 32] (q | k | v, head-major),
+ * bias [heads][49 queries][49 keys], scale [heads] (already clamped and exponentiated).  mode 0: fp32 in -> out fp32 [tokens][heads 32];
+ * mode 2: fp32 in -> out16 [tokens][2 heads 32] = [oh | ol'] (ol' = f16((o - oh) 2^11)); mode 1: qkv rounded to f16 -> out16 [tokens][heads 32]. */
+int reid_debug_window_attn_cos(reid_ctx* ctx, int mode, const float* qkv, int n, int h, int w, int heads, int shifted, const float* bias,
+                               const float* scale, float* out, uint16_t* out16);
+/* post_norm: out = x + (LayerNorm(y) g + b) over t rows of c channels (eps 1e-5), x / y / out fp32 [t][c]; side 0: out only, 1: out16 = f16
+ * copy of out [t][c], 2: out16 = [oh | ol'] [t][2c].  in_place != 0: the launch writes out over its own x. */
+int reid_debug_post_norm(reid_ctx* ctx, int side, const float* x, const float* y, int t, int c, const float* g, const float* b, int in_place,
+                         float* out, uint16_t* out16);
 /* Timing experiments on that kernel (WRONG results while set): bit 0 = no weight refills after the first two steps, bit 1 = no block
  * barriers.  0 restores the product behaviour. */
 int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits);

@@ -259,8 +259,11 @@ def emares18_ibn(num_classes=751, loss="triplet", pretrained=False, use_gpu=True
 
 
 class SwinT:
-    """The reference's custom Swin-T, version "v1" (reid/backbones/swin_transformer.py:339-427, swin_t :508-513): conv stem,
-    4 stages of (W-MSA, SW-MSA) blocks, top-down ConvTranspose fusion, LN -> GeM_1D -> BatchNorm1d(96).
+    """The reference's custom Swin-T (reid/backbones/swin_transformer.py:339-427, swin_t :508-513): conv stem,
+    4 stages of (W-MSA, SW-MSA) blocks, top-down ConvTranspose fusion, LN -> GeM_1D -> BatchNorm1d(96).  ``version="v1"`` (default):
+    pre-norm blocks, scaled dot-product attention with a 13x13 relative-position table; ``version="v2"``: post-norm blocks, cosine
+    attention with a learned scale per head and a position bias from meta_mlp (:140-149,205-209,238-246) - the reference's
+    ``--backbone swin_v2``.  The state_dict speaks the reference's keys of that version.
 
     ``model(x)`` -> embedding [N,96] (x_norm); ``model(x, return_logits=True)`` -> (logits, embedding), the order of the
     reference's eval-mode tuple (:422-423).  ``x``: float [N,3,H,W] with H, W multiples of 224 - the
@@ -273,7 +276,10 @@ class SwinT:
     _arch = "swin"            # precision.run: which of the shared engine's two weight sets this object owns
 
     def __init__(self, num_classes=751, loss="softmax", pretrained=False, use_gpu=True, seed=0, camera=0, sequence=0, side_info=True,
-                 side_info_coeff=1.5, precision=None, **_):
+                 side_info_coeff=1.5, precision=None, version="v1", **_):
+        if version not in synth.SWIN_VERSIONS:
+            raise ValueError("swin_t: version must be 'v1' or 'v2', got %r" % (version,))
+        self.version = version
         self._mode = _precision.resolve(precision)
         self.num_classes = num_classes
         self.loss = loss
@@ -282,7 +288,7 @@ class SwinT:
         # ShadowFeatureExtraction's side-information table (swin_transformer.py:285-293): camera * sequence, camera or sequence rows
         self.views = camera * sequence if camera * sequence > 0 else camera if camera > 0 else max(sequence, 0)
         self.side_info, self.side_info_coeff = bool(side_info), float(side_info_coeff)
-        self._sd = synth.swin_state_dict(seed, num_class=num_classes, views=self.views)
+        self._sd = synth.swin_state_dict(seed, num_class=num_classes, views=self.views, version=version)
         self._dirty = True
         if pretrained:
             import warnings

@@ -811,3 +811,69 @@ extern "C" int reid_debug_comm_loopback(reid_ctx** ctxs, int world) {
     }
     return REID_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ Swin v2 kernels alone
+// window_attn_cos_kernel (swin_v2.hip) through the launcher the forward calls, on host operands: qkv fp32 [n H W][3 heads 32]
+// (mode 1: rounded to f16 on the device first), bias [heads][49 queries][49 keys], scale [heads].  mode 0 -> out fp32 [tokens][C];
+// mode 2 -> out16 = [oh | ol'] raw f16 bits [tokens][2C]; mode 1 -> out16 raw f16 bits [tokens][C].
+extern "C" int reid_debug_window_attn_cos(reid_ctx* ctx, int mode, const float* qkv, int n, int h, int w, int heads, int shifted,
+                                          const float* bias, const float* scale, float* out, uint16_t* out16) {
+    ARG_CHECK(ctx && mode >= 0 && mode <= 2 && qkv && bias && scale && n >= 1 && heads >= 1 && heads <= 64 && h >= 7 && w >= 7 && h % 7 == 0 &&
+              w % 7 == 0);
+    ARG_CHECK(mode == 0 ? out != nullptr : out16 != nullptr);
+    CTX_ENTER(ctx);
+    const int C = heads * 32;
+    const size_t T = (size_t)n * h * w;
+    std::vector<float> bt((size_t)heads * 49 * 64, 0.f);   // [head][key][query padded to 64], as reid_swin_load makes it
+    for (int hd = 0; hd < heads; ++hd)
+        for (int query = 0; query < 49; ++query)
+            for (int key = 0; key < 49; ++key) bt[((size_t)hd * 49 + key) * 64 + query] = bias[((size_t)hd * 49 + query) * 49 + key];
+    float *dq, *dbt, *dsc, *dout = nullptr;
+    _Float16 *dq16 = nullptr, *dout16 = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgv2.qkv", qkv, T * 3 * C, &dq));
+    REID_TRY(dbg_upload(ctx, "dbgv2.bt", bt.data(), bt.size(), &dbt));
+    REID_TRY(dbg_upload(ctx, "dbgv2.sc", scale, (size_t)heads, &dsc));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));            // bt is a local
+    const void* src = dq;
+    void* dst;
+    if (mode == 1) {
+        REID_TRY(ctx_ws(ctx, "dbgv2.q16", T * 3 * C * 2, (void**)&dq16));
+        REID_TRY(launch_f32_to_f16(ctx, dq, T * 3 * C, dq16));
+        src = dq16;
+    }
+    if (mode == 0) {
+        REID_TRY(dbg_output(ctx, "dbgv2.out", T * C, &dout));
+        dst = dout;
+    } else {
+        REID_TRY(dbg_output(ctx, "dbgv2.o16", T * C * (mode == 2 ? 2 : 1), &dout16));
+        dst = dout16;
+    }
+    REID_TRY(launch_window_attn_cos(ctx, mode, src, 3 * C, n, h, w, heads, shifted, dbt, dsc, dst));
+    if (mode == 0) REID_TRY(dbg_download(ctx, out, dout, T * C));
+    else REID_TRY(dbg_download(ctx, (_Float16*)out16, dout16, T * C * (mode == 2 ? 2 : 1)));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// post_norm_kernel (swin_v2.hip) through its launcher: out = x + (LayerNorm(y) g + b), x / y / out fp32 [t][c]; side 1 -> out16 = f16 copy
+// of out (raw bits, [t][c]); side 2 -> out16 = [oh | ol'] raw f16 bits [t][2c].  in_place != 0: the launch writes out over its x.
+extern "C" int reid_debug_post_norm(reid_ctx* ctx, int side, const float* x, const float* y, int t, int c, const float* g, const float* b,
+                                    int in_place, float* out, uint16_t* out16) {
+    ARG_CHECK(ctx && side >= 0 && side <= 2 && x && y && g && b && out && t >= 1 && c >= 4 && c <= 768 && c % 4 == 0 && (side == 0 || out16));
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)t * c;
+    float *dx, *dy, *dg, *db, *dout;
+    _Float16* dside = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgv2.x", x, nx, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgv2.y", y, nx, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgv2.g", g, (size_t)c, &dg));
+    REID_TRY(dbg_upload(ctx, "dbgv2.b", b, (size_t)c, &db));
+    if (in_place) dout = dx;
+    else REID_TRY(dbg_output(ctx, "dbgv2.out", nx, &dout));
+    if (side) REID_TRY(dbg_output(ctx, "dbgv2.o16", nx * (side == 2 ? 2 : 1), &dside));
+    REID_TRY(launch_post_norm(ctx, side, dx, dy, t, c, dg, db, dout, dside));
+    REID_TRY(dbg_download(ctx, out, dout, nx));
+    if (side) REID_TRY(dbg_download(ctx, (_Float16*)out16, dside, nx * (side == 2 ? 2 : 1)));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}

@@ -209,6 +209,11 @@ int launch_two_linear(reid_ctx*, const _Float16* a16, long long T, int C, int hi
 bool ln_linear_supported(const reid_ctx*, long long T, int C, int n);
 int launch_ln_linear(reid_ctx*, const float* x32, const float* ln_g, const float* ln_b, long long T, int C, int n, const float* w, const float* bias,
                      float* out, int ldc);
+// swin.hip: cosine window attention and the post-norm of the Swin "v2" blocks through libreid_hip_swin_v2.so (argument layouts: swin_v2.h)
+int launch_window_attn_cos(reid_ctx* ctx, int mode, const void* qkv, int ldq, int n_img, int H, int W, int heads, int shifted,
+                           const float* bias_t, const float* scale, void* out);
+int launch_post_norm(reid_ctx* ctx, int side_mode, const float* x, const float* y, long long T, int C, const float* g, const float* b,
+                     float* out, _Float16* side);
 int launch_split_pack(reid_ctx* ctx, const float* x, long long rows, int C, _Float16* out, const float* d_scale = nullptr);           // fp32 [rows][C] -> f16 [rows][2C] = [xh | xl']
 int launch_split_weights(reid_ctx* ctx, const float* w, int cout, int taps, int cin, int terms, _Float16* out, const float* d_scale = nullptr);  // fp32 [cout][taps][cin] -> f16 [cout][taps][terms * cin]
 // fp16 elementwise kernels (elementwise_f16.hip)

@@ -1,12 +1,14 @@
-// Swin-T (reference "v1": reid/backbones/swin_transformer.py) on the device: token layout [image][y][x][C] fp32.
+// Swin-T (reference: reid/backbones/swin_transformer.py, versions "v1" and "v2") on the device: token layout [image][y][x][C] fp32.
 // Every Linear / patch-merge / 8x8 conv / ConvTranspose is a launch of the f32 MFMA GEMM (gemm_f32.hip) with fused
 // bias / GELU / residual epilogues; this file holds the kernels that are not GEMMs (stem, LayerNorm, window attention,
-// LN + GeM_1D + BN tail) and the launch sequence.
+// LN + GeM_1D + BN tail) and the launch sequence.  The two kernels only v2 blocks launch are in swin_v2.hip (libreid_hip_swin_v2.so, opened when v2 weights are loaded).
 //
 // Cyclic shift: LayerNorm and every Linear are per-token, so the roll(-3,-3) ... roll(+3,+3) pair of a shifted block
 // (swin_transformer.py:193-194,230-231) is folded into the attention kernel's indexing alone: window position (y', x')
 // reads and writes token ((y'+3) % H, (x'+3) % W).
 #include "reid_internal.h"
+#include "swin_v2.h"
+#include <dlfcn.h>
 #include <mutex>
 #include <math.h>
 #include <string.h>
@@ -1119,8 +1121,47 @@ const int kDims[4] = {96, 192, 384, 768}, kLayers[4] = {2, 2, 6, 2}, kHeads[4] =
 
 }  // namespace
 
+// libreid_hip_swin_v2.so, opened from the directory this library lies in when the first v2 checkpoint is loaded (or a v2 harness runs):
+// a process that never loads v2 weights never opens it.  Missing library or symbol: REID_ERR_STATE naming the file - no other path runs v2.
+struct SwinV2Api {
+    decltype(&swin_v2_window_attn_cos) attn = nullptr;
+    decltype(&swin_v2_post_norm) post_norm = nullptr;
+};
+static int swin_v2_api(const SwinV2Api** out) {
+    static std::mutex m;
+    static SwinV2Api api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.attn) {
+        Dl_info info;
+        std::string path = "libreid_hip_swin_v2.so";
+        if (dladdr((const void*)&swin_v2_api, &info) && info.dli_fname) {
+            const std::string self = info.dli_fname;
+            const size_t slash = self.rfind('/');
+            if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
+        }
+        void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!h) {
+            reid_set_error("Swin v2 needs %s beside libreid_hip.so: %s", path.c_str(), dlerror());
+            return REID_ERR_STATE;
+        }
+        auto a = (decltype(api.attn))dlsym(h, "swin_v2_window_attn_cos");
+        auto p = (decltype(api.post_norm))dlsym(h, "swin_v2_post_norm");
+        if (!a || !p) {
+            reid_set_error("%s lacks swin_v2_window_attn_cos / swin_v2_post_norm", path.c_str());
+            return REID_ERR_STATE;
+        }
+        api.post_norm = p;
+        api.attn = a;
+    }
+    *out = &api;
+    return REID_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ weights
 struct SwinBlockW {
+    // v2: no pos; bias_t = the block's position-bias table as [head][key 49][query 64] (made at load time from the blob's
+    // [head][query][key] .bias), scale = exp(min(logit_scale, ln 100)) per head
+    const float *bias_t = nullptr, *scale = nullptr, *bias = nullptr;   // bias: the blob's [head][query][key] table
     const float *ln1_g, *ln1_b, *qkv_w, *pos, *out_w, *out_b, *post_w, *post_b, *ln2_g, *ln2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
 };
 struct SwinBlockW16 {
@@ -1136,7 +1177,8 @@ struct SwinWeights {
     float* blob = nullptr;
     f16* blob16 = nullptr;        // fp16-storage mode: the block linears
     float* fold_bias = nullptr;   // folded biases of the twelve blocks, back to back
-    float* bias_tabs = nullptr;   // expanded relative-position bias tables of the twelve blocks
+    float* bias_tabs = nullptr;   // expanded relative-position bias tables of the twelve blocks (v2: their bias_t tables)
+    int version = 1;              // 1 / 2: the manifest's swin.version entry (absent: 1)
     SwinBlockW16 blk16[12];
     const f16 *merge16[4], *img16, *t16[3];   // patch merging, 8x8 alignment conv, ConvTranspose parities (rows padded to 64)
     f16* zero_page = nullptr;
@@ -1219,6 +1261,26 @@ extern "C" int reid_swin_load(reid_ctx* ctx, const float* blob, size_t n_floats,
     SwinWeights w;
     HIP_TRY(hipMalloc((void**)&w.blob, n_floats * sizeof(float)));
     HIP_TRY(hipMemcpy(w.blob, blob, n_floats * sizeof(float), hipMemcpyHostToDevice));
+    {
+        auto ver = tab.find("swin.version");
+        if (ver != tab.end()) {
+            const float v = ver->second.second == 1 ? blob[ver->second.first] : 0.f;
+            if (v != 1.0f && v != 2.0f) {
+                reid_set_error("reid_swin_load: manifest entry 'swin.version' must hold 1 or 2");
+                (void)hipFree(w.blob);
+                return REID_ERR_ARG;
+            }
+            w.version = (int)v;
+            if (w.version == 2) {   // the v2 kernels' library: absent -> refuse the checkpoint here, not in the middle of a forward
+                const SwinV2Api* v2;
+                const int rc = swin_v2_api(&v2);
+                if (rc != REID_OK) {
+                    (void)hipFree(w.blob);
+                    return rc;
+                }
+            }
+        }
+    }
     bool missing = false;
     std::string first;
     auto get = [&](const std::string& name, size_t expect) -> const float* {
@@ -1247,7 +1309,14 @@ extern "C" int reid_swin_load(reid_ctx* ctx, const float* blob, size_t n_floats,
             const std::string b = st + ".b" + std::to_string(j);
             SwinBlockW& k = w.blk[bi];
             k.ln1_g = get(b + ".ln1.g", c); k.ln1_b = get(b + ".ln1.b", c);
-            k.qkv_w = get(b + ".qkv.w", 3 * c * c); k.pos = get(b + ".pos", 169);
+            k.qkv_w = get(b + ".qkv.w", 3 * c * c);
+            if (w.version == 2) {
+                k.pos = nullptr;
+                k.bias = get(b + ".bias", (size_t)kHeads[s] * 49 * 49);
+                k.scale = get(b + ".scale", (size_t)kHeads[s]);
+            } else {
+                k.pos = get(b + ".pos", 169);
+            }
             k.out_w = get(b + ".out.w", c * c); k.out_b = get(b + ".out.b", c);
             k.post_w = get(b + ".post.w", c * c); k.post_b = get(b + ".post.b", c);
             k.ln2_g = get(b + ".ln2.g", c); k.ln2_b = get(b + ".ln2.b", c);
@@ -1310,7 +1379,30 @@ extern "C" int reid_swin_load(reid_ctx* ctx, const float* blob, size_t n_floats,
         size_t nbias = 0;
         for (int s = 0; s < 4; ++s) nbias += (size_t)kLayers[s] * kDims[s];
         HIP_TRY(hipMalloc((void**)&w.fold_bias, nbias * sizeof(float)));
-        {   // [key][query] bias tables of the MFMA attention kernel (same entries as build_bias_table)
+        if (w.version == 2) {   // window_attn_cos_kernel's tables: [head][query][key] of the blob -> [head][key][query padded to 64]
+            size_t total_heads = 0;
+            for (int s = 0; s < 4; ++s) total_heads += (size_t)kLayers[s] * kHeads[s];
+            std::vector<float> tabs(total_heads * 49 * 64, 0.f);
+            std::vector<size_t> at(12);
+            size_t cur_t = 0;
+            int bt = 0;
+            for (int s = 0; s < 4; ++s)
+                for (int j = 0; j < kLayers[s]; ++j, ++bt) {
+                    const float* src = blob + (w.blk[bt].bias - w.blob);   // the host copy of what get() found
+                    at[bt] = cur_t;
+                    for (int hd = 0; hd < kHeads[s]; ++hd)
+                        for (int query = 0; query < 49; ++query)
+                            for (int key = 0; key < 49; ++key)
+                                tabs[cur_t + ((size_t)hd * 49 + key) * 64 + query] = src[((size_t)hd * 49 + query) * 49 + key];
+                    cur_t += (size_t)kHeads[s] * 49 * 64;
+                }
+            HIP_TRY(hipMalloc((void**)&w.bias_tabs, tabs.size() * sizeof(float)));
+            HIP_TRY(hipMemcpy(w.bias_tabs, tabs.data(), tabs.size() * sizeof(float), hipMemcpyHostToDevice));
+            for (int i = 0; i < 12; ++i) {
+                w.blk[i].bias_t = w.bias_tabs + at[i];
+                w.blk16[i].bias_tab = nullptr;
+            }
+        } else {   // [key][query] bias tables of the MFMA attention kernel (same entries as build_bias_table)
             std::vector<float> tabs((size_t)12 * 4096);
             int bt = 0;
             for (int s = 0; s < 4; ++s)
@@ -1404,6 +1496,90 @@ extern "C" int reid_swin_dims(reid_ctx* ctx, int* embed_dim, int* num_class) {
     return REID_OK;
 }
 
+// The two launches of libreid_hip_swin_v2.so (swin_v2.h) with the context's argument checks and profiling slots.
+int launch_window_attn_cos(reid_ctx* ctx, int mode, const void* qkv, int ldq, int n_img, int H, int W, int heads, int shifted,
+                           const float* bias_t, const float* scale, void* out) {
+    if (mode < 0 || mode > 2 || !qkv || !bias_t || !scale || !out || n_img < 1 || heads < 1 || H < 7 || W < 7 || H % 7 || W % 7 ||
+        ldq < 3 * heads * 32 || ldq % 4) {
+        reid_set_error("launch_window_attn_cos: bad arguments (mode %d, %d x %d tokens, %d heads, ldq %d)", mode, H, W, heads, ldq);
+        return REID_ERR_ARG;
+    }
+    const SwinV2Api* v2;
+    REID_TRY(swin_v2_api(&v2));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n_img * H * W * heads * 32 * (mode == 1 ? 8 : 16));
+    const hipError_t e = v2->attn(ctx->stream, mode, qkv, ldq, n_img, H, W, heads, shifted, bias_t, scale, out, ctx->fault);
+    prof_end(ctx);
+    HIP_TRY(e);
+    return REID_OK;
+}
+
+int launch_post_norm(reid_ctx* ctx, int side_mode, const float* x, const float* y, long long T, int C, const float* g, const float* b,
+                     float* out, _Float16* side) {
+    if (side_mode < 0 || side_mode > 2 || !x || !y || !g || !b || !out || (side_mode && !side) || T < 1 || C < 4 || C > 768 || C % 4) {
+        reid_set_error("launch_post_norm: bad arguments (side %d, %lld rows of %d)", side_mode, T, C);
+        return REID_ERR_ARG;
+    }
+    const SwinV2Api* v2;
+    REID_TRY(swin_v2_api(&v2));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T * C * (12 + 2 * side_mode));
+    const hipError_t e = v2->post_norm(ctx->stream, side_mode, x, y, T, C, g, b, out, side, ctx->fault);
+    prof_end(ctx);
+    HIP_TRY(e);
+    return REID_OK;
+}
+
+// One block of version "v2" (swin_transformer.py:238-246: Residual(PostNorm(attention)), Residual(PostNorm(feed-forward))):
+//   x = x + LN(post_proj(to_out(cos_attn(to_qkv(x)))));   x = x + LN(fc2(gelu(fc1(x))))
+// No LayerNorm in front of a linear: to_qkv reads the residual stream itself and fc1 the stream after the first post-norm, so in the
+// fp32-class and fp16-storage modes the post-norm kernel also writes the [xh | xl'] pair / the f16 copy the next linear reads (into
+// `att`, free by then); `first` = the stream was not written by a post-norm (first block of a stage): one pack / convert pass.
+// The reference's two roundings to_out -> post_proj are kept in modes 0 and 2; mode 1 folds them as it does for v1 (swin_fold).
+// Buffers as in swin_forward: big = qkv / MLP hidden, att, tmp, lnb = the branch result y (fp32) in every mode.
+static int swin_block_v2(reid_ctx* ctx, const SwinBlockW& k, const SwinBlockW16& h, const float* xin, float* xcur, long long T, int n,
+                         int Hs, int Ws, int C, int heads, int shifted, bool first, float* lnb, float* big, float* att, float* tmp) {
+    if (ctx->precision == 1) {
+        f16* x16 = (f16*)att;       // [T][C]: the stream as f16, then the attention output, then the stream again
+        f16* big16 = (f16*)big;     // qkv [T][ldq] / MLP hidden [T][4C]
+        f16* tmp16 = (f16*)tmp;     // [T][C]
+        const int ldq = (3 * C + 63) / 64 * 64;
+        if (first) REID_TRY(launch_f32_to_f16(ctx, xin, (size_t)T * C, x16));
+        REID_TRY(linear16(ctx, x16, T, C, C, h.qkv, nullptr, 3 * C, 0, nullptr, big16, nullptr, ldq));
+        REID_TRY(launch_window_attn_cos(ctx, 1, big16, ldq, n, Hs, Ws, heads, shifted, k.bias_t, k.scale, x16));
+        if (ctx->swin_fold) {
+            REID_TRY(linear16(ctx, x16, T, C, C, h.fold, h.fold_b, C, 0, nullptr, nullptr, lnb, C));
+        } else {
+            REID_TRY(linear16(ctx, x16, T, C, C, h.out, k.out_b, C, 0, nullptr, tmp16, nullptr, C));
+            REID_TRY(linear16(ctx, tmp16, T, C, C, h.post, k.post_b, C, 0, nullptr, nullptr, lnb, C));
+        }
+        REID_TRY(launch_post_norm(ctx, 1, xin, lnb, T, C, k.ln1_g, k.ln1_b, xcur, x16));
+        REID_TRY(linear16(ctx, x16, T, C, C, h.fc1, k.fc1_b, 4 * C, 1, nullptr, big16, nullptr, 4 * C));
+        REID_TRY(linear16(ctx, big16, T, 4 * C, 4 * C, h.fc2, k.fc2_b, C, 0, nullptr, nullptr, lnb, C));
+        return launch_post_norm(ctx, 1, xcur, lnb, T, C, k.ln2_g, k.ln2_b, xcur, x16);
+    }
+    if (ctx->precision == 2) {      // (every pass size: an image's arithmetic must not depend on the batch it comes in)
+        f16* x16 = (f16*)att;       // [T][2C]: the stream as [xh | xl'], then the attention output, then the stream again
+        f16* big16 = (f16*)big;     // MLP hidden [T][8C] (same bytes as the fp32 [T][4C])
+        f16* tmp16 = (f16*)tmp;     // [T][2C]
+        if (first) REID_TRY(launch_split_pack(ctx, xin, T, C, x16));
+        REID_TRY(linear(ctx, nullptr, T, C, k.qkv_w, nullptr, 3 * C, 0, nullptr, big, x16));
+        REID_TRY(launch_window_attn_cos(ctx, 2, big, 3 * C, n, Hs, Ws, heads, shifted, k.bias_t, k.scale, x16));
+        REID_TRY(linear(ctx, nullptr, T, C, k.out_w, k.out_b, C, 0, nullptr, nullptr, x16, tmp16));
+        REID_TRY(linear(ctx, nullptr, T, C, k.post_w, k.post_b, C, 0, nullptr, lnb, tmp16));
+        REID_TRY(launch_post_norm(ctx, 2, xin, lnb, T, C, k.ln1_g, k.ln1_b, xcur, x16));
+        REID_TRY(linear(ctx, nullptr, T, C, k.fc1_w, k.fc1_b, 4 * C, 1, nullptr, nullptr, x16, big16));
+        REID_TRY(linear(ctx, nullptr, T, 4 * C, k.fc2_w, k.fc2_b, C, 0, nullptr, lnb, big16));
+        return launch_post_norm(ctx, 2, xcur, lnb, T, C, k.ln2_g, k.ln2_b, xcur, x16);
+    }
+    REID_TRY(linear(ctx, xin, T, C, k.qkv_w, nullptr, 3 * C, 0, nullptr, big));
+    REID_TRY(launch_window_attn_cos(ctx, 0, big, 3 * C, n, Hs, Ws, heads, shifted, k.bias_t, k.scale, att));
+    REID_TRY(linear(ctx, att, T, C, k.out_w, k.out_b, C, 0, nullptr, tmp));
+    REID_TRY(linear(ctx, tmp, T, C, k.post_w, k.post_b, C, 0, nullptr, lnb));
+    REID_TRY(launch_post_norm(ctx, 0, xin, lnb, T, C, k.ln1_g, k.ln1_b, xcur, nullptr));
+    REID_TRY(linear(ctx, xcur, T, C, k.fc1_w, k.fc1_b, 4 * C, 1, nullptr, big));
+    REID_TRY(linear(ctx, big, T, 4 * C, k.fc2_w, k.fc2_b, C, 0, nullptr, lnb));
+    return launch_post_norm(ctx, 0, xcur, lnb, T, C, k.ln2_g, k.ln2_b, xcur, nullptr);
+}
+
 // ------------------------------------------------------------------------------------------------ forward
 // x: fp32 NCHW [n][3][h][w] on the device; h, w multiples of 224
 static int swin_forward(reid_ctx* ctx, const SwinWeights& w, const float* x, int n, int h, int wd, float* d_emb, float* d_logits) {
@@ -1476,6 +1652,10 @@ static int swin_forward(reid_ctx* ctx, const SwinWeights& w, const float* x, int
             // residual stream; every later block updates that stream in place
             const float* xin = (s == 0 && j == 0) ? sfe : xcur;
             const long long ntask = (long long)n * (Hs / 7) * (Ws / 7) * heads;
+            if (w.version == 2) {   // post-norm blocks with cosine attention; REID_SWIN_STOP's phases inside a block are v1's only
+                REID_TRY(swin_block_v2(ctx, k, w.blk16[bi], xin, xcur, T, n, Hs, Ws, C, heads, shifted, j == 0, lnb, big, att, tmp));
+                continue;
+            }
             if (ctx->precision == 1) {
                 // fp16-storage mode: the five linears of the block (95 % of its MACs) on the f16 MFMA GEMM with fp32
                 // accumulation; LayerNorm, softmax, GELU and the residual stream x stay fp32

@@ -524,6 +524,42 @@ class Engine:
             _ptr(_f32(shift)), _ptr(g), _ptr(e)))
         return g, e
 
+    def debug_window_attn_cos(self, mode, qkv, bias, scale, shifted):
+        """The Swin v2 cosine window attention alone (libreid_hip_debug.so reid_debug_window_attn_cos).  qkv [n, h, w, 3 * heads * 32]
+        fp32, bias [heads, 49, 49] (query, key), scale [heads].  mode 0 -> fp32 [n, h, w, C]; mode 2 -> the [oh | ol'] pair decoded
+        to float64 oh + ol' / 2^11; mode 1 (qkv rounded to f16 on the device) -> the f16 result as fp32."""
+        qkv, bias, scale = _f32(qkv), _f32(bias), _f32(scale)
+        n, h, w, c3 = qkv.shape
+        heads = bias.shape[0]
+        assert c3 == 3 * heads * 32 and bias.shape == (heads, 49, 49) and scale.shape == (heads,)
+        c = heads * 32
+        out = np.empty((n, h, w, c), np.float32) if mode == 0 else None
+        o16 = None if mode == 0 else np.empty((n * h * w, 2 * c if mode == 2 else c), np.uint16)
+        check(_ffi.debug_lib().reid_debug_window_attn_cos(
+            self.h, C.c_int(mode), _ptr(qkv), C.c_int(n), C.c_int(h), C.c_int(w), C.c_int(heads), C.c_int(int(bool(shifted))), _ptr(bias),
+            _ptr(scale), _ptr(out), _ptr(o16)))
+        if mode == 0:
+            return out
+        f = o16.view(np.float16)
+        if mode == 2:
+            return (f[:, :c].astype(np.float64) + f[:, c:].astype(np.float64) / 2048.0).reshape(n, h, w, c)
+        return f.astype(np.float32).reshape(n, h, w, c)
+
+    def debug_post_norm(self, side, x, y, g, b, in_place=False):
+        """The Swin v2 post-norm alone (reid_debug_post_norm): out = x + (LayerNorm(y) g + b), x / y [t, c].  Returns (out fp32 [t, c],
+        side output or None: side 1 -> the f16 copy as fp32, side 2 -> the [oh | ol'] pair decoded to float64)."""
+        x, y = _f32(x), _f32(y)
+        t, c = x.shape
+        out = np.empty((t, c), np.float32)
+        o16 = None if side == 0 else np.empty((t, 2 * c if side == 2 else c), np.uint16)
+        check(_ffi.debug_lib().reid_debug_post_norm(
+            self.h, C.c_int(side), _ptr(x), _ptr(y), C.c_int(t), C.c_int(c), _ptr(_f32(g)), _ptr(_f32(b)), C.c_int(int(bool(in_place))),
+            _ptr(out), _ptr(o16)))
+        if side == 0:
+            return out, None
+        f = o16.view(np.float16)
+        return out, (f[:, :c].astype(np.float64) + f[:, c:].astype(np.float64) / 2048.0) if side == 2 else f.astype(np.float32)
+
     def debug_swin_stage(self, stage, n, h=224, w=224):
         """Stage activations of the last Swin pass as NHWC arrays (0 sfe, 1..4 stage outputs, 5 GeM output [n,96])."""
         if stage == 5:

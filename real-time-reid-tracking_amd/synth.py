@@ -225,11 +225,54 @@ def _swin_mask(ws, disp, upper_lower):
     return m
 
 
-def swin_state_dict(seed=0, num_class=751, views=0):
-    """numpy ``state_dict`` with exactly the keys/shapes of ``swin_t(version='v1').state_dict()``
+SWIN_VERSIONS = ("v1", "v2")
+SWIN_V2_LOGIT_MAX = float(np.log(100.0))   # clamp of logit_scale (swin_transformer.py:207: math.log(1. / 0.01))
+
+
+def _swin_v2_from_v1(sd, seed):
+    """The v2 key set (swin_transformer.py:140-149) from a v1 dict: per block ``pos_embedding`` gives way to ``logit_scale``
+    [heads] (a Parameter of the attention module: where pos_embedding stood) and ``meta_mlp.fc1 / fc2`` (Linear(2, 384) -> ReLU ->
+    Linear(384, heads), registered between to_qkv and to_out) is added.  The v2-only tensors come from a generator of their own,
+    drawn in key order, so every other tensor equals the v1 dict's.  logit_scale is uniform in [ln 2, ln 150]: the heads differ
+    and some lie above the clamp at ln 100; meta_mlp is large enough that the bias it makes is a few units."""
+    rng = np.random.default_rng(seed + 104729)
+    out = OrderedDict()
+    for k, v in sd.items():
+        if k.endswith(".fn.fn.pos_embedding"):
+            pre = k[:-len("pos_embedding")]
+            heads = sd[pre + "to_qkv.weight"].shape[1] // 32
+            out[pre + "logit_scale"] = rng.uniform(np.log(2.0), np.log(150.0), heads).astype(np.float32)
+            continue
+        out[k] = v
+        if k.endswith(".fn.fn.to_qkv.weight"):
+            pre = k[:-len("to_qkv.weight")]
+            heads = v.shape[1] // 32
+            out[pre + "meta_mlp.fc1.weight"] = rng.normal(0.0, 0.7, (384, 2)).astype(np.float32)
+            out[pre + "meta_mlp.fc1.bias"] = rng.normal(0.0, 0.1, 384).astype(np.float32)
+            out[pre + "meta_mlp.fc2.weight"] = rng.normal(0.0, np.sqrt(2.0 / 384), (heads, 384)).astype(np.float32)
+            out[pre + "meta_mlp.fc2.bias"] = rng.normal(0.0, 0.1, heads).astype(np.float32)
+    return out
+
+
+def swin_relative_coordinates_log(ws=7):
+    """WindowAttention._make_pair_wise_relative_positions (swin_transformer.py:165-175), restated: [ws^4][2] float64, row
+    i * ws^2 + j = sign(d) * log(1 + |d|) of d = coordinate(i) - coordinate(j), (row, column) order."""
+    idx = np.arange(ws * ws)
+    coords = np.stack([idx // ws, idx % ws], 0).astype(np.float64)          # [2][49]
+    rel = (coords[:, :, None] - coords[:, None, :]).transpose(1, 2, 0).reshape(-1, 2)
+    return np.sign(rel) * np.log1p(np.abs(rel))
+
+
+def swin_state_dict(seed=0, num_class=751, views=0, version="v1"):
+    """numpy ``state_dict`` with exactly the keys/shapes of ``swin_t(version=version).state_dict()``
     (reid/backbones/swin_transformer.py:339-395,508-513; 40.8 M parameters).  ``views`` > 0 adds the side-information table
     ``sfe.side_info_embedding`` [views,1,1,96] of a model built with camera / sequence (:285-293; views = camera * sequence, camera
-    or sequence), drawn from a generator of its own so that the other tensors do not depend on it."""
+    or sequence), drawn from a generator of its own so that the other tensors do not depend on it.  ``version="v2"``: the keys of
+    the cosine-attention blocks (_swin_v2_from_v1); every tensor both versions hold is the same for the same seed."""
+    if version not in SWIN_VERSIONS:
+        raise ValueError("swin version must be one of %s, got %r" % (SWIN_VERSIONS, version))
+    if version == "v2":
+        return _swin_v2_from_v1(swin_state_dict(seed, num_class, views), seed)
     rng = np.random.default_rng(seed)
     sd = OrderedDict()
     sd["sfe.conv1.weight"] = rng.normal(0, np.sqrt(1.0 / 12), (12, 3, 2, 2)).astype(np.float32)

@@ -186,7 +186,7 @@ def pack_seres18(state_dict, cam_factor=-1.0):
     return blob, manifest, {"arch": arch, "embed_dim": 512, "num_class": num_class}
 
 
-# ------------------------------------------------------------------------------------------------ Swin-T (v1)
+# ------------------------------------------------------------------------------------------------ Swin-T (v1, v2)
 def _convt_parity(w):
     """ConvTranspose2d(4, 2, 1) weight [Cin][Cout][4][4] -> [py][px][Cout][r][s][Cin]: the four output-parity 2x2
     convolutions.  Output row 2j+py takes input rows j-1+r (py=0: kernel rows 3,1) or j+r (py=1: kernel rows 2,0)."""
@@ -202,16 +202,59 @@ def _convt_parity(w):
     return out
 
 
+_V2_LEAVES = ("logit_scale", "meta_mlp.fc1.weight", "meta_mlp.fc1.bias", "meta_mlp.fc2.weight", "meta_mlp.fc2.bias")
+
+
+def swin_version(sd):
+    """"v1" or "v2" from the keys of a (normalised) swin_t state_dict: v2 blocks hold logit_scale + meta_mlp where v1 blocks hold
+    pos_embedding (swin_transformer.py:140-158).  A dict that mixes the two raises KeyError naming the first offending key."""
+    version = "v2" if any(k.endswith(".fn.fn.logit_scale") for k in sd) else "v1"
+    want, other = (("pos_embedding",), _V2_LEAVES) if version == "v1" else (_V2_LEAVES, ("pos_embedding",))
+    for si, nl in enumerate(synth.SWIN_LAYERS):
+        for li in range(nl // 2):
+            for bi in range(2):
+                a = "stage%d.layers.%d.%d.attention_block.fn.fn." % (si + 1, li, bi)
+                for leaf in other:
+                    if a + leaf in sd:
+                        raise KeyError("swin_t checkpoint mixes v1 and v2 blocks: '%s' in a %s checkpoint" % (a + leaf, version))
+                for leaf in want:
+                    if a + leaf not in sd:
+                        raise KeyError("swin_t (%s) checkpoint: missing '%s'" % (version, a + leaf))
+    return version
+
+
+def swin_v2_bias_table(fc1_w, fc1_b, fc2_w, fc2_b):
+    """WindowAttention._relative_positional_encodings (swin_transformer.py:177-189): meta_mlp over the 49 x 49 log-spaced relative
+    coordinates -> [heads][49][49] (query, key).  It does not depend on the input, so it is evaluated here, once, in float64, and
+    rounded to fp32; no kernel holds meta_mlp."""
+    rel = synth.swin_relative_coordinates_log(7)                                          # [2401][2]
+    hid = np.maximum(rel @ np.asarray(fc1_w, np.float64).T + np.asarray(fc1_b, np.float64), 0.0)
+    out = hid @ np.asarray(fc2_w, np.float64).T + np.asarray(fc2_b, np.float64)           # [2401][heads]
+    return np.ascontiguousarray(out.T).reshape(-1, 49, 49).astype(np.float32)
+
+
+def swin_v2_scale(logit_scale):
+    """exp(min(logit_scale, ln 100)) per head (swin_transformer.py:207).  The clamp is the reference's fp32 one (fp32(ln 100) lies
+    6e-8 above ln 100, so a clamped head scales by 100.00001); the exponential is taken in float64 and rounded once."""
+    clamped = np.minimum(np.asarray(logit_scale, np.float32), np.float32(np.log(1.0 / 0.01)))
+    return np.exp(clamped.astype(np.float64)).astype(np.float32)
+
+
 def pack_swin(state_dict, side_info_coeff=1.5):
-    """state_dict of swin_t(version='v1') (reid/backbones/swin_transformer.py) -> (blob, manifest, info) for reid_swin_load.
+    """state_dict of swin_t(version='v1' or 'v2') (reid/backbones/swin_transformer.py) -> (blob, manifest, info) for
+    reid_swin_load; the version is read from the keys (swin_version).
     ``side_info_coeff``: ShadowFeatureExtraction's constructor argument (:279) that scales the side-information embedding.
     Dropped: stage1.patch_partition (never applied, patch_merge=False :357-359), the constant shift masks (recomputed in
-    the attention kernel), num_batches_tracked."""
+    the attention kernel), num_batches_tracked.  v2: per block the bias table [heads][49][49] (.bias) and the clamped,
+    exponentiated scale per head (.scale) instead of .pos; the manifest carries ``swin.version`` (one float, 2)."""
     sd = normalize_state_dict(state_dict)
     if "sfe.conv1.weight" not in sd or "stage4.layers.0.1.attention_block.fn.fn.to_qkv.weight" not in sd:
-        raise KeyError("state_dict is not a swin_t (v1) checkpoint")
+        raise KeyError("state_dict is not a swin_t (v1 / v2) checkpoint")
+    version = swin_version(sd)
     f = lambda k: np.asarray(sd[k], np.float32)
     pk = Packer()
+    if version == "v2":
+        pk.add("swin.version", np.asarray([2.0], np.float32))
     pk.add("sfe.conv1.w", f("sfe.conv1.weight").transpose(0, 2, 3, 1))       # [12][(kh,kw,c)]
     pk.add("sfe.conv1.b", f("sfe.conv1.bias"))
     pk.add("sfe.in_gamma", f("sfe.norm.instancenorm.weight"))
@@ -238,7 +281,12 @@ def pack_swin(state_dict, side_info_coeff=1.5):
                 pk.add(o + ".ln1.g", f(a + ".norm.weight"))
                 pk.add(o + ".ln1.b", f(a + ".norm.bias"))
                 pk.add(o + ".qkv.w", f(a + ".fn.to_qkv.weight"))
-                pk.add(o + ".pos", f(a + ".fn.pos_embedding").reshape(169))
+                if version == "v2":
+                    pk.add(o + ".bias", swin_v2_bias_table(sd[a + ".fn.meta_mlp.fc1.weight"], sd[a + ".fn.meta_mlp.fc1.bias"],
+                                                           sd[a + ".fn.meta_mlp.fc2.weight"], sd[a + ".fn.meta_mlp.fc2.bias"]))
+                    pk.add(o + ".scale", swin_v2_scale(sd[a + ".fn.logit_scale"]))
+                else:
+                    pk.add(o + ".pos", f(a + ".fn.pos_embedding").reshape(169))
                 pk.add(o + ".out.w", f(a + ".fn.to_out.weight"))
                 pk.add(o + ".out.b", f(a + ".fn.to_out.bias"))
                 pk.add(o + ".post.w", f(a + ".fn.post_proj.weight"))
@@ -271,4 +319,7 @@ def pack_swin(state_dict, side_info_coeff=1.5):
         pk.add("sfe.side", f("sfe.side_info_embedding").reshape(-1, 96))
         pk.add("sfe.side_coeff", np.asarray([side_info_coeff], np.float32))
     blob, manifest = pk.finish()
-    return blob, manifest, {"arch": "swin_transformer", "embed_dim": 96, "num_class": num_class}
+    info = {"arch": "swin_transformer", "embed_dim": 96, "num_class": num_class}
+    if version == "v2":
+        info["version"] = "v2"
+    return blob, manifest, info
