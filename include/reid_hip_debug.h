@@ -68,6 +68,11 @@ int reid_debug_norm_finish(reid_ctx* ctx, int form, int n, int hw, int c, int ha
  * gate for 11). */
 int reid_debug_se_tail(reid_ctx* ctx, int form, int n, int hw, int c, int mid, int tiles, const float* stats, const float* w1,
                        const float* w2t, const void* y, const void* shortcut, float* out, uint16_t* out16, float* gate);
+/* The exact-fp32 attention tails of the sibling backbones (csrc/attention_f32.hip) through the forward's launchers, on host operands:
+ * arch 1 TripletAttention (prm [3][100]), arch 2 EMA (prm of c / 32 channels per group), out = relu(tail(y) + shortcut), NHWC [n][h][w][c].
+ * The yardstick tests/test_gpu_siblings_f16.py measures the f16 tails of libreid_hip_siblings_f16.so against. */
+int reid_debug_sibling_tail(reid_ctx* ctx, int arch, int n, int h, int w, int c, const float* prm, const float* y, const float* shortcut,
+                            float* out);
 /* gem_neck: GeM (exponent p) + BNNeck, emb = gem * scale + shift, on fp32 x (f16 = 0) or f16 x (f16 = 1); gem_out may be null. */
 int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale, const float* shift,
                         float* gem_out, float* emb);

@@ -238,13 +238,15 @@ def seres18_ibn(num_classes=751, loss="triplet", pretrained=False, use_gpu=True,
 
 class CARes18IBN(SERes18IBN):
     """CARes18_IBN (reid/backbones/CARes18.py:185-281): the same IBN-Net skeleton, every block ends in
-    relu(TripletAttention(y) + shortcut) (:148-157; triplet_attention.py:69-101).  Exact fp32 arithmetic only."""
+    relu(TripletAttention(y) + shortcut) (:148-157; triplet_attention.py:69-101).  All three arithmetic modes; precision="f16"
+    (fp16 storage) runs the tails of libreid_hip_siblings_f16.so, which must lie beside libreid_hip.so."""
     arch = "cares18_ibn"
 
 
 class EMARes18IBN(SERes18IBN):
     """EMARes18_IBN (reid/backbones/EMA_Res18.py:118-181): every block ends in relu(EMA(y) + shortcut) (:79-86), EMA with 32
-    channel groups (:10-38).  Exact fp32 arithmetic only."""
+    channel groups (:10-38).  All three arithmetic modes; precision="f16" (fp16 storage) runs the tails of
+    libreid_hip_siblings_f16.so, which must lie beside libreid_hip.so."""
     arch = "emares18_ibn"
 
 

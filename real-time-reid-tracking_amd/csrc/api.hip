@@ -1,6 +1,9 @@
 // C ABI of libreid_hip.so (include/reid_hip.h): context, weights, the ResNet18-IBN-SE launch sequence,
 // distance / selection entry points.  No torch types, no CPU compute fallback: every result comes from a HIP kernel.
 #include "reid_internal.h"
+#include "siblings_f16.h"
+#include <dlfcn.h>
+#include <mutex>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -986,6 +989,64 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
 }
 
 // ------------------------------------------------------------------------------------------------ fp16 forward
+// libreid_hip_siblings_f16.so (siblings_f16.h), opened from the directory this library lies in the first time a sibling backbone
+// (CARes18_IBN / EMARes18_IBN) runs in the fp16-storage mode: a process that never does never opens it.  Missing library or symbol:
+// REID_ERR_STATE naming the file - no other path runs a sibling in mode 1.
+struct SiblingsF16Api {
+    decltype(&siblings_f16_ta_workspace_bytes) ta_bytes = nullptr;
+    decltype(&siblings_f16_ta_tail) ta = nullptr;
+    decltype(&siblings_f16_ema_tail) ema = nullptr;
+};
+static int siblings_f16_api(const SiblingsF16Api** out) {
+    static std::mutex m;
+    static SiblingsF16Api api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.ta) {
+        Dl_info info;
+        std::string path = "libreid_hip_siblings_f16.so";
+        if (dladdr((const void*)&siblings_f16_api, &info) && info.dli_fname) {
+            const std::string self = info.dli_fname;
+            const size_t slash = self.rfind('/');
+            if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
+        }
+        void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!h) {
+            reid_set_error("CARes18-IBN / EMARes18-IBN in the fp16-storage mode need %s beside libreid_hip.so: %s", path.c_str(), dlerror());
+            return REID_ERR_STATE;
+        }
+        auto b = (decltype(api.ta_bytes))dlsym(h, "siblings_f16_ta_workspace_bytes");
+        auto t = (decltype(api.ta))dlsym(h, "siblings_f16_ta_tail");
+        auto e = (decltype(api.ema))dlsym(h, "siblings_f16_ema_tail");
+        if (!b || !t || !e) {
+            dlclose(h);
+            reid_set_error("%s lacks siblings_f16_ta_workspace_bytes / siblings_f16_ta_tail / siblings_f16_ema_tail", path.c_str());
+            return REID_ERR_STATE;
+        }
+        api.ta_bytes = b;
+        api.ema = e;
+        api.ta = t;
+    }
+    *out = &api;
+    return REID_OK;
+}
+
+// The two launches of that library with the context's workspace, argument checks and profiling slot.
+static int launch_sibling_tail_f16(reid_ctx* ctx, const SiblingsF16Api* api, int arch, const _Float16* y, const _Float16* sc, int n, int H,
+                                   int W, int C, const float* prm, _Float16* out) {
+    ARG_CHECK(api && y && sc && prm && out && out != y && out != sc);
+    void* ws = nullptr;
+    if (arch == 1) {
+        const size_t bytes = api->ta_bytes(n, H, W, C);
+        ARG_CHECK(bytes > 0);
+        REID_TRY(ctx_ws(ctx, "ta16.ws", bytes, &ws));
+    }
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * H * W * C * 2.0 * 4.0);
+    const hipError_t e = arch == 1 ? api->ta(ctx->stream, y, sc, n, H, W, C, prm, ws, out) : api->ema(ctx->stream, y, sc, n, H, W, C, prm, out);
+    prof_end(ctx);
+    HIP_TRY(e);
+    return REID_OK;
+}
+
 int conv_gemm16(reid_ctx* ctx, int amode, const _Float16* x, int n, int H, int W, int Cin, const _Float16* wgt, int Cout,
                        int R, int S, int stride, int pad, int K, const float* col_scale, const float* col_shift,
                        const _Float16* residual, int relu, float* stats, _Float16* out, int Hp, int Wp) {
@@ -1026,6 +1087,11 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
     typedef _Float16 f16;
     const size_t per = 131072;
     const bool keep = ctx->debug_keep != 0;
+    // CARes18_IBN / EMARes18_IBN: the same convolutions, the block tail from libreid_hip_siblings_f16.so.  Everything that exists for
+    // the SE tail only - the pooled statistics of conv2, the fused SE build of the layer-1 kernel, the f16_se_tail switch - is skipped.
+    const bool sibling = w.arch != 0;
+    const SiblingsF16Api* sib = nullptr;
+    if (sibling) REID_TRY(siblings_f16_api(&sib));
     f16 *pad_in, *stem, *pool, *tbase;
     float *stats, *a_scale, *a_shift, *se, *gem;
     REID_TRY(ctx_ws(ctx, "se18h.pad", (size_t)n * PAD_H * PAD_W * 4 * 2, (void**)&pad_in));
@@ -1096,7 +1162,7 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
             REID_TRY(conv_gemm16(ctx, A16_IM2COL, cur, n, H, W, k.cin, w.h(k.conv1_w), k.c, 3, 3, k.stride, 1, 9 * k.cin,
                                  k.bn1_scale, k.bn1_shift, nullptr, 1, nullptr, c1));
         }
-        if (c64 && ctx->f16_c64 == 2) {
+        if (c64 && ctx->f16_c64 == 2 && !sibling) {
             // conv2 + residual + ReLU (Q5) + SE gate + combine in one kernel: `out` is the block output, y never reaches HBM
             f16* outb = y;   // c1 is this launch's input, cur its shortcut: the block output goes to the third buffer
             REID_TRY(launch_conv3x3_c64_f16(ctx, c1, n, w.l1_conv2_w16s[i], k.bn2_shift, cur, 1, nullptr, outb, w.zero_page, k.se_w1,
@@ -1107,10 +1173,11 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
             W = Wo;
             continue;
         } else if (c64) {
-            REID_TRY(launch_conv3x3_c64_f16(ctx, c1, n, w.l1_conv2_w16s[i], k.bn2_shift, cur, 1, stats, y, w.zero_page));   // residual + ReLU: Q5
+            REID_TRY(launch_conv3x3_c64_f16(ctx, c1, n, w.l1_conv2_w16s[i], k.bn2_shift, cur, 1, sibling ? nullptr : stats, y,
+                                            w.zero_page));   // residual + ReLU: Q5
         } else {
             REID_TRY(conv_gemm16(ctx, A16_IM2COL, c1, n, Ho, Wo, k.c, w.h(k.conv2_w), k.c, 3, 3, 1, 1, 9 * k.c, k.bn2_scale,
-                                 k.bn2_shift, k.ds ? nullptr : cur, k.ds ? 0 : 1, stats, y));
+                                 k.bn2_shift, k.ds ? nullptr : cur, k.ds ? 0 : 1, sibling ? nullptr : stats, y));
         }
         const f16* shortcut = cur;
         if (k.ds) {
@@ -1119,7 +1186,9 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
             shortcut = sc;
         }
         f16* out = c1;
-        if (ctx->f16_se_tail && ctx->debug_keep != 1) {   // gate + combine in one launch, sliced per image when there are few images
+        if (sibling) {   // TripletAttention / EMA + shortcut + ReLU (CARes18.py:150-157, EMA_Res18.py:79-86)
+            REID_TRY(launch_sibling_tail_f16(ctx, sib, w.arch, y, shortcut, n, Ho, Wo, k.c, w.arch == 1 ? k.ta : k.ema, out));
+        } else if (ctx->f16_se_tail && ctx->debug_keep != 1) {   // gate + combine in one launch, sliced per image when there are few images
             REID_TRY(launch_se_tail_f16(ctx, stats, n, c64 ? 1 : tiles, k.c, k.mid, hw, k.se_w1, k.se_w2, y, shortcut, out));
         } else {
             REID_TRY(launch_se_finalize(ctx, stats, n, c64 ? 1 : tiles, k.c, k.mid, hw, k.se_w1, k.se_w2, se));
@@ -1160,9 +1229,7 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
 // (Replaying a captured hipGraph for small batches was tried: the host saves ~150 us of launch calls per tracking frame, but
 // the device-side replay is slower than plain launches and the frame pipeline already hides the host - 1421 vs 1516 frames/s.)
 static int seres18_run(reid_ctx* ctx, const void* x, bool is_u8, int n, float* d_emb, float* d_logits) {
-    // the sibling backbones (CARes18 / EMARes18) exist in the reference's arithmetic only
-    return (ctx->precision == 1 && ctx->se18.arch == 0) ? seres18_forward_f16(ctx, x, is_u8, n, d_emb, d_logits)
-                                                         : seres18_forward(ctx, x, is_u8, n, d_emb, d_logits);
+    return ctx->precision == 1 ? seres18_forward_f16(ctx, x, is_u8, n, d_emb, d_logits) : seres18_forward(ctx, x, is_u8, n, d_emb, d_logits);
 }
 
 static const size_t kStageElems[11] = {524288, 131072, 131072, 131072, 65536, 65536, 32768, 32768, 65536, 65536, 512};

@@ -630,6 +630,23 @@ extern "C" int reid_debug_se_tail(reid_ctx* ctx, int form, int n, int hw, int c,
     return ctx_fault_status(ctx);
 }
 
+extern "C" int reid_debug_sibling_tail(reid_ctx* ctx, int arch, int n, int h, int w, int c, const float* prm, const float* y,
+                                       const float* shortcut, float* out) {
+    ARG_CHECK(ctx && (arch == 1 || arch == 2) && n >= 1 && h >= 1 && w >= 1 && c >= 32 && c % 32 == 0 && prm && y && shortcut && out);
+    CTX_ENTER(ctx);
+    const size_t ny = (size_t)n * h * w * c, cg = (size_t)c / 32;
+    float *dp, *dy, *dsc, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", prm, arch == 1 ? (size_t)300 : cg * cg * 10 + 4 * cg, &dp));
+    REID_TRY(dbg_upload(ctx, "dbgt.x", y, ny, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgt.sc", shortcut, ny, &dsc));
+    REID_TRY(dbg_output(ctx, "dbgt.out", ny, &dout));
+    if (arch == 1) REID_TRY(launch_ta_tail(ctx, dy, dsc, n, h, w, c, dp, dout));
+    else REID_TRY(launch_ema_tail(ctx, dy, dsc, n, h, w, c, dp, dout));
+    REID_TRY(dbg_download(ctx, out, dout, ny));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 extern "C" int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale,
                                    const float* shift, float* gem_out, float* emb) {
     ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && x && scale && shift && emb);

@@ -513,6 +513,16 @@ class Engine:
             _ptr(_f32(w2t)), _ptr(ya), _ptr(sa), _ptr(out), _ptr(o16), _ptr(gate)))
         return out, o16, gate
 
+    def debug_sibling_tail(self, arch, prm, y, shortcut):
+        """The exact-fp32 TripletAttention (arch 1) / EMA (arch 2) tail through the forward's launcher (libreid_hip_debug.so
+        reid_debug_sibling_tail).  y / shortcut [n, h, w, c] fp32; returns relu(tail(y) + shortcut) [n, h, w, c].  Unwritten outputs read as NaN."""
+        y, shortcut = _f32(y), _f32(shortcut)
+        n, h, w, c = y.shape
+        out = np.empty((n, h, w, c), np.float32)
+        check(_ffi.debug_lib().reid_debug_sibling_tail(self.h, C.c_int(arch), C.c_int(n), C.c_int(h), C.c_int(w), C.c_int(c), _ptr(_f32(prm)),
+                                                       _ptr(y), _ptr(shortcut), _ptr(out)))
+        return out
+
     def debug_gem_neck(self, x, p, scale, shift, f16=False):
         """GeM + BNNeck through the forward's launcher (libreid_hip_debug.so reid_debug_gem_neck).  x [n, hw, c] fp32 (or uint16 f16
         bits with f16=True).  Returns (gem [n, c], emb [n, c])."""
