@@ -76,6 +76,22 @@ int reid_debug_sibling_tail(reid_ctx* ctx, int arch, int n, int h, int w, int c,
 /* gem_neck: GeM (exponent p) + BNNeck, emb = gem * scale + shift, on fp32 x (f16 = 0) or f16 x (f16 = 1); gem_out may be null. */
 int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale, const float* shift,
                         float* gem_out, float* emb);
+/* The front end of a ResNet pass (correctness harness, tests/test_gpu_frontend.py), each through the launcher the forward calls, on host
+ * operands.  Every output the launch leaves alone reads as NaN (0xffff); each call returns the context's fault status.
+ * stem: conv 7x7 stride 2 pad 3 (3 -> 64) * scale + shift, no ReLU, + MaxPool(3, 2, 1).  x [n][256][128][3], uint8 crops (is_u8, normalised
+ * (2v - 255) / 255 by the loaders) or fp32; w [64][7][7][3], packed here to stem.w [64][8][24] and its two f16 forms as reid_seres18_load does.
+ * form 0 launch_stem_f32 unpooled -> out [n][128][64][64]; 1 launch_stem_f32 pooled -> out [n][64][32][64]; 2 launch_stem_split -> out and
+ * out16 [n 64 32][xh 64 | xl' 64]; 3 launch_stem_pool_f16 straight from uint8 -> out16 [n][64][32][64]; 4 prep_*_pad_f16 +
+ * launch_stem_pool_f16 -> out16; 5 prep_*_pad_f16 + conv_gemm16(A16_STEM) + launch_maxpool3s2_f16 -> out16; 6 conv_gemm(A_STEM_U8 /
+ * A_STEM_F32) + launch_maxpool3s2 -> out.  f16 results are raw bits.  The launchers keep the strip / tile count they choose to themselves:
+ * the test restates the two rules. */
+int reid_debug_stem(reid_ctx* ctx, int form, int is_u8, const void* x, int n, const float* w, const float* scale, const float* shift,
+                    float* out, uint16_t* out16);
+/* resize_norm: n uint8 windows of hw[i] = (h, w) pixels at byte offsets[i] of `packed`, rows `pitch` pixels apart (0: the window's own
+ * width), bilinear to 256 x 128 and normalised -> out [n][256][128][3] fp32. */
+int reid_debug_resize_norm(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch, float* out);
+/* maxpool: MaxPool(3, 2, 1) of x NHWC [n][h][w][c] -> out [n][(h - 1) / 2 + 1][(w - 1) / 2 + 1][c], fp32 (f16 = 0) or raw f16 bits. */
+int reid_debug_maxpool(reid_ctx* ctx, int f16, const void* x, int n, int h, int w, int c, void* out);
 /* The two kernels of the Swin "v2" blocks alone (csrc/swin_v2.hip; correctness harnesses, tests/test_gpu_swin_v2.py), each through the
  * launcher the forward calls, on host operands; f16 results are raw f16 bits; each call returns the context's fault status.
  * window_attn_cos: cosine window attention of n maps of h x w tokens (multiples of 7), qkv fp32 [n h w][3 heads 32] (q | k | v, head-major),

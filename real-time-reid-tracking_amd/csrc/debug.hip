@@ -894,3 +894,122 @@ extern "C" int reid_debug_post_norm(reid_ctx* ctx, int side, const float* x, con
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }
+
+// ------------------------------------------------------------------------------------------------ front end (tests/test_gpu_frontend.py)
+// What runs before layer 1 of a ResNet pass, each through the launcher the forward calls, on host operands.  Outputs are set to 0xff
+// bytes first (NaN / 0xffff where a launch leaves them alone); every call returns the context's fault status.
+extern "C" int reid_debug_stem(reid_ctx* ctx, int form, int is_u8, const void* x, int n, const float* w, const float* scale,
+                               const float* shift, float* out, uint16_t* out16) {
+    ARG_CHECK(ctx && form >= 0 && form <= 6 && x && n >= 1 && w && scale && shift);
+    ARG_CHECK((form == 3 ? is_u8 != 0 : true) && (form >= 3 && form <= 5 ? out16 != nullptr : out != nullptr) && (form != 2 || out16));
+    CTX_ENTER(ctx);
+    typedef _Float16 f16;
+    const int PAD_H = 262, PAD_W = 136;                      // the padded NHWC4 image of the fp16 path (api.hip)
+    const size_t npix = (size_t)n * 256 * 128, nmap = (size_t)n * 128 * 64 * 64, npool = (size_t)n * 64 * 32 * 64;
+    // [64][7][7][3] -> stem.w [64][8][24] (k = r 24 + s 3 + c, zero padded: weights.stem_pack), then the two f16 forms reid_seres18_load makes
+    std::vector<float> wp((size_t)64 * 192, 0.f);
+    for (int co = 0; co < 64; ++co)
+        for (int r = 0; r < 7; ++r)
+            for (int k = 0; k < 21; ++k) wp[(size_t)co * 192 + r * 24 + k] = w[((size_t)co * 7 + r) * 21 + k];
+    float *dw, *dsc, *dsh, *dxf = nullptr, *dmap = nullptr, *dout = nullptr;
+    uint8_t* dxu = nullptr;
+    f16 *dw16 = nullptr, *dpad = nullptr, *dmap16 = nullptr, *dout16 = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgf.w", wp.data(), wp.size(), &dw));
+    REID_TRY(dbg_upload(ctx, "dbgf.scale", scale, (size_t)64, &dsc));
+    REID_TRY(dbg_upload(ctx, "dbgf.shift", shift, (size_t)64, &dsh));
+    if (is_u8) REID_TRY(dbg_upload(ctx, "dbgf.xu8", (const uint8_t*)x, npix * 3, &dxu));
+    else REID_TRY(dbg_upload(ctx, "dbgf.xf32", (const float*)x, npix * 3, &dxf));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));              // wp is a local
+    const void* dx = is_u8 ? (const void*)dxu : (const void*)dxf;
+    if (form >= 3 && form <= 5) {
+        REID_TRY(ctx_ws(ctx, "dbgf.w16", (size_t)64 * 256 * 2, (void**)&dw16));
+        if (form == 5) REID_TRY(launch_stem_w16(ctx, dw, dw16));
+        else REID_TRY(launch_stem_w16_scaled(ctx, dw, dsc, dw16));
+        REID_TRY(dbg_output(ctx, "dbgf.out16", npool, &dout16));
+        if (form >= 4) {
+            REID_TRY(dbg_output(ctx, "dbgf.pad", (size_t)n * PAD_H * PAD_W * 4, &dpad));
+            if (is_u8) REID_TRY(launch_prep_u8_pad_f16(ctx, dxu, n, 256, 128, PAD_H, PAD_W, dpad));
+            else REID_TRY(launch_prep_f32_pad_f16(ctx, dxf, n, 256, 128, PAD_H, PAD_W, dpad));
+        }
+    }
+    switch (form) {
+    case 0:
+        REID_TRY(dbg_output(ctx, "dbgf.map", nmap, &dout));
+        REID_TRY(launch_stem_f32(ctx, dx, is_u8 != 0, n, dw, dsc, dsh, dout, false));
+        break;
+    case 1:
+        REID_TRY(dbg_output(ctx, "dbgf.out", npool, &dout));
+        REID_TRY(launch_stem_f32(ctx, dx, is_u8 != 0, n, dw, dsc, dsh, dout, true));
+        break;
+    case 2:
+        REID_TRY(dbg_output(ctx, "dbgf.out", npool, &dout));
+        REID_TRY(dbg_output(ctx, "dbgf.out16", npool * 2, &dout16));
+        REID_TRY(launch_stem_split(ctx, dx, is_u8 != 0, n, dw, dsc, dsh, dout, dout16));
+        break;
+    case 3: REID_TRY(launch_stem_pool_f16(ctx, nullptr, dxu, n, dw16, dsh, dout16)); break;
+    case 4: REID_TRY(launch_stem_pool_f16(ctx, dpad, nullptr, n, dw16, dsh, dout16)); break;
+    case 5:
+        REID_TRY(dbg_output(ctx, "dbgf.map16", nmap, &dmap16));
+        REID_TRY(conv_gemm16(ctx, A16_STEM, dpad, n, 256, 128, 4, dw16, 64, 7, 7, 2, 3, 224, dsc, dsh, nullptr, 0, nullptr, dmap16, PAD_H, PAD_W));
+        REID_TRY(launch_maxpool3s2_f16(ctx, dmap16, n, 128, 64, 64, dout16));
+        break;
+    case 6:
+        REID_TRY(dbg_output(ctx, "dbgf.map", nmap, &dmap));
+        REID_TRY(dbg_output(ctx, "dbgf.out", npool, &dout));
+        REID_TRY(conv_gemm(ctx, is_u8 ? A_STEM_U8 : A_STEM_F32, dx, n, 256, 128, 3, dw, 64, 7, 7, 2, 3, 192, nullptr, nullptr, 0, dsc, dsh, nullptr,
+                           0, nullptr, dmap));
+        REID_TRY(launch_maxpool3s2(ctx, dmap, n, 128, 64, 64, dout));
+        break;
+    }
+    if (dout) REID_TRY(dbg_download(ctx, out, dout, form == 0 ? nmap : npool));
+    if (dout16) REID_TRY(dbg_download(ctx, (f16*)out16, dout16, form == 2 ? npool * 2 : npool));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_resize_norm(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch,
+                                      float* out) {
+    ARG_CHECK(ctx && packed && offsets && hw && n >= 1 && pitch >= 0 && out);
+    size_t bytes = 0;                                        // the source bytes the n windows span
+    for (int i = 0; i < n; ++i) {
+        const int h = hw[2 * i], w = hw[2 * i + 1];
+        ARG_CHECK(h >= 1 && w >= 1 && offsets[i] >= 0 && (pitch == 0 || w <= pitch));
+        const size_t end = (size_t)offsets[i] + ((size_t)(h - 1) * (pitch ? pitch : w) + w) * 3;
+        if (end > bytes) bytes = end;
+    }
+    CTX_ENTER(ctx);
+    uint8_t* dpk;
+    long long* doff;
+    int* dhw;
+    float* dout;
+    REID_TRY(dbg_upload(ctx, "dbgf.xu8", packed, bytes, &dpk));
+    REID_TRY(dbg_upload(ctx, "dbgf.off", offsets, (size_t)n, &doff));
+    REID_TRY(dbg_upload(ctx, "dbgf.hw", hw, (size_t)2 * n, &dhw));
+    REID_TRY(dbg_output(ctx, "dbgf.xf32", (size_t)n * 256 * 128 * 3, &dout));
+    REID_TRY(launch_resize_norm(ctx, dpk, doff, dhw, n, 256, 128, pitch, dout));
+    REID_TRY(dbg_download(ctx, out, dout, (size_t)n * 256 * 128 * 3));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_maxpool(reid_ctx* ctx, int f16, const void* x, int n, int h, int w, int c, void* out) {
+    ARG_CHECK(ctx && x && out && n >= 1 && h >= 1 && w >= 1 && c >= 1);
+    CTX_ENTER(ctx);
+    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    const size_t nin = (size_t)n * h * w * c, nout = (size_t)n * ho * wo * c;
+    if (f16) {
+        _Float16 *dx, *dout;
+        REID_TRY(dbg_upload(ctx, "dbgf.map16", (const _Float16*)x, nin, &dx));
+        REID_TRY(dbg_output(ctx, "dbgf.out16", nout, &dout));
+        REID_TRY(launch_maxpool3s2_f16(ctx, dx, n, h, w, c, dout));
+        REID_TRY(dbg_download(ctx, (_Float16*)out, dout, nout));
+    } else {
+        float *dx, *dout;
+        REID_TRY(dbg_upload(ctx, "dbgf.map", (const float*)x, nin, &dx));
+        REID_TRY(dbg_output(ctx, "dbgf.out", nout, &dout));
+        REID_TRY(launch_maxpool3s2(ctx, dx, n, h, w, c, dout));
+        REID_TRY(dbg_download(ctx, (float*)out, dout, nout));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}

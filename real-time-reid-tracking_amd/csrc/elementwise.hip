@@ -33,8 +33,12 @@ __global__ void nchw_to_nhwc3_kernel(const float* __restrict__ x, long long npix
 
 // ---- Extractor._preprocess (feature_extractor.py:31-46): u8/255 -> bilinear resize (cv2 INTER_LINEAR: half-pixel
 // centres, edge clamp, no antialias, horizontal then vertical fp32 lerp) -> (x-0.5)/0.5, NHWC out.
-// Unfused mul/add (_rn intrinsics) so the result is bit-identical to the numpy oracle.
+// Every multiply and add rounds on its own, as numpy's do, so the result is bit-identical to the numpy oracle
+// (tests/test_gpu_frontend.py::test_resize_on_device): plain * and + under fp contract(off).  The __fmul_rn / __fadd_rn intrinsics this
+// used before are inline * and + compiled under the default fp-contract=fast, which fused each lerp into an FMA wherever they were
+// inlined (a 1-ulp difference in every tenth output of a resized crop); the pragma is lexical and does not reach into them.
 __device__ __forceinline__ void lin_tap(int d, int dst, int src, int& s, float& f) {
+#pragma clang fp contract(off)
     const double scale = (double)src / (double)dst;
     float fx = (float)(((double)d + 0.5) * scale - 0.5);
     int sx = (int)floorf(fx);
@@ -47,6 +51,7 @@ __device__ __forceinline__ void lin_tap(int d, int dst, int src, int& s, float& 
 // pitch: source row length in pixels (0: the crop's own width, packed crops; frame width when the crops are windows of a frame)
 __global__ void resize_norm_kernel(const uint8_t* __restrict__ packed, const long long* __restrict__ offsets,
                                    const int* __restrict__ hw, int n, int H, int W, int pitch, float* __restrict__ out) {
+#pragma clang fp contract(off)
     const long long total = (long long)n * H * W;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int img = (int)(i / (H * W));
@@ -60,17 +65,17 @@ __global__ void resize_norm_kernel(const uint8_t* __restrict__ packed, const lon
         lin_tap(dx, W, w, sx, fx);
         lin_tap(dy, H, h, sy, fy);
         const int sx1 = min(sx + 1, w - 1), sy1 = min(sy + 1, h - 1);
-        const float gx = __fsub_rn(1.0f, fx), gy = __fsub_rn(1.0f, fy);
+        const float gx = 1.0f - fx, gy = 1.0f - fy;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float p00 = (float)src[(sy * ps + sx) * 3 + c] / 255.0f;
             const float p01 = (float)src[(sy * ps + sx1) * 3 + c] / 255.0f;
             const float p10 = (float)src[(sy1 * ps + sx) * 3 + c] / 255.0f;
             const float p11 = (float)src[(sy1 * ps + sx1) * 3 + c] / 255.0f;
-            const float r0 = __fadd_rn(__fmul_rn(p00, gx), __fmul_rn(p01, fx));
-            const float r1 = __fadd_rn(__fmul_rn(p10, gx), __fmul_rn(p11, fx));
-            const float v = __fadd_rn(__fmul_rn(r0, gy), __fmul_rn(r1, fy));
-            out[i * 3 + c] = __fsub_rn(v, 0.5f) / 0.5f;
+            const float r0 = p00 * gx + p01 * fx;
+            const float r1 = p10 * gx + p11 * fx;
+            const float v = r0 * gy + r1 * fy;
+            out[i * 3 + c] = (v - 0.5f) / 0.5f;
         }
     }
 }

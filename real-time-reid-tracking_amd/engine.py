@@ -534,6 +534,45 @@ class Engine:
             _ptr(_f32(shift)), _ptr(g), _ptr(e)))
         return g, e
 
+    def debug_stem(self, form, x, w, scale, shift):
+        """The stem + max-pool through the forward's launchers (libreid_hip_debug.so reid_debug_stem; forms in include/reid_hip_debug.h).
+        x [n, 256, 128, 3] uint8 crops or fp32 (already normalised), w [64, 7, 7, 3].  Returns (out, out16), None where the form has no
+        such output: out fp32 [n, 128, 64, 64] (form 0) or [n, 64, 32, 64] (1, 2, 6); out16 uint16 f16 bits [n 64 32, 128] = [xh | xl']
+        (form 2) or [n, 64, 32, 64] (3-5).  Unwritten outputs read as NaN."""
+        is_u8 = np.asarray(x).dtype == np.uint8
+        x = np.ascontiguousarray(x, np.uint8) if is_u8 else _f32(x)
+        n = x.shape[0]
+        if x.shape[1:] != (IMG_H, IMG_W, 3) or np.shape(w) != (64, 7, 7, 3):
+            raise ValueError("debug_stem expects x[n, 256, 128, 3] and w[64, 7, 7, 3]")
+        out = np.empty((n, 128, 64, 64) if form == 0 else (n, 64, 32, 64), np.float32) if form in (0, 1, 2, 6) else None
+        o16 = np.empty((n * 2048, 128), np.uint16) if form == 2 else (np.empty((n, 64, 32, 64), np.uint16) if form in (3, 4, 5) else None)
+        check(_ffi.debug_lib().reid_debug_stem(self.h, C.c_int(form), C.c_int(int(is_u8)), _ptr(x), C.c_int(n), _ptr(_f32(w)),
+                                               _ptr(_f32(scale)), _ptr(_f32(shift)), _ptr(out), _ptr(o16)))
+        return out, o16
+
+    def debug_resize_norm(self, packed, offsets, hw, pitch=0):
+        """resize_norm_kernel through its launcher (reid_debug_resize_norm): windows of hw[i] = (h, w) pixels at byte offsets[i] of the
+        uint8 buffer `packed`, rows `pitch` pixels apart (0: packed crops).  Returns fp32 [n, 256, 128, 3]."""
+        packed = np.ascontiguousarray(packed, np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        hw = np.ascontiguousarray(hw, np.int32).reshape(-1, 2)
+        n = len(offsets)
+        end = max(int(o) + ((int(h) - 1) * (pitch or int(w)) + int(w)) * 3 for o, (h, w) in zip(offsets, hw))
+        if len(hw) != n or end > packed.size:
+            raise ValueError("debug_resize_norm: a window leaves the buffer")
+        out = np.empty((n, IMG_H, IMG_W, 3), np.float32)
+        check(_ffi.debug_lib().reid_debug_resize_norm(self.h, _ptr(packed), _ptr(offsets), _ptr(hw), C.c_int(n), C.c_int(int(pitch)), _ptr(out)))
+        return out
+
+    def debug_maxpool(self, x):
+        """MaxPool(3, 2, 1) through the forward's launcher (reid_debug_maxpool): x [n, h, w, c] fp32, or uint16 f16 bits; same type back."""
+        f16 = np.asarray(x).dtype == np.uint16
+        x = np.ascontiguousarray(x, np.uint16) if f16 else _f32(x)
+        n, h, w, c = x.shape
+        out = np.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), x.dtype)
+        check(_ffi.debug_lib().reid_debug_maxpool(self.h, C.c_int(int(f16)), _ptr(x), C.c_int(n), C.c_int(h), C.c_int(w), C.c_int(c), _ptr(out)))
+        return out
+
     def debug_window_attn_cos(self, mode, qkv, bias, scale, shifted):
         """The Swin v2 cosine window attention alone (libreid_hip_debug.so reid_debug_window_attn_cos).  qkv [n, h, w, 3 * heads * 32]
         fp32, bias [heads, 49, 49] (query, key), scale [heads].  mode 0 -> fp32 [n, h, w, C]; mode 2 -> the [oh | ol'] pair decoded

@@ -754,7 +754,7 @@ def test_nn_matching_edge_cases(eng):
 def test_embed_from_frame_equals_host_sliced_crops(eng_w0):
     """Extractor.from_frame(bbox_xywh, frame) == Extractor([frame[y1:y2, x1:x2] ...]) bit for bit (same taps, the frame is
     only indexed with a pitch), incl. boxes touching the frame border and a 3-pixel-wide window.  The host-sliced path is
-    itself checked against the oracle's resize in test_ragged_crops_resize_on_device."""
+    itself checked against the oracle's resize in tests/test_gpu_frontend.py::test_resize_on_device."""
     from reid_amd.extractor import Extractor
     eng, sd = eng_w0
     ext = Extractor(sd)
