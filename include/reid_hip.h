@@ -173,6 +173,20 @@ int reid_swin_load(reid_ctx* ctx, const float* blob, size_t n_floats, const char
 int reid_swin_dims(reid_ctx* ctx, int* embed_dim, int* num_class);
 int reid_swin_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits);
 int reid_swin_embed_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits);
+/* The same model fed the way a tracker feeds it - the reference registers swin_transformer as a tracker ReID model
+ * (modification_tracking/models/__init__.py:80, reid_model_factory.py:9) and its Extractor hands over uint8 crops of any size
+ * (feature_extractor.py:31-53).  ragged: crops as for reid_embed_ragged_u8; frame: windows of one frame as for reid_embed_frame_u8
+ * (DeepSort._get_features).  Each crop is resized (bilinear, the taps of the ResNet entry points) to out_h x out_w - multiples of 224;
+ * the reference uses 224x224 and 448x224 - and normalised as (x / 255 - mean[c]) / std[c], mean_std6 = mean[3] then std[3] (std > 0),
+ * NULL = ImageNet's 0.485, 0.456, 0.406 / 0.229, 0.224, 0.225 (reid/data_transforms.py:64).  Resize, normalisation and the stem's first
+ * convolution are one kernel of libreid_hip_swin_crops.so, which must lie beside this library (REID_ERR_STATE naming it otherwise); the
+ * result is bit-identical to reid_swin_embed_f32_nchw on the same crops preprocessed in fp32 on the host.  emb fp32[n][96], logits
+ * fp32[n][num_class] or NULL.  Passes of min(chunk, the Swin pass cap) crops; with several, reid_swin_embed_ragged_u8 moves pass k + 1's
+ * crops up and pass k - 1's embeddings down under pass k's kernels.  reid_ctx_set_side_index applies as to the float entries. */
+int reid_swin_embed_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,
+                              const float* mean_std6, float* emb, float* logits);
+int reid_swin_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame_hwc, int fh, int fw, const int32_t* boxes_xyxy, int n, int out_h, int out_w,
+                             const float* mean_std6, float* emb, float* logits);
 
 /* ---- matching ----------------------------------------------------------------------------- */
 /* out[m][n] = metric(x[m][d], y[n][d])        reid/losses/utils.py:12-35, reid/evaluate.py:58 */

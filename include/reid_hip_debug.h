@@ -90,6 +90,14 @@ int reid_debug_stem(reid_ctx* ctx, int form, int is_u8, const void* x, int n, co
 /* resize_norm: n uint8 windows of hw[i] = (h, w) pixels at byte offsets[i] of `packed`, rows `pitch` pixels apart (0: the window's own
  * width), bilinear to 256 x 128 and normalised -> out [n][256][128][3] fp32. */
 int reid_debug_resize_norm(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch, float* out);
+/* swin_crop_front: the one kernel of libreid_hip_swin_crops.so (csrc/swin_crops.hip; tests/test_gpu_swin_crops.py) through the launcher the
+ * Swin crops entry points call: windows as for resize_norm, bilinear to out_h x out_w (multiples of 224), (v - mean) / std with mean_std6 =
+ * mean[3], std[3], then ShadowFeatureExtraction's first convolution (2x2 stride 2, 3 -> 12, c1_w [12][(kh, kw, c)], c1_b [12]) ->
+ * out [n][out_h / 2][out_w / 2][12] fp32.  swin_conv1: the stem of the float entry points (sfe_conv1_kernel) alone, x fp32 NCHW
+ * [n][3][h][w] -> out [n][h / 2][w / 2][12]. */
+int reid_debug_swin_crop_front(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch, int out_h,
+                               int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out);
+int reid_debug_swin_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out);
 /* maxpool: MaxPool(3, 2, 1) of x NHWC [n][h][w][c] -> out [n][(h - 1) / 2 + 1][(w - 1) / 2 + 1][c], fp32 (f16 = 0) or raw f16 bits. */
 int reid_debug_maxpool(reid_ctx* ctx, int f16, const void* x, int n, int h, int w, int c, void* out);
 /* The two kernels of the Swin "v2" blocks alone (csrc/swin_v2.hip; correctness harnesses, tests/test_gpu_swin_v2.py), each through the

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import precision as _precision
 from . import synth, weights
-from .engine import IMG_H, IMG_W, get_engine
+from .engine import IMG_H, IMG_W, Engine, get_engine
 
 
 def _device_index(device):
@@ -380,6 +380,18 @@ class SwinT:
         return (logits, emb) if return_logits else emb
 
     forward = __call__
+
+    def embed_crops(self, crops, size=(224, 224)):
+        """uint8 HxWx3 crops of any size -> float32[N,96]: bilinear resize to ``size`` = (H, W) (multiples of 224), ImageNet
+        normalisation (reid/data_transforms.py:64) and the stem's first convolution in one kernel on the device."""
+        crops = list(crops)
+        Engine._swin_crop_args(size, None)                  # a bad size raises here, before anything is bound or launched
+        return self._run(lambda eng: eng.swin_embed_ragged_u8(crops, size=size))
+
+    def embed_frame(self, frame, boxes_xyxy, size=(224, 224)):
+        """Windows frame[y1:y2, x1:x2] of one uint8 frame (int boxes [N,4] as x1,y1,x2,y2) -> float32[N,96]; the frame is uploaded once."""
+        Engine._swin_crop_args(size, None)
+        return self._run(lambda eng: eng.swin_embed_frame_u8(frame, boxes_xyxy, size=size))
 
 
 def swin_t(num_classes=751, loss="softmax", pretrained=False, use_gpu=True, **kwargs):

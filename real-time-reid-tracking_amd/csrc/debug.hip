@@ -992,6 +992,54 @@ extern "C" int reid_debug_resize_norm(reid_ctx* ctx, const uint8_t* packed, cons
     return ctx_fault_status(ctx);
 }
 
+// swin_crop_front_kernel (swin_crops.hip) through the launcher the crops entry points call, on host operands: windows as for
+// reid_debug_resize_norm, c1_w [12][(kh, kw, c)], c1_b [12] -> out [n][out_h / 2][out_w / 2][12].  Every window is checked against the
+// bytes uploaded before anything is launched.
+extern "C" int reid_debug_swin_crop_front(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch,
+                                          int out_h, int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out) {
+    ARG_CHECK(ctx && packed && offsets && hw && n >= 1 && pitch >= 0 && mean_std6 && c1_w && c1_b && out);
+    REID_TRY(swin_crops_check(out_h, out_w, mean_std6));
+    size_t bytes = 0;                                        // the source bytes the n windows span
+    for (int i = 0; i < n; ++i) {
+        const int h = hw[2 * i], w = hw[2 * i + 1];
+        ARG_CHECK(h >= 1 && w >= 1 && offsets[i] >= 0 && (pitch == 0 || w <= pitch));
+        const size_t end = (size_t)offsets[i] + ((size_t)(h - 1) * (pitch ? pitch : w) + w) * 3;
+        if (end > bytes) bytes = end;
+    }
+    CTX_ENTER(ctx);
+    uint8_t* dpk;
+    long long* doff;
+    int* dhw;
+    float *dw, *db, *dout;
+    const size_t nout = (size_t)n * (out_h / 2) * (out_w / 2) * 12;
+    REID_TRY(dbg_upload(ctx, "dbgf.xu8", packed, bytes, &dpk));
+    REID_TRY(dbg_upload(ctx, "dbgf.off", offsets, (size_t)n, &doff));
+    REID_TRY(dbg_upload(ctx, "dbgf.hw", hw, (size_t)2 * n, &dhw));
+    REID_TRY(dbg_upload(ctx, "dbgf.c1w", c1_w, (size_t)144, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgf.c1b", c1_b, (size_t)12, &db));
+    REID_TRY(dbg_output(ctx, "dbgf.c1", nout, &dout));
+    REID_TRY(launch_swin_crop_front(ctx, dpk, doff, dhw, n, out_h, out_w, pitch, mean_std6, dw, db, dout));
+    REID_TRY(dbg_download(ctx, out, dout, nout));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// sfe_conv1_kernel (swin.hip), the stem the float entry points run, through its launcher: x fp32 NCHW [n][3][h][w] -> out [n][h / 2][w / 2][12]
+extern "C" int reid_debug_swin_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out) {
+    ARG_CHECK(ctx && x && n >= 1 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && c1_w && c1_b && out);
+    CTX_ENTER(ctx);
+    float *dx, *dw, *db, *dout;
+    const size_t nout = (size_t)n * (h / 2) * (w / 2) * 12;
+    REID_TRY(dbg_upload(ctx, "dbgf.xf32", x, (size_t)n * 3 * h * w, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgf.c1w", c1_w, (size_t)144, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgf.c1b", c1_b, (size_t)12, &db));
+    REID_TRY(dbg_output(ctx, "dbgf.c1", nout, &dout));
+    REID_TRY(launch_sfe_conv1(ctx, dx, n, h, w, dw, db, dout));
+    REID_TRY(dbg_download(ctx, out, dout, nout));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 extern "C" int reid_debug_maxpool(reid_ctx* ctx, int f16, const void* x, int n, int h, int w, int c, void* out) {
     ARG_CHECK(ctx && x && out && n >= 1 && h >= 1 && w >= 1 && c >= 1);
     CTX_ENTER(ctx);

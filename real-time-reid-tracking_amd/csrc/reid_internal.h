@@ -214,6 +214,12 @@ int launch_window_attn_cos(reid_ctx* ctx, int mode, const void* qkv, int ldq, in
                            const float* bias_t, const float* scale, void* out);
 int launch_post_norm(reid_ctx* ctx, int side_mode, const float* x, const float* y, long long T, int C, const float* g, const float* b,
                      float* out, _Float16* side);
+// swin.hip: the two stems of the Swin forward, each writing c1 [n][h / 2][w / 2][12] - sfe_conv1_kernel from normalised NCHW images, and
+// swin_crop_front_kernel (libreid_hip_swin_crops.so, swin_crops.h) from uint8 windows; mean_std6 is a host pointer
+int launch_sfe_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* c1);
+int swin_crops_check(int out_h, int out_w, const float* mean_std6);   // sizes multiples of 224, mean finite, std > 0 (REID_ERR_ARG otherwise)
+int launch_swin_crop_front(reid_ctx* ctx, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
+                           const float* mean_std6, const float* c1_w, const float* c1_b, float* c1);
 int launch_split_pack(reid_ctx* ctx, const float* x, long long rows, int C, _Float16* out, const float* d_scale = nullptr);           // fp32 [rows][C] -> f16 [rows][2C] = [xh | xl']
 int launch_split_weights(reid_ctx* ctx, const float* w, int cout, int taps, int cin, int terms, _Float16* out, const float* d_scale = nullptr);  // fp32 [cout][taps][cin] -> f16 [cout][taps][terms * cin]
 // fp16 elementwise kernels (elementwise_f16.hip)

@@ -8,6 +8,7 @@
 // reads and writes token ((y'+3) % H, (x'+3) % W).
 #include "reid_internal.h"
 #include "swin_v2.h"
+#include "swin_crops.h"
 #include <dlfcn.h>
 #include <mutex>
 #include <math.h>
@@ -1157,6 +1158,37 @@ static int swin_v2_api(const SwinV2Api** out) {
     return REID_OK;
 }
 
+// libreid_hip_swin_crops.so (swin_crops.h), opened the same way on the first crops call (reid_swin_embed_ragged_u8 / _frame_u8, or their
+// harness): a process that only embeds float images never opens it.  Missing library or symbol: REID_ERR_STATE naming the file - there
+// is no other path from uint8 crops to the Swin stem.
+static int swin_crops_api(decltype(&swin_crops_front)* out) {
+    static std::mutex m;
+    static decltype(&swin_crops_front) front = nullptr;
+    std::lock_guard<std::mutex> lk(m);
+    if (!front) {
+        Dl_info info;
+        std::string path = "libreid_hip_swin_crops.so";
+        if (dladdr((const void*)&swin_crops_api, &info) && info.dli_fname) {
+            const std::string self = info.dli_fname;
+            const size_t slash = self.rfind('/');
+            if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
+        }
+        void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        if (!h) {
+            reid_set_error("Swin from uint8 crops needs %s beside libreid_hip.so: %s", path.c_str(), dlerror());
+            return REID_ERR_STATE;
+        }
+        auto f = (decltype(front))dlsym(h, "swin_crops_front");
+        if (!f) {
+            reid_set_error("%s lacks swin_crops_front", path.c_str());
+            return REID_ERR_STATE;
+        }
+        front = f;
+    }
+    *out = front;
+    return REID_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ weights
 struct SwinBlockW {
     // v2: no pos; bias_t = the block's position-bias table as [head][key 49][query 64] (made at load time from the blob's
@@ -1581,12 +1613,84 @@ static int swin_block_v2(reid_ctx* ctx, const SwinBlockW& k, const SwinBlockW16&
 }
 
 // ------------------------------------------------------------------------------------------------ forward
+// The two stems.  Both write ShadowFeatureExtraction's first convolution, c1 [n][h / 2][w / 2][12]; swin_body goes on from there.
+// From NCHW: sfe_conv1_kernel on normalised fp32 images [n][3][h][w] on the device.  This launcher, with a profiling bracket of its own,
+// serves the harness (reid_debug_swin_conv1); the forward launches the kernel inside the stem's one bracket, as it always has (swin_body).
+int launch_sfe_conv1(reid_ctx* ctx, const float* x, int n, int h, int wd, const float* c1_w, const float* c1_b, float* c1) {
+    if (!x || !c1_w || !c1_b || !c1 || n < 1 || h < 2 || wd < 2 || (h & 1) || (wd & 1)) {
+        reid_set_error("launch_sfe_conv1: bad arguments (%d images of %d x %d)", n, h, wd);
+        return REID_ERR_ARG;
+    }
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * wd * (12 + 12));
+    hipLaunchKernelGGL(sfe_conv1_kernel, dim3(grid_for((long long)n * (h / 2) * (wd / 2), 256)), dim3(256), 0, ctx->stream, x, n, h,
+                       wd, c1_w, c1_b, c1);
+    prof_end(ctx);
+    LAUNCH_CHECK();
+    return REID_OK;
+}
+
+// out_h x out_w multiples of 224, mean finite, std finite and positive: the one check of the crops entry points and of the harness
+int swin_crops_check(int out_h, int out_w, const float* mean_std6) {
+    if (!mean_std6 || out_h <= 0 || out_w <= 0 || out_h % 224 || out_w % 224) {
+        reid_set_error("Swin crops: the output size must be multiples of 224 and mean / std given, got %d x %d", out_h, out_w);
+        return REID_ERR_ARG;
+    }
+    for (int c = 0; c < 3; ++c)
+        if (!(mean_std6[3 + c] > 0.f) || !std::isfinite(mean_std6[3 + c]) || !std::isfinite(mean_std6[c])) {
+            reid_set_error("Swin crops: mean must be finite and std positive (channel %d: mean %g, std %g)", c, mean_std6[c], mean_std6[3 + c]);
+            return REID_ERR_ARG;
+        }
+    return REID_OK;
+}
+
+// From uint8 windows: swin_crop_front_kernel (libreid_hip_swin_crops.so) - resize, normalise and the same convolution in one launch.
+// d_src / d_off / d_hw on the device (window i: d_hw[2i] x d_hw[2i + 1] pixels at byte d_off[i], rows `pitch` pixels apart, 0 = its own
+// width); mean_std6 on the HOST.  The callers have checked that every window lies inside d_src.
+int launch_swin_crop_front(reid_ctx* ctx, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int wd, int pitch,
+                           const float* mean_std6, const float* c1_w, const float* c1_b, float* c1) {
+    if (!d_src || !d_off || !d_hw || !mean_std6 || !c1_w || !c1_b || !c1 || n < 1 || h < 224 || wd < 224 || h % 224 || wd % 224 || pitch < 0) {
+        reid_set_error("launch_swin_crop_front: bad arguments (%d windows to %d x %d, pitch %d)", n, h, wd, pitch);
+        return REID_ERR_ARG;
+    }
+    decltype(&swin_crops_front) front;
+    REID_TRY(swin_crops_api(&front));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * wd * 12);
+    const hipError_t e = front(ctx->stream, d_src, d_off, d_hw, n, h, wd, pitch, mean_std6, c1_w, c1_b, c1);
+    prof_end(ctx);
+    HIP_TRY(e);
+    return REID_OK;
+}
+
+static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float* c1, int n, int h, int wd, float* d_emb, float* d_logits);
+
+static int swin_c1(reid_ctx* ctx, int n, int h, int wd, float** c1) {
+    return ctx_ws(ctx, "swin.c1", (size_t)n * (h / 2) * (wd / 2) * 12 * 4, (void**)c1);
+}
+
 // x: fp32 NCHW [n][3][h][w] on the device; h, w multiples of 224
 static int swin_forward(reid_ctx* ctx, const SwinWeights& w, const float* x, int n, int h, int wd, float* d_emb, float* d_logits) {
+    float* c1;
+    REID_TRY(swin_c1(ctx, n, h, wd, &c1));
+    return swin_body(ctx, w, x, c1, n, h, wd, d_emb, d_logits);
+}
+
+// n uint8 windows on the device -> embeddings: the fused stem, then the common body
+static int swin_forward_crops(reid_ctx* ctx, const SwinWeights& w, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n,
+                              int h, int wd, int pitch, const float* mean_std6, float* d_emb, float* d_logits) {
+    float* c1;
+    REID_TRY(swin_c1(ctx, n, h, wd, &c1));
+    REID_TRY(launch_swin_crop_front(ctx, d_src, d_off, d_hw, n, h, wd, pitch, mean_std6, w.c1_w, w.c1_b, c1));
+    return swin_body(ctx, w, nullptr, c1, n, h, wd, d_emb, d_logits);
+}
+
+// The common body: from c1 [n][h / 2][w / 2][12] to the embeddings.  x != nullptr (the float entries): c1 is still to be written, by the
+// stem from NCHW - sfe_conv1_kernel's launch, first in the stem's one profiling bracket, where it has always been.  x == nullptr (the
+// crops entries): the fused stem has filled c1 on this stream.  The side index (reid_ctx_set_side_index) is taken here, so it serves every
+// entry point.
+static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float* c1, int n, int h, int wd, float* d_emb, float* d_logits) {
     const int H1 = h / 4, W1 = wd / 4;
     const long long T1 = (long long)n * H1 * W1;   // tokens of stage 1
-    float *c1, *ab, *sfe, *xs[4], *lnb, *big, *att, *tmp, *f3, *f2, *f1, *gem;
-    REID_TRY(ctx_ws(ctx, "swin.c1", (size_t)n * (h / 2) * (wd / 2) * 12 * 4, (void**)&c1));
+    float *ab, *sfe, *xs[4], *lnb, *big, *att, *tmp, *f3, *f2, *f1, *gem;
     REID_TRY(ctx_ws(ctx, "swin.ab", (size_t)n * 24 * 4, (void**)&ab));
     REID_TRY(ctx_ws(ctx, "swin.sfe", (size_t)T1 * 96 * 4, (void**)&sfe));
     for (int s = 0; s < 4; ++s) {
@@ -1605,8 +1709,9 @@ static int swin_forward(reid_ctx* ctx, const SwinWeights& w, const float* x, int
 
     // stem
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, 0);
-    hipLaunchKernelGGL(sfe_conv1_kernel, dim3(grid_for((long long)n * (h / 2) * (wd / 2), 256)), dim3(256), 0, ctx->stream, x, n, h,
-                       wd, w.c1_w, w.c1_b, c1);
+    if (x)
+        hipLaunchKernelGGL(sfe_conv1_kernel, dim3(grid_for((long long)n * (h / 2) * (wd / 2), 256)), dim3(256), 0, ctx->stream, x, n, h,
+                           wd, w.c1_w, w.c1_b, c1);
     hipLaunchKernelGGL(sfe_norm_kernel, dim3(n), dim3(256), 0, ctx->stream, c1, (h / 2) * (wd / 2), w.in_g, w.in_b, w.bn_s, w.bn_t, ab);
     hipLaunchKernelGGL(sfe_conv2_fc_kernel, dim3(grid_for(T1, 256)), dim3(256), 0, ctx->stream, c1, ab, n, h / 2, wd / 2, w.c2_w,
                        w.c2_b, w.fc_w, w.fc_b, sfe);
@@ -1895,5 +2000,125 @@ extern "C" int reid_swin_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, in
             if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
             return REID_OK;
         }));
+    return ctx_fault_status(ctx);
+}
+
+// ---- uint8 crops in, embeddings out: the tracker's way of feeding a ReID model (Extractor.__call__, feature_extractor.py:48-53, and
+// DeepSort._get_features) for the reference's swin_transformer tracker model (modification_tracking/models/__init__.py:80), with its
+// transform for transformer models (reid/data_transforms.py:64: resize to out_h x out_w, ImageNet mean / std)
+static const float kImagenetMeanStd[6] = {0.485f, 0.456f, 0.406f, 0.229f, 0.224f, 0.225f};
+
+static int swin_crops_args(int out_h, int out_w, const float** mean_std6) {
+    if (!*mean_std6) *mean_std6 = kImagenetMeanStd;
+    return swin_crops_check(out_h, out_w, *mean_std6);
+}
+
+extern "C" int reid_swin_embed_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                         int out_w, const float* mean_std6, float* emb, float* logits) {
+    ARG_CHECK(ctx && packed && offsets && hw && emb && n >= 0);
+    REID_TRY(swin_crops_args(out_h, out_w, &mean_std6));
+    size_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        ARG_CHECK(hw[2 * i] >= 1 && hw[2 * i + 1] >= 1 && offsets[i] >= 0);
+        const size_t e = (size_t)offsets[i] + (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
+        if (e > total) total = e;
+    }
+    CTX_ENTER(ctx);
+    const SwinWeights* swp = swin_find(ctx);
+    if (!swp || !swp->loaded) {
+        reid_set_error("reid_swin_embed_*: call reid_swin_load first");
+        return REID_ERR_STATE;
+    }
+    if (n == 0) return REID_OK;
+    const SwinWeights& sw = *swp;
+    const int nc = sw.num_class;
+    uint8_t* d_pk;
+    char* d_meta;
+    float *d_emb, *d_log = nullptr;
+    REID_TRY(ctx_ws(ctx, "io.in", total, (void**)&d_pk));
+    REID_TRY(ctx_ws(ctx, "io.meta", (size_t)n * 16, (void**)&d_meta));
+    long long* d_off = (long long*)d_meta;
+    int* d_hw = (int*)(d_meta + (size_t)n * 8);
+    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 96 * 4, (void**)&d_emb));
+    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
+    const int chunk = ctx->chunk < ctx->swin_chunk_cap ? ctx->chunk : ctx->swin_chunk_cap;   // = reid_swin_embed_f32_nchw's passes
+    // host in -> host out as reid_embed_ragged_u8: the bytes a pass reads are the span [lowest offset, highest end) of its crops (crop after
+    // crop, the usual packing, makes the spans a partition of the buffer); pass k + 1's span goes up and pass k - 1's embeddings come
+    // down under pass k's kernels (host_passes).  One pass, or host_pipeline = 0: one span, everything on the compute stream.
+    REID_TRY(host_passes(
+        ctx, n, chunk,
+        [&](int i, int m, hipStream_t s) -> int {
+            size_t lo = (size_t)-1, hi = 0;
+            for (int j = i; j < i + m; ++j) {
+                const size_t b = (size_t)offsets[j], e = b + (size_t)hw[2 * j] * hw[2 * j + 1] * 3;
+                if (b < lo) lo = b;
+                if (e > hi) hi = e;
+            }
+            if (i == 0) {
+                HIP_TRY(hipMemcpyAsync(d_off, offsets, (size_t)n * 8, hipMemcpyHostToDevice, s));
+                HIP_TRY(hipMemcpyAsync(d_hw, hw, (size_t)n * 8, hipMemcpyHostToDevice, s));
+            }
+            HIP_TRY(hipMemcpyAsync(d_pk + lo, packed + lo, hi - lo, hipMemcpyHostToDevice, s));
+            return REID_OK;
+        },
+        [&](int i, int m) -> int {
+            return swin_forward_crops(ctx, sw, d_pk, d_off + i, d_hw + 2 * i, m, out_h, out_w, 0, mean_std6, d_emb + (size_t)i * 96,
+                                      d_log ? d_log + (size_t)i * nc : nullptr);
+        },
+        [&](int i, int m, hipStream_t s) -> int {
+            HIP_TRY(hipMemcpyAsync(emb + (size_t)i * 96, d_emb + (size_t)i * 96, (size_t)m * 96 * 4, hipMemcpyDeviceToHost, s));
+            if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
+            return REID_OK;
+        }));
+    return ctx_fault_status(ctx);
+}
+
+// Windows frame[y1:y2, x1:x2] of ONE frame, as reid_embed_frame_u8: the frame goes up once, every window is resized straight out of it
+// (same taps, clamped to the WINDOW's border: bit-identical to the same pixels handed over as packed crops).
+extern "C" int reid_swin_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame, int fh, int fw, const int32_t* boxes_xyxy, int n, int out_h,
+                                        int out_w, const float* mean_std6, float* emb, float* logits) {
+    ARG_CHECK(ctx && frame && boxes_xyxy && emb && fh >= 1 && fw >= 1 && n >= 0);
+    REID_TRY(swin_crops_args(out_h, out_w, &mean_std6));
+    std::vector<long long> off(n);
+    std::vector<int> hw(2 * (size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const int x1 = boxes_xyxy[4 * i], y1 = boxes_xyxy[4 * i + 1], x2 = boxes_xyxy[4 * i + 2], y2 = boxes_xyxy[4 * i + 3];
+        ARG_CHECK(x1 >= 0 && y1 >= 0 && x2 <= fw && y2 <= fh && x2 > x1 && y2 > y1);   // an empty slice fails in cv2.resize too
+        off[i] = ((long long)y1 * fw + x1) * 3;
+        hw[2 * i] = y2 - y1;
+        hw[2 * i + 1] = x2 - x1;
+    }
+    CTX_ENTER(ctx);
+    const SwinWeights* swp = swin_find(ctx);
+    if (!swp || !swp->loaded) {
+        reid_set_error("reid_swin_embed_*: call reid_swin_load first");
+        return REID_ERR_STATE;
+    }
+    if (n == 0) return REID_OK;
+    const SwinWeights& sw = *swp;
+    const int nc = sw.num_class;
+    uint8_t* d_fr;
+    long long* d_off;
+    int* d_hw;
+    float *d_emb, *d_log = nullptr;
+    const size_t total = (size_t)fh * fw * 3;
+    REID_TRY(ctx_ws(ctx, "io.in", total, (void**)&d_fr));
+    REID_TRY(ctx_ws(ctx, "io.off", (size_t)n * 8, (void**)&d_off));
+    REID_TRY(ctx_ws(ctx, "io.hw", (size_t)n * 8, (void**)&d_hw));
+    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 96 * 4, (void**)&d_emb));
+    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
+    HIP_TRY(hipMemcpyAsync(d_fr, frame, total, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_hw, hw.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));   // off / hw are locals
+    const int chunk = ctx->chunk < ctx->swin_chunk_cap ? ctx->chunk : ctx->swin_chunk_cap;
+    for (int i = 0; i < n; i += chunk) {
+        const int m = n - i < chunk ? n - i : chunk;
+        REID_TRY(swin_forward_crops(ctx, sw, d_fr, d_off + i, d_hw + 2 * i, m, out_h, out_w, fw, mean_std6, d_emb + (size_t)i * 96,
+                                    d_log ? d_log + (size_t)i * nc : nullptr));
+    }
+    HIP_TRY(hipMemcpyAsync(emb, d_emb, (size_t)n * 96 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (logits) HIP_TRY(hipMemcpyAsync(logits, d_log, (size_t)n * nc * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }

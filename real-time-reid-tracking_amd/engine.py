@@ -204,6 +204,49 @@ class Engine:
         check(self.lib.reid_swin_embed_f32_nchw_dev(self.h, C.c_void_p(d_x), int(n), int(h), int(w), C.c_void_p(d_emb),
                                                     C.c_void_p(d_logits or 0)))
 
+    @staticmethod
+    def _swin_crop_args(size, mean_std):
+        """(H, W) multiples of 224 and mean[3] / std[3] (None: the library's ImageNet default), checked before any device call."""
+        try:
+            h, w = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError("size must be (H, W), got %r" % (size,))
+        if h <= 0 or w <= 0 or h % 224 or w % 224:
+            raise ValueError("Swin crops are resized to multiples of 224 (the reference uses 224x224 and 448x224), got size (H, W) = %r" % (size,))
+        ms = None
+        if mean_std is not None:
+            ms = _f32(mean_std).reshape(-1)
+            if ms.size != 6 or not np.isfinite(ms).all() or not (ms[3:] > 0).all():
+                raise ValueError("mean_std must be (mean[3], std[3]) with finite values and std > 0, got %r" % (mean_std,))
+        return h, w, ms
+
+    def swin_embed_ragged_u8(self, crops, size=(224, 224), mean_std=None, logits=False):
+        """list of uint8[h_i,w_i,3] -> float32[n,96] (and logits): each crop is resized to ``size`` = (H, W), normalised with ``mean_std``
+        = (mean[3], std[3]) (None: ImageNet, reid/data_transforms.py:64) and run through the Swin stem's first convolution in one kernel
+        (reid_swin_embed_ragged_u8); packing and passes as embed_ragged_u8."""
+        h, w, ms = self._swin_crop_args(size, mean_std)
+        n = len(crops)
+        src, offs, hw, _keep = self._pack_ragged(crops)
+        emb = np.empty((n, self.swin_dim), np.float32)
+        lg = np.empty((n, self.swin_num_class), np.float32) if logits else None
+        check(self.lib.reid_swin_embed_ragged_u8(self.h, src, _ptr(offs), _ptr(hw), n, h, w, _ptr(ms), _ptr(emb), _ptr(lg)))
+        return (emb, lg) if logits else emb
+
+    def swin_embed_frame_u8(self, frame, boxes_xyxy, size=(224, 224), mean_std=None, logits=False):
+        """uint8[H,W,3] frame + int boxes [n,4] (x1,y1,x2,y2; crop = frame[y1:y2, x1:x2]) -> float32[n,96] (and logits); ``size`` and
+        ``mean_std`` as swin_embed_ragged_u8 (reid_swin_embed_frame_u8)."""
+        h, w, ms = self._swin_crop_args(size, mean_std)
+        frame = np.ascontiguousarray(frame, dtype=np.uint8)
+        if frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError("frame must be uint8[H,W,3], got %s" % (frame.shape,))
+        boxes = np.ascontiguousarray(boxes_xyxy, dtype=np.int32).reshape(-1, 4)
+        n = boxes.shape[0]
+        emb = np.empty((n, self.swin_dim), np.float32)
+        lg = np.empty((n, self.swin_num_class), np.float32) if logits else None
+        check(self.lib.reid_swin_embed_frame_u8(self.h, _ptr(frame), frame.shape[0], frame.shape[1], _ptr(boxes), n, h, w, _ptr(ms), _ptr(emb),
+                                                _ptr(lg)))
+        return (emb, lg) if logits else emb
+
     # ---- embedding
     def _outs(self, n, want_logits):
         emb = np.empty((n, self.embed_dim), np.float32)
@@ -219,10 +262,10 @@ class Engine:
         check(self.lib.reid_embed_u8(self.h, _ptr(crops), crops.shape[0], _ptr(emb), _ptr(lg)))
         return (emb, lg) if logits else emb
 
-    def embed_ragged_u8(self, crops, logits=False):
-        """list of uint8[h_i,w_i,3] -> float32[n,512]; resize + normalise run on the device.  Crops that already lie one after
-        the other in ONE host buffer (views of a stacked array, slices of a pinned slab) are handed over in place - no packing copy;
-        more crops than a pass holds go up pass by pass under the kernels (csrc/api.hip reid_embed_ragged_u8)."""
+    @staticmethod
+    def _pack_ragged(crops):
+        """list of uint8[h_i,w_i,3] -> (source pointer, offsets int64[n], hw int32[n,2], keep-alive).  Crops that already lie one after
+        the other in ONE host buffer (views of a stacked array, slices of a pinned slab) are handed over in place - no packing copy."""
         n = len(crops)
         hw = np.empty((n, 2), np.int32)
         offs = np.empty(n, np.int64)
@@ -242,12 +285,18 @@ class Engine:
                 base = None
             total += c.size
             flat.append(c)
-        emb, lg = self._outs(n, logits)
         if base is not None and n:
-            src = C.c_void_p(base)               # `flat` keeps the views (and so their buffer) alive over the call
-        else:
-            packed = np.concatenate([c.reshape(-1) for c in flat]) if flat else np.empty(0, np.uint8)
-            src = _ptr(packed)
+            return C.c_void_p(base), offs, hw, flat        # `flat` keeps the views (and so their buffer) alive over the call
+        packed = np.concatenate([c.reshape(-1) for c in flat]) if flat else np.empty(0, np.uint8)
+        return _ptr(packed), offs, hw, packed
+
+    def embed_ragged_u8(self, crops, logits=False):
+        """list of uint8[h_i,w_i,3] -> float32[n,512]; resize + normalise run on the device.  Crops that already lie one after
+        the other in ONE host buffer (views of a stacked array, slices of a pinned slab) are handed over in place - no packing copy;
+        more crops than a pass holds go up pass by pass under the kernels (csrc/api.hip reid_embed_ragged_u8)."""
+        n = len(crops)
+        src, offs, hw, _keep = self._pack_ragged(crops)
+        emb, lg = self._outs(n, logits)
         check(self.lib.reid_embed_ragged_u8(self.h, src, _ptr(offs), _ptr(hw), n, _ptr(emb), _ptr(lg)))
         return (emb, lg) if logits else emb
 
@@ -562,6 +611,37 @@ class Engine:
             raise ValueError("debug_resize_norm: a window leaves the buffer")
         out = np.empty((n, IMG_H, IMG_W, 3), np.float32)
         check(_ffi.debug_lib().reid_debug_resize_norm(self.h, _ptr(packed), _ptr(offsets), _ptr(hw), C.c_int(n), C.c_int(int(pitch)), _ptr(out)))
+        return out
+
+    def debug_swin_crop_front(self, packed, offsets, hw, c1_w, c1_b, size=(224, 224), mean_std=None, pitch=0):
+        """swin_crop_front_kernel alone through its launcher (reid_debug_swin_crop_front): windows as debug_resize_norm, ``size`` = (H, W),
+        mean_std = (mean[3], std[3]) (None: ImageNet), c1_w [12, 2, 2, 3] / c1_b [12] -> fp32 [n, H / 2, W / 2, 12]."""
+        h_out, w_out, ms = self._swin_crop_args(size, mean_std)
+        if ms is None:
+            ms = _f32([0.485, 0.456, 0.406, 0.229, 0.224, 0.225])
+        packed = np.ascontiguousarray(packed, np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        hw = np.ascontiguousarray(hw, np.int32).reshape(-1, 2)
+        n = len(offsets)
+        end = max(int(o) + ((int(h) - 1) * (pitch or int(w)) + int(w)) * 3 for o, (h, w) in zip(offsets, hw))
+        if len(hw) != n or end > packed.size or int(offsets.min()) < 0 or int(hw.min()) < 1:
+            raise ValueError("debug_swin_crop_front: a window leaves the buffer")
+        c1_w, c1_b = _f32(c1_w).reshape(-1), _f32(c1_b).reshape(-1)
+        if c1_w.size != 144 or c1_b.size != 12:
+            raise ValueError("debug_swin_crop_front expects c1_w[12,2,2,3] and c1_b[12]")
+        out = np.empty((n, h_out // 2, w_out // 2, 12), np.float32)
+        check(_ffi.debug_lib().reid_debug_swin_crop_front(self.h, _ptr(packed), _ptr(offsets), _ptr(hw), C.c_int(n), C.c_int(int(pitch)),
+                                                          C.c_int(h_out), C.c_int(w_out), _ptr(ms), _ptr(c1_w), _ptr(c1_b), _ptr(out)))
+        return out
+
+    def debug_swin_conv1(self, x, c1_w, c1_b):
+        """sfe_conv1_kernel alone through its launcher (reid_debug_swin_conv1): x fp32 [n, 3, h, w] -> fp32 [n, h / 2, w / 2, 12]."""
+        x, c1_w, c1_b = _f32(x), _f32(c1_w).reshape(-1), _f32(c1_b).reshape(-1)
+        n, c, h, w = x.shape
+        if c != 3 or h % 2 or w % 2 or c1_w.size != 144 or c1_b.size != 12:
+            raise ValueError("debug_swin_conv1 expects x[n,3,2k,2m], c1_w[12,2,2,3] and c1_b[12]")
+        out = np.empty((n, h // 2, w // 2, 12), np.float32)
+        check(_ffi.debug_lib().reid_debug_swin_conv1(self.h, _ptr(x), C.c_int(n), C.c_int(h), C.c_int(w), _ptr(c1_w), _ptr(c1_b), _ptr(out)))
         return out
 
     def debug_maxpool(self, x):

@@ -3,6 +3,10 @@
     extractor = Extractor(model_path, use_cuda=True)
     features  = extractor(im_crops)        # list of HxWx3 uint8 -> np.ndarray float32 [N, 512]
 
+A checkpoint of the reference's other tracker ReID model, swin_transformer (modification_tracking/models/__init__.py:80,
+reid_model_factory.py:9), is recognised from its keys: the same object then resizes to 224x224 (``size=`` overrides; multiples of 224),
+normalises with ImageNet's mean / std (reid/data_transforms.py:64) and returns float32 [N, 96].
+
 What the reference does per call (feature_extractor.py:31-53): a Python loop of cv2.resize + ToTensor + Normalize
 per crop, torch.cat, H2D copy, backbone forward, D2H copy.  Here the crops are packed once, copied once, and the
 resize / normalise / backbone all run as HIP kernels; the return value is a fresh C-contiguous host array.
@@ -20,15 +24,24 @@ from . import precision as _precision
 from . import weights
 
 
+def pack_checkpoint(state_dict):
+    """state_dict -> (arch, blob, manifest, info): arch "swin" for a swin_t checkpoint (v1 or v2: the ShadowFeatureExtraction stem and
+    the stage keys, weights.is_swin_state_dict), packed with weights.pack_swin; "seres18" for everything else, packed with
+    weights.pack_seres18 as before (strict=False semantics, feature_extractor.py:19).  No engine, no device."""
+    if weights.is_swin_state_dict(state_dict):
+        return ("swin",) + tuple(weights.pack_swin(state_dict))
+    return ("seres18",) + tuple(weights.pack_seres18(state_dict))
+
+
 class Extractor(object):
-    def __init__(self, model_path, use_cuda=True, device=0, precision=None):
+    def __init__(self, model_path, use_cuda=True, device=0, precision=None, size=None):
         """``Extractor(model_path, use_cuda=True)`` as feature_extractor.py:15-29.  ``precision`` (keyword, not in the reference):
         "f16x3" (default; $REID_PRECISION overrides the default) / "f32" / "f16" - see precision.py; a checkpoint the fp32-class
-        arithmetic cannot represent runs in exact fp32, with one log line."""
+        arithmetic cannot represent runs in exact fp32, with one log line.  ``size`` (keyword, (W, H) like ``self.size``): the size
+        crops are resized to - a Swin checkpoint takes multiples of 224 (default (224, 224)), the ResNet family (128, 256) only."""
         if not use_cuda:
             raise RuntimeError("Extractor: the MI355X engine has no CPU path (use_cuda=False is not supported)")
         self.device = "cuda"
-        self.size = (128, 256)                 # (W, H), feature_extractor.py:24
         self._mode = _precision.resolve(precision)
         if isinstance(model_path, dict):
             state_dict = model_path            # already-loaded state_dict (tests, benchmarks)
@@ -38,11 +51,19 @@ class Extractor(object):
             # loads two and aborts in the exit handlers - DESIGN.md section 6, the rule parallel.RcclComm.from_env enforces)
             import torch
             state_dict = torch.load(model_path, map_location="cpu")   # {"state_dict": ...} / "module." prefixes: weights.pack_seres18
-        from .engine import get_engine
+        from .engine import Engine, get_engine
         self.net = get_engine(device)
-        blob, manifest, self.info = weights.pack_seres18(state_dict)   # strict=False semantics, :19
+        self._arch, blob, manifest, self.info = pack_checkpoint(state_dict)
+        if self._arch == "swin":
+            self.size = tuple(int(v) for v in (size or (224, 224)))           # (W, H)
+            Engine._swin_crop_args(self.size[::-1], None)
+            self.net._swin_owner = None
+        else:
+            self.size = (128, 256)             # (W, H), feature_extractor.py:24
+            if size is not None and tuple(size) != self.size:
+                raise ValueError("Extractor: the ResNet18-IBN family runs at size (W, H) = (128, 256) only, got %r" % (size,))
+            self.net._owner = None
         self._packed = (blob, manifest)
-        self.net._owner = None
         _precision.run(self, self.net, "Extractor", lambda eng: None)      # load now; a checkpoint mode 2 refuses falls back here
         logger = logging.getLogger("root.tracker")
         logger.info("Loading weights from {}... Done!".format(model_path if not isinstance(model_path, dict) else "<state_dict>"))
@@ -59,12 +80,16 @@ class Extractor(object):
             raise RuntimeError("Extractor: expected a non-empty list of crops")   # torch.cat([]) raises, :44
         return [np.asarray(im) for im in im_crops]
 
-    def _needs_bind(self, eng):
-        return getattr(eng, "_owner", None) is not self        # another model was loaded on this device meanwhile
+    def _needs_bind(self, eng):                                # another model of this family was loaded on this device meanwhile
+        return getattr(eng, "_swin_owner" if self._arch == "swin" else "_owner", None) is not self
 
     def _do_bind(self, eng):
-        eng.load_seres18(*self._packed)
-        eng._owner = self
+        if self._arch == "swin":
+            eng.load_swin(*self._packed)
+            eng._swin_owner = self
+        else:
+            eng.load_seres18(*self._packed)
+            eng._owner = self
 
     def _run(self, fn):
         return _precision.run(self, self.net, "Extractor", fn)
@@ -72,17 +97,24 @@ class Extractor(object):
     def __call__(self, im_crops):
         """feature_extractor.py:48-53: host crops in, host features out (the upload of one pass of crops, its download and the
         kernels of its neighbours overlap inside the library).  A stacked ``uint8[n,256,128,3]`` array - crops already at the
-        extractor's size, for which the reference's cv2.resize is the identity - goes to the fixed-size entry point as it is."""
+        extractor's size, for which the reference's cv2.resize is the identity - goes to the fixed-size entry point as it is (Swin:
+        to the crops entry point in place, without a packing copy).  A Swin checkpoint returns float32 [N, 96]."""
+        size_hw = (self.size[1], self.size[0])
         if isinstance(im_crops, np.ndarray) and im_crops.dtype == np.uint8 and im_crops.ndim == 4 \
-                and im_crops.shape[1:] == (self.size[1], self.size[0], 3) and im_crops.shape[0] > 0:
+                and im_crops.shape[1:] == size_hw + (3,) and im_crops.shape[0] > 0:
+            if self._arch == "swin":
+                stacked = np.ascontiguousarray(im_crops)
+                return self._run(lambda eng: eng.swin_embed_ragged_u8(list(stacked), size=size_hw))
             return self._run(lambda eng: eng.embed_u8(im_crops))
         crops = self._preprocess(im_crops)
+        if self._arch == "swin":
+            return self._run(lambda eng: eng.swin_embed_ragged_u8(crops, size=size_hw))
         return self._run(lambda eng: eng.embed_ragged_u8(crops))
 
     def from_frame(self, bbox_xywh, ori_img):
         """DeepSort._get_features(bbox_xywh, ori_img) ([external] deep_sort.py) in one call: centre-format boxes are
         converted and clipped like DeepSort._xywh_to_xyxy (x1 = max(int(x - w/2), 0), x2 = min(int(x + w/2), W - 1), ...),
-        the frame goes to the device once and the windows are cut and resized there.  Returns float32 [N, 512]
+        the frame goes to the device once and the windows are cut and resized there.  Returns float32 [N, 512] ([N, 96] for Swin)
         (an empty array when there is no box, as the reference's `np.array([])` branch)."""
         ori_img = np.asarray(ori_img)
         boxes = np.asarray(bbox_xywh, dtype=np.float64).reshape(-1, 4)
@@ -92,4 +124,6 @@ class Extractor(object):
         xyxy = np.empty((boxes.shape[0], 4), np.int32)
         for i, (x, y, w, h) in enumerate(boxes):
             xyxy[i] = (max(int(x - w / 2), 0), max(int(y - h / 2), 0), min(int(x + w / 2), width - 1), min(int(y + h / 2), height - 1))
+        if self._arch == "swin":
+            return self._run(lambda eng: eng.swin_embed_frame_u8(ori_img, xyxy, size=(self.size[1], self.size[0])))
         return self._run(lambda eng: eng.embed_frame_u8(ori_img, xyxy))

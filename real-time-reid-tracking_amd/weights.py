@@ -223,6 +223,17 @@ def swin_version(sd):
     return version
 
 
+def is_swin_state_dict(state_dict):
+    """True when the keys are those of a swin_t checkpoint, v1 or v2 (the ShadowFeatureExtraction stem `sfe.` and the `stage1.` .. `stage4.`
+    blocks, swin_transformer.py:339-427) - looked up the way normalize_state_dict would name them ({'state_dict': ...} unwrapped,
+    'module.' stripped), without converting a tensor.  What pack_swin then requires of the dict is pack_swin's business."""
+    if isinstance(state_dict, dict) and "state_dict" in state_dict and not hasattr(state_dict["state_dict"], "shape"):
+        state_dict = state_dict["state_dict"]
+    keys = {k[7:] if k.startswith("module.") else k for k in state_dict}
+    return "sfe.conv1.weight" in keys and any(k.startswith("stage1.layers.") for k in keys) and \
+        "stage4.layers.0.1.attention_block.fn.fn.to_qkv.weight" in keys
+
+
 def swin_v2_bias_table(fc1_w, fc1_b, fc2_w, fc2_b):
     """WindowAttention._relative_positional_encodings (swin_transformer.py:177-189): meta_mlp over the 49 x 49 log-spaced relative
     coordinates -> [heads][49][49] (query, key).  It does not depend on the input, so it is evaluated here, once, in float64, and
