@@ -111,6 +111,42 @@ int reid_debug_window_attn_cos(reid_ctx* ctx, int mode, const float* qkv, int n,
  * copy of out [t][c], 2: out16 = [oh | ol'] [t][2c].  in_place != 0: the launch writes out over its own x. */
 int reid_debug_post_norm(reid_ctx* ctx, int side, const float* x, const float* y, int t, int c, const float* g, const float* b, int in_place,
                          float* out, uint16_t* out16);
+/* The kernels of the Swin v1 forward that are not GEMMs, and its geometric convolutions (csrc/swin.hip; correctness harnesses,
+ * tests/test_gpu_swin_kernels.py), each through the function the forward calls, on host operands.  f16 results are raw f16 bits; every
+ * output the launch leaves alone reads as NaN (0xffff); each call returns the context's fault status.
+ * window_attn: window attention of n maps of h x w tokens (multiples of 7) through launch_window_attn, with the context put into the precision
+ * and switches that reach one kernel for the call: form 0 window_attn_kernel<float> -> out fp32 [tokens][heads 32]; 1 the same kernel's packed
+ * store -> out16 [tokens][2 heads 32] = [oh | ol'] (ol' = f16((o - oh) 2^11)); 2 window_attn_kernel<f16> and 3 window_attn_mfma_f16_kernel ->
+ * out16 [tokens][heads 32], qkv rounded to f16 on the device into rows of the forward's stride (3 heads 32 rounded up to 64, the padding NaN);
+ * 4 window_attn_mfma_split_kernel -> out16 as form 1; 5 window_attn_mfma_f32_kernel -> out.  qkv fp32 [n h w][3 heads 32] (q | k | v,
+ * head-major), pos169 the block's [13][13] relative-position table (expanded to [key 64][query 64] by the function reid_swin_load uses). */
+int reid_debug_window_attn(reid_ctx* ctx, int form, const float* qkv, int n, int h, int w, int heads, int shifted, const float* pos169,
+                           float* out, uint16_t* out16);
+/* layernorm: (x - mean) / sqrt(var + 1e-5) g + b over t rows of c channels (c <= 768, a multiple of 4).  form 0 launch_layernorm<float> ->
+ * out [t][c]; 1 launch_layernorm<f16> -> out16 [t][c]; 2 launch_layernorm_packed -> out16 [t][2c] = [yh | yl']. */
+int reid_debug_layernorm(reid_ctx* ctx, int form, const float* x, int t, int c, const float* g, const float* b, float* out, uint16_t* out16);
+/* ln_linear: LayerNorm 1 + to_qkv of the fp32-class mode in one kernel (csrc/two_linear_f16.hip, launch_ln_linear; the context is in
+ * precision 2 for the call): out [t][n] = LayerNorm(x [t][c]; ln_g, ln_b) . w [n][c]^T + bias (bias may be null).  Drops the tile image
+ * cached for its weight buffer first. */
+int reid_debug_ln_linear(reid_ctx* ctx, const float* x, const float* ln_g, const float* ln_b, const float* w, const float* bias, int t, int c,
+                         int n, float* out);
+/* swin_sfe: ShadowFeatureExtraction after its first convolution (sfe_norm_kernel + sfe_conv2_fc_kernel with the forward's grids).  c1
+ * [n][h1][w1][12]; in_g / in_b [6] InstanceNorm affine of channels 0-5, bn_s / bn_t [6] folded BatchNorm of channels 6-11; c2_w [48][(kh, kw,
+ * c) 48], c2_b [48], fc_w [96][48], fc_b [96] -> ab [n][24] (12 scales, 12 shifts) and tok [n][h1 / 2][w1 / 2][96]. */
+int reid_debug_swin_sfe(reid_ctx* ctx, const float* c1, int n, int h1, int w1, const float* in_g, const float* in_b, const float* bn_s,
+                        const float* bn_t, const float* c2_w, const float* c2_b, const float* fc_w, const float* fc_b, float* ab, float* tok);
+/* swin_tail: LayerNorm(96, eps 1e-6; g, b) per token -> GeM_1D (exponent p; p == 3 takes the cube branch) over ntok tokens -> BatchNorm1d
+ * (swin_tail_partial_kernel + swin_tail_final_kernel with the forward's grids).  x [n][ntok][96] -> gem [n][96], emb = gem bn_s + bn_t. */
+int reid_debug_swin_tail(reid_ctx* ctx, const float* x, int n, int ntok, const float* g, const float* b, float p, const float* bn_s,
+                         const float* bn_t, float* gem, float* emb);
+/* swin_merge / swin_fuse: the geometric convolutions of the trunk on the weights THIS CONTEXT HAS LOADED (reid_swin_load: Unfold-order and
+ * parity repacking, f16 rows, split forms) and in its precision, through the functions the forward calls.  merge: patch merging in front of
+ * `stage` (2 .. 4), x [n][h][w][48 2^(stage - 1)] -> out fp32 [n][h / 2][w / 2][96 2^(stage - 1)].  fuse: the top-down fusion, sfe / x1
+ * [n][h1][w1][96], x2 .. x4 the later stage outputs (half the tokens, twice the channels each) -> a0 = x4 + Conv8x8s8(sfe)
+ * [n][h1 / 8][w1 / 8][768], f3 = x3 + ConvT(a0), f2 = x2 + ConvT(f3) (fp32; precision 1: raw f16 bits) and f1 = x1 + ConvT(f2) fp32. */
+int reid_debug_swin_merge(reid_ctx* ctx, int stage, const float* x, int n, int h, int w, float* out);
+int reid_debug_swin_fuse(reid_ctx* ctx, const float* sfe, const float* x1, const float* x2, const float* x3, const float* x4, int n, int h1,
+                         int w1, void* a0, void* f3, void* f2, float* f1);
 /* Timing experiments on that kernel (WRONG results while set): bit 0 = no weight refills after the first two steps, bit 1 = no block
  * barriers.  0 restores the product behaviour. */
 int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits);

@@ -1061,3 +1061,217 @@ extern "C" int reid_debug_maxpool(reid_ctx* ctx, int f16, const void* x, int n, 
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }
+
+// ------------------------------------------------------------------------------------------------ Swin v1 kernels alone (tests/test_gpu_swin_kernels.py)
+// The kernels of the v1 forward that are not GEMMs, and its geometric convolutions, each through the function the forward calls
+// (reid_internal.h: launch_window_attn, launch_swin_layernorm, launch_ln_linear, launch_sfe_norm_fc, launch_swin_tail, swin_loaded_merge,
+// swin_loaded_fuse), on host operands.  Outputs are set to 0xff bytes first (NaN / 0xffff where a launch leaves them alone); every call
+// returns the context's fault status.
+namespace {
+// a harness that runs a launcher in another precision / with other switches than the context's puts them back on every way out
+struct CtxModes {
+    reid_ctx* ctx;
+    int precision, attn_mfma, attn_split;
+    explicit CtxModes(reid_ctx* c) : ctx(c), precision(c->precision), attn_mfma(c->swin_attn_mfma), attn_split(c->swin_attn_split) {}
+    ~CtxModes() {
+        ctx->precision = precision;
+        ctx->swin_attn_mfma = attn_mfma;
+        ctx->swin_attn_split = attn_split;
+    }
+};
+}  // namespace
+
+// launch_window_attn in the precision and switches that reach kernel `form`: 0 window_attn_kernel<float> -> out fp32 [T][C]; 1 the same
+// with the packed store -> out16 [T][2C]; 2 window_attn_kernel<f16> and 3 window_attn_mfma_f16_kernel -> out16 [T][C] (qkv rounded to f16 on
+// the device into rows of swin_attn_ldq f16, the padding columns NaN); 4 window_attn_mfma_split_kernel -> out16 [T][2C];
+// 5 window_attn_mfma_f32_kernel -> out.  qkv fp32 [n h w][3 heads 32], pos169 the block's [13][13] table.
+extern "C" int reid_debug_window_attn(reid_ctx* ctx, int form, const float* qkv, int n, int h, int w, int heads, int shifted,
+                                      const float* pos169, float* out, uint16_t* out16) {
+    ARG_CHECK(ctx && form >= 0 && form <= 5 && qkv && pos169 && n >= 1 && heads >= 1 && heads <= 64 && h >= 7 && w >= 7 && h % 7 == 0 &&
+              w % 7 == 0);
+    ARG_CHECK(form == 0 || form == 5 ? out != nullptr : out16 != nullptr);
+    CTX_ENTER(ctx);
+    CtxModes keep(ctx);
+    static const int prec[6] = {0, 2, 1, 1, 2, 0}, mfma[6] = {1, 1, 0, 1, 1, 2}, split[6] = {0, 0, 0, 0, 1, 0};
+    ctx->precision = prec[form];
+    ctx->swin_attn_mfma = mfma[form];
+    ctx->swin_attn_split = split[form];
+    const int C = heads * 32, ldq = swin_attn_ldq(ctx, C);
+    const size_t T = (size_t)n * h * w;
+    std::vector<float> tab(4096);
+    swin_bias_table(pos169, tab.data());
+    float *dq, *dpos, *dtab, *dout = nullptr;
+    _Float16 *dq16 = nullptr, *dq16c = nullptr, *dout16 = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgsw.qkv", qkv, T * 3 * C, &dq));
+    REID_TRY(dbg_upload(ctx, "dbgsw.pos", pos169, (size_t)169, &dpos));
+    REID_TRY(dbg_upload(ctx, "dbgsw.tab", tab.data(), tab.size(), &dtab));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));            // tab is a local
+    const void* src = dq;
+    if (ctx->precision == 1) {
+        REID_TRY(ctx_ws(ctx, "dbgsw.q16c", T * 3 * C * 2, (void**)&dq16c));
+        REID_TRY(dbg_output(ctx, "dbgsw.q16", T * ldq, &dq16));
+        REID_TRY(launch_f32_to_f16(ctx, dq, T * 3 * C, dq16c));
+        HIP_TRY(hipMemcpy2DAsync(dq16, (size_t)ldq * 2, dq16c, (size_t)3 * C * 2, (size_t)3 * C * 2, T, hipMemcpyDeviceToDevice, ctx->stream));
+        src = dq16;
+    }
+    void* dst;
+    const size_t nout16 = T * C * (ctx->precision == 2 ? 2 : 1);
+    if (ctx->precision == 0) {
+        REID_TRY(dbg_output(ctx, "dbgsw.out", T * C, &dout));
+        dst = dout;
+    } else {
+        REID_TRY(dbg_output(ctx, "dbgsw.o16", nout16, &dout16));
+        dst = dout16;
+    }
+    REID_TRY(launch_window_attn(ctx, src, n, h, w, heads, shifted, dpos, dtab, dst));
+    if (dout) REID_TRY(dbg_download(ctx, out, dout, T * C));
+    else REID_TRY(dbg_download(ctx, (_Float16*)out16, dout16, nout16));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// launch_layernorm<float> (form 0 -> out [t][c]), launch_layernorm<f16> (1 -> out16 [t][c]), launch_layernorm_packed (2 -> out16 [t][2c])
+extern "C" int reid_debug_layernorm(reid_ctx* ctx, int form, const float* x, int t, int c, const float* g, const float* b, float* out,
+                                    uint16_t* out16) {
+    ARG_CHECK(ctx && form >= 0 && form <= 2 && x && g && b && t >= 1 && c >= 4 && c <= 768 && c % 4 == 0 && (form == 0 ? out != nullptr : out16 != nullptr));
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)t * c, nout16 = nx * (form == 2 ? 2 : 1);
+    float *dx, *dg, *db, *dout = nullptr;
+    _Float16* dout16 = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgsw.x", x, nx, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgsw.g", g, (size_t)c, &dg));
+    REID_TRY(dbg_upload(ctx, "dbgsw.b", b, (size_t)c, &db));
+    if (form == 0) REID_TRY(dbg_output(ctx, "dbgsw.out", nx, &dout));
+    else REID_TRY(dbg_output(ctx, "dbgsw.o16", nout16, &dout16));
+    REID_TRY(launch_swin_layernorm(ctx, form, dx, t, c, dg, db, form == 0 ? (void*)dout : (void*)dout16));
+    if (dout) REID_TRY(dbg_download(ctx, out, dout, nx));
+    else REID_TRY(dbg_download(ctx, (_Float16*)out16, dout16, nout16));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// launch_ln_linear with the context in precision 2: out [t][n] = LayerNorm(x [t][c]; ln_g, ln_b) . w [n][c]^T (+ bias, may be null)
+extern "C" int reid_debug_ln_linear(reid_ctx* ctx, const float* x, const float* ln_g, const float* ln_b, const float* w, const float* bias, int t,
+                                    int c, int n, float* out) {
+    ARG_CHECK(ctx && x && ln_g && ln_b && w && out && t >= 1 && c >= 4 && n >= 1);
+    CTX_ENTER(ctx);
+    CtxModes keep(ctx);
+    ctx->precision = 2;
+    ARG_CHECK(ln_linear_supported(ctx, t, c, n));
+    float *dx, *dg, *db, *dw, *dbias, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgsw.x", x, (size_t)t * c, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgsw.g", ln_g, (size_t)c, &dg));
+    REID_TRY(dbg_upload(ctx, "dbgsw.b", ln_b, (size_t)c, &db));
+    REID_TRY(dbg_upload(ctx, "dbgsw.w", w, (size_t)n * c, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgsw.bias", bias, (size_t)n, &dbias));
+    REID_TRY(dbg_output(ctx, "dbgsw.out", (size_t)t * n, &dout));
+    // the tiled weight image is cached by blob address: this harness re-uses its buffer, so drop what an earlier call left
+    auto it = ctx->split_w.find((const void*)((const char*)dw + 1));
+    if (it != ctx->split_w.end()) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        (void)hipFree(it->second);
+        ctx->split_w.erase(it);
+    }
+    REID_TRY(launch_ln_linear(ctx, dx, dg, db, t, c, n, dw, dbias, dout, n));
+    REID_TRY(dbg_download(ctx, out, dout, (size_t)t * n));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// launch_sfe_norm_fc: sfe_norm_kernel + sfe_conv2_fc_kernel with the forward's grids.  c1 [n][h1][w1][12] -> ab [n][24] (12 scales, 12
+// shifts) and tok [n][h1 / 2][w1 / 2][96]
+extern "C" int reid_debug_swin_sfe(reid_ctx* ctx, const float* c1, int n, int h1, int w1, const float* in_g, const float* in_b, const float* bn_s,
+                                   const float* bn_t, const float* c2_w, const float* c2_b, const float* fc_w, const float* fc_b, float* ab,
+                                   float* tok) {
+    ARG_CHECK(ctx && c1 && n >= 1 && h1 >= 2 && w1 >= 2 && h1 % 2 == 0 && w1 % 2 == 0 && in_g && in_b && bn_s && bn_t && c2_w && c2_b && fc_w && fc_b &&
+              ab && tok);
+    CTX_ENTER(ctx);
+    const size_t ntok = (size_t)n * (h1 / 2) * (w1 / 2) * 96;
+    float *dc1, *dig, *dib, *dbs, *dbt, *dw2, *db2, *dwf, *dbf, *dab, *dtok;
+    REID_TRY(dbg_upload(ctx, "dbgsw.x", c1, (size_t)n * h1 * w1 * 12, &dc1));
+    REID_TRY(dbg_upload(ctx, "dbgsw.ing", in_g, (size_t)6, &dig));
+    REID_TRY(dbg_upload(ctx, "dbgsw.inb", in_b, (size_t)6, &dib));
+    REID_TRY(dbg_upload(ctx, "dbgsw.bns", bn_s, (size_t)6, &dbs));
+    REID_TRY(dbg_upload(ctx, "dbgsw.bnt", bn_t, (size_t)6, &dbt));
+    REID_TRY(dbg_upload(ctx, "dbgsw.c2w", c2_w, (size_t)48 * 48, &dw2));
+    REID_TRY(dbg_upload(ctx, "dbgsw.c2b", c2_b, (size_t)48, &db2));
+    REID_TRY(dbg_upload(ctx, "dbgsw.fcw", fc_w, (size_t)96 * 48, &dwf));
+    REID_TRY(dbg_upload(ctx, "dbgsw.fcb", fc_b, (size_t)96, &dbf));
+    REID_TRY(dbg_output(ctx, "dbgsw.ab", (size_t)n * 24, &dab));
+    REID_TRY(dbg_output(ctx, "dbgsw.out", ntok, &dtok));
+    REID_TRY(launch_sfe_norm_fc(ctx, dc1, n, h1, w1, dig, dib, dbs, dbt, dw2, db2, dwf, dbf, dab, dtok));
+    REID_TRY(dbg_download(ctx, ab, dab, (size_t)n * 24));
+    REID_TRY(dbg_download(ctx, tok, dtok, ntok));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// launch_swin_tail: swin_tail_partial_kernel + swin_tail_final_kernel with the forward's grids.  x [n][ntok][96], g / b the tail LayerNorm's,
+// p the GeM exponent, bn_s / bn_t [96] -> gem [n][96], emb [n][96]
+extern "C" int reid_debug_swin_tail(reid_ctx* ctx, const float* x, int n, int ntok, const float* g, const float* b, float p, const float* bn_s,
+                                    const float* bn_t, float* gem, float* emb) {
+    ARG_CHECK(ctx && x && n >= 1 && ntok >= 1 && g && b && bn_s && bn_t && gem && emb);
+    CTX_ENTER(ctx);
+    float *dx, *dg, *db, *dp, *dbs, *dbt, *dgem, *demb;
+    REID_TRY(dbg_upload(ctx, "dbgsw.x", x, (size_t)n * ntok * 96, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgsw.g", g, (size_t)96, &dg));
+    REID_TRY(dbg_upload(ctx, "dbgsw.b", b, (size_t)96, &db));
+    REID_TRY(dbg_upload(ctx, "dbgsw.p", &p, (size_t)1, &dp));
+    REID_TRY(dbg_upload(ctx, "dbgsw.bns", bn_s, (size_t)96, &dbs));
+    REID_TRY(dbg_upload(ctx, "dbgsw.bnt", bn_t, (size_t)96, &dbt));
+    REID_TRY(dbg_output(ctx, "dbgsw.ab", (size_t)n * 96, &dgem));
+    REID_TRY(dbg_output(ctx, "dbgsw.out", (size_t)n * 96, &demb));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));            // p is an argument
+    REID_TRY(launch_swin_tail(ctx, dx, n, ntok, dg, db, dp, dbs, dbt, dgem, demb));
+    REID_TRY(dbg_download(ctx, gem, dgem, (size_t)n * 96));
+    REID_TRY(dbg_download(ctx, emb, demb, (size_t)n * 96));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// Patch merging in front of `stage` (2 .. 4) on the weights this context has loaded, in its precision: x [n][h][w][48 2^(stage - 1)] ->
+// out fp32 [n][h / 2][w / 2][96 2^(stage - 1)]
+extern "C" int reid_debug_swin_merge(reid_ctx* ctx, int stage, const float* x, int n, int h, int w, float* out) {
+    ARG_CHECK(ctx && stage >= 2 && stage <= 4 && x && out && n >= 1 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0);
+    CTX_ENTER(ctx);
+    const size_t cin = (size_t)48 << (stage - 1), nin = (size_t)n * h * w * cin, nout = (size_t)n * (h / 2) * (w / 2) * cin * 2;
+    float *dx, *dout;
+    _Float16* dscr;
+    REID_TRY(dbg_upload(ctx, "dbgsw.x", x, nin, &dx));
+    REID_TRY(dbg_output(ctx, "dbgsw.o16", nin, &dscr));
+    REID_TRY(dbg_output(ctx, "dbgsw.out", nout, &dout));
+    REID_TRY(swin_loaded_merge(ctx, stage, dx, n, h, w, (float*)dscr, dout));
+    REID_TRY(dbg_download(ctx, out, dout, nout));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// The top-down fusion on the weights this context has loaded, in its precision: sfe / x1 [n][h1][w1][96], x2 [n][h1/2][w1/2][192], x3
+// [..][384], x4 [n][h1/8][w1/8][768] -> a0 = x4 + Conv8x8s8(sfe) [..][768], f3 [..][384], f2 [..][192] (fp32; precision 1: raw f16 bits) and
+// f1 [n][h1][w1][96] fp32
+extern "C" int reid_debug_swin_fuse(reid_ctx* ctx, const float* sfe, const float* x1, const float* x2, const float* x3, const float* x4, int n,
+                                    int h1, int w1, void* a0, void* f3, void* f2, float* f1) {
+    ARG_CHECK(ctx && sfe && x1 && x2 && x3 && x4 && n >= 1 && h1 >= 8 && w1 >= 8 && h1 % 8 == 0 && w1 % 8 == 0 && a0 && f3 && f2 && f1);
+    CTX_ENTER(ctx);
+    const size_t n1 = (size_t)n * h1 * w1 * 96;   // elements of stage 1; each later stage holds half as many
+    const size_t esz = ctx->precision == 1 ? 2 : 4;
+    float *dsfe, *dxs[4], *da0, *df3, *df2, *df1;
+    _Float16* dscr;
+    REID_TRY(dbg_upload(ctx, "dbgsw.x", sfe, n1, &dsfe));
+    REID_TRY(dbg_upload(ctx, "dbgsw.x1", x1, n1, &dxs[0]));
+    REID_TRY(dbg_upload(ctx, "dbgsw.x2", x2, n1 / 2, &dxs[1]));
+    REID_TRY(dbg_upload(ctx, "dbgsw.x3", x3, n1 / 4, &dxs[2]));
+    REID_TRY(dbg_upload(ctx, "dbgsw.x4", x4, n1 / 8, &dxs[3]));
+    REID_TRY(dbg_output(ctx, "dbgsw.o16", n1, &dscr));
+    REID_TRY(dbg_output(ctx, "dbgsw.a0", n1 / 8, &da0));
+    REID_TRY(dbg_output(ctx, "dbgsw.f3", n1 / 4, &df3));
+    REID_TRY(dbg_output(ctx, "dbgsw.f2", n1 / 2, &df2));
+    REID_TRY(dbg_output(ctx, "dbgsw.out", n1, &df1));
+    REID_TRY(swin_loaded_fuse(ctx, dsfe, dxs, n, h1, w1, (float*)dscr, da0, df3, df2, df1));
+    HIP_TRY(hipMemcpyAsync(a0, da0, n1 / 8 * esz, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(f3, df3, n1 / 4 * esz, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(f2, df2, n1 / 2 * esz, hipMemcpyDeviceToHost, ctx->stream));
+    REID_TRY(dbg_download(ctx, f1, df1, n1));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}

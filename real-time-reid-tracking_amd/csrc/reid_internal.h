@@ -214,6 +214,20 @@ int launch_window_attn_cos(reid_ctx* ctx, int mode, const void* qkv, int ldq, in
                            const float* bias_t, const float* scale, void* out);
 int launch_post_norm(reid_ctx* ctx, int side_mode, const float* x, const float* y, long long T, int C, const float* g, const float* b,
                      float* out, _Float16* side);
+// swin.hip: the v1 kernels through the functions the forward calls (argument layouts at their definitions); the harnesses of
+// include/reid_hip_debug.h call the same ones
+void swin_bias_table(const float* pos169, float* tab4096);   // host: pos [13][13] -> [key 64][query 64], -inf on padded keys
+int swin_attn_ldq(const reid_ctx* ctx, int C);
+int launch_window_attn(reid_ctx* ctx, const void* qkv, int n, int Hs, int Ws, int heads, int shifted, const float* pos, const float* bias_tab,
+                       void* out);
+int launch_swin_layernorm(reid_ctx* ctx, int form, const float* x, long long T, int C, const float* g, const float* b, void* out);
+int launch_sfe_norm_fc(reid_ctx* ctx, const float* c1, int n, int h1, int w1, const float* in_g, const float* in_b, const float* bn_s,
+                       const float* bn_t, const float* c2_w, const float* c2_b, const float* fc_w, const float* fc_b, float* ab, float* tok);
+int launch_swin_tail(reid_ctx* ctx, const float* x, int n, int ntok, const float* g, const float* b, const float* p, const float* bn_s,
+                     const float* bn_t, float* gem, float* emb);
+int swin_loaded_merge(reid_ctx* ctx, int stage, const float* x, int n, int h, int w, float* scratch, float* out);
+int swin_loaded_fuse(reid_ctx* ctx, const float* sfe, float* const* xs, int n, int h1, int w1, float* scratch16, float* a0, float* f3, float* f2,
+                     float* f1);
 // swin.hip: the two stems of the Swin forward, each writing c1 [n][h / 2][w / 2][12] - sfe_conv1_kernel from normalised NCHW images, and
 // swin_crop_front_kernel (libreid_hip_swin_crops.so, swin_crops.h) from uint8 windows; mean_std6 is a host pointer
 int launch_sfe_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* c1);

@@ -893,8 +893,10 @@ __global__ __launch_bounds__(256) void swin_tail_partial_kernel(const float* __r
         const float mean = wsum(v0 + v1) / 96.f;
         const float d0 = v0 - mean, d1 = lane < 32 ? v1 - mean : 0.f;
         const float rstd = 1.0f / sqrtf(wsum(d0 * d0 + d1 * d1) / 96.f + 1e-6f);
-        a0 += pw(fmaxf(d0 * rstd * g0 + b0, 1e-6f));
-        if (lane < 32) a1 += pw(fmaxf(d1 * rstd * g1 + b1, 1e-6f));
+        // clamp(min = 1e-6) as torch's: a NaN stays a NaN (fmaxf returns the other operand, and a non-finite token left as 1e-6)
+        const float y0 = d0 * rstd * g0 + b0, y1 = d1 * rstd * g1 + b1;
+        a0 += pw(y0 < 1e-6f ? 1e-6f : y0);
+        if (lane < 32) a1 += pw(y1 < 1e-6f ? 1e-6f : y1);
     };
     int t = t0 + wave;
     for (; t + 12 < t1; t += 16) {      // four tokens per wave and trip: their loads are in flight together
@@ -1121,6 +1123,93 @@ int conv_transpose_parities(reid_ctx* ctx, const float* x, int n, int Hi, int Wi
 const int kDims[4] = {96, 192, 384, 768}, kLayers[4] = {2, 2, 6, 2}, kHeads[4] = {3, 6, 12, 24};
 
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------ launchers shared with the harnesses
+// (reid_internal.h; include/reid_hip_debug.h: each harness of tests/test_gpu_swin_kernels.py goes through the function the forward calls)
+
+// The relative-position bias of one block (pos [13][13]) expanded to the [key 64][query 64] table of the MFMA attention kernels: -inf on
+// the padded keys, 0 on the padded queries (same entries as build_bias_table).  Host side: reid_swin_load makes one per block.
+void swin_bias_table(const float* pos169, float* tab4096) {
+    for (int key = 0; key < 64; ++key)
+        for (int query = 0; query < 64; ++query) {
+            float b = 0.f;
+            if (key >= 49) b = -INFINITY;
+            else if (query < 49) b = pos169[(key / 7 - query / 7 + 6) * 13 + (key % 7 - query % 7 + 6)];
+            tab4096[key * 64 + query] = b;
+        }
+}
+
+// Row stride of the qkv buffer the attention kernel of this context's precision reads: the f16 GEMM writes rows padded to its 64-wide tile
+int swin_attn_ldq(const reid_ctx* ctx, int C) { return ctx->precision == 1 ? (3 * C + 63) / 64 * 64 : 3 * C; }
+
+// WindowAttention v1 of one block: the context's precision and switches pick the kernel, its grid and which form of the bias it reads.
+//   precision 1: qkv f16 [T][ldq] -> out f16 [T][C]; matrix-core kernel (bias_tab) unless swin_attn_mfma == 0 (VALU kernel, pos)
+//   precision 2: qkv fp32 [T][3C] -> out f16 [T][2C] = [oh | ol']; VALU kernel (pos) unless swin_attn_split (matrix cores, bias_tab)
+//   precision 0: qkv fp32 [T][3C] -> out fp32 [T][C]; VALU kernel unless swin_attn_mfma == 2 (v_mfma_f32_32x32x2_f32), both read pos
+int launch_window_attn(reid_ctx* ctx, const void* qkv, int n, int Hs, int Ws, int heads, int shifted, const float* pos, const float* bias_tab,
+                       void* out) {
+    const int C = heads * 32, ldq = swin_attn_ldq(ctx, C);
+    const long long T = (long long)n * Hs * Ws, ntask = (long long)n * (Hs / 7) * (Ws / 7) * heads;
+    const dim3 grid4((unsigned)((ntask + 3) / 4));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T * C * (ctx->precision == 1 ? 8 : 16));
+    if (ctx->precision == 1) {
+        if (ctx->swin_attn_mfma)
+            hipLaunchKernelGGL(window_attn_mfma_f16_kernel, grid4, dim3(256), 0, ctx->stream, (const f16*)qkv, ldq, n, Hs, Ws, heads, shifted,
+                               bias_tab, (f16*)out);
+        else
+            hipLaunchKernelGGL(window_attn_kernel<f16>, grid4, dim3(256), 0, ctx->stream, (const f16*)qkv, ldq, n, Hs, Ws, heads, shifted, pos,
+                               (f16*)out);
+    } else if (ctx->precision == 2) {
+        if (ctx->swin_attn_split)
+            hipLaunchKernelGGL(window_attn_mfma_split_kernel, grid4, dim3(256), 0, ctx->stream, (const float*)qkv, ldq, n, Hs, Ws, heads, shifted,
+                               bias_tab, (f16*)out, ctx->fault);
+        else
+            hipLaunchKernelGGL(window_attn_kernel<float>, grid4, dim3(256), 0, ctx->stream, (const float*)qkv, ldq, n, Hs, Ws, heads, shifted,
+                               pos, (float*)nullptr, (f16*)out, ctx->fault);
+    } else if (ctx->swin_attn_mfma == 2) {   // fp32 MFMA runs at the fp32 VALU rate: measured 5 % slower than the VALU kernel, kept for A/B
+        hipLaunchKernelGGL(window_attn_mfma_f32_kernel, dim3((unsigned)((ntask + 1) / 2)), dim3(128), 0, ctx->stream, (const float*)qkv, ldq, n,
+                           Hs, Ws, heads, shifted, pos, (float*)out);
+    } else {
+        hipLaunchKernelGGL(window_attn_kernel<float>, grid4, dim3(256), 0, ctx->stream, (const float*)qkv, ldq, n, Hs, Ws, heads, shifted, pos,
+                           (float*)out);
+    }
+    prof_end(ctx);
+    LAUNCH_CHECK();
+    return REID_OK;
+}
+
+// LayerNorm (eps 1e-5) of T rows of C channels through the forward's three launchers: form 0 fp32 out, 1 f16 out, 2 [yh | yl'] f16 [T][2C]
+int launch_swin_layernorm(reid_ctx* ctx, int form, const float* x, long long T, int C, const float* g, const float* b, void* out) {
+    if (form == 0) launch_layernorm<float>(ctx, x, T, C, g, b, (float*)out);
+    else if (form == 1) launch_layernorm<f16>(ctx, x, T, C, g, b, (f16*)out);
+    else launch_layernorm_packed(ctx, x, T, C, g, b, (f16*)out);
+    LAUNCH_CHECK();
+    return REID_OK;
+}
+
+// ShadowFeatureExtraction after its first convolution: MixedNorm statistics of c1 [n][h1][w1][12] -> ab [n][24], then MixedNorm + ReLU ->
+// conv2x2 s2 -> ReLU -> Linear -> tok [n][h1 / 2][w1 / 2][96].  No profiling bracket of its own: the forward runs it inside the stem's.
+int launch_sfe_norm_fc(reid_ctx* ctx, const float* c1, int n, int h1, int w1, const float* in_g, const float* in_b, const float* bn_s,
+                       const float* bn_t, const float* c2_w, const float* c2_b, const float* fc_w, const float* fc_b, float* ab, float* tok) {
+    hipLaunchKernelGGL(sfe_norm_kernel, dim3(n), dim3(256), 0, ctx->stream, c1, h1 * w1, in_g, in_b, bn_s, bn_t, ab);
+    hipLaunchKernelGGL(sfe_conv2_fc_kernel, dim3(grid_for((long long)n * (h1 / 2) * (w1 / 2), 256)), dim3(256), 0, ctx->stream, c1, ab, n, h1,
+                       w1, c2_w, c2_b, fc_w, fc_b, tok);
+    LAUNCH_CHECK();
+    return REID_OK;
+}
+
+// The tail: LayerNorm(96, eps 1e-6) -> GeM_1D over ntok tokens -> BatchNorm1d, x [n][ntok][96] -> gem [n][96] (may be null), emb [n][96].
+// No profiling bracket of its own.
+int launch_swin_tail(reid_ctx* ctx, const float* x, int n, int ntok, const float* g, const float* b, const float* p, const float* bn_s,
+                     const float* bn_t, float* gem, float* emb) {
+    float* tail_part;
+    REID_TRY(ctx_ws(ctx, "swin.tailp", (size_t)n * TAIL_SLICES * 96 * 4, (void**)&tail_part));
+    hipLaunchKernelGGL(swin_tail_partial_kernel, dim3(n, TAIL_SLICES), dim3(256), 0, ctx->stream, x, ntok, g, b, p, tail_part);
+    hipLaunchKernelGGL(swin_tail_final_kernel, dim3((n * 96 + 255) / 256), dim3(256), 0, ctx->stream, tail_part, n, ntok, p, bn_s, bn_t, gem,
+                       emb, ctx->fault);
+    LAUNCH_CHECK();
+    return REID_OK;
+}
 
 // libreid_hip_swin_v2.so, opened from the directory this library lies in when the first v2 checkpoint is loaded (or a v2 harness runs):
 // a process that never loads v2 weights never opens it.  Missing library or symbol: REID_ERR_STATE naming the file - no other path runs v2.
@@ -1440,13 +1529,7 @@ extern "C" int reid_swin_load(reid_ctx* ctx, const float* blob, size_t n_floats,
             for (int s = 0; s < 4; ++s)
                 for (int j = 0; j < kLayers[s]; ++j, ++bt) {
                     const float* pos = blob + tab["s" + std::to_string(s + 1) + ".b" + std::to_string(j) + ".pos"].first;
-                    for (int key = 0; key < 64; ++key)
-                        for (int query = 0; query < 64; ++query) {
-                            float b = 0.f;
-                            if (key >= 49) b = -INFINITY;
-                            else if (query < 49) b = pos[(key / 7 - query / 7 + 6) * 13 + (key % 7 - query % 7 + 6)];
-                            tabs[(size_t)bt * 4096 + key * 64 + query] = b;
-                        }
+                    swin_bias_table(pos, tabs.data() + (size_t)bt * 4096);
                 }
             HIP_TRY(hipMalloc((void**)&w.bias_tabs, tabs.size() * sizeof(float)));
             HIP_TRY(hipMemcpy(w.bias_tabs, tabs.data(), tabs.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1683,6 +1766,81 @@ static int swin_forward_crops(reid_ctx* ctx, const SwinWeights& w, const uint8_t
     return swin_body(ctx, w, nullptr, c1, n, h, wd, d_emb, d_logits);
 }
 
+// PatchMerging in front of stage s + 1 (s = 1 .. 3) = conv2x2 s2 with weights repacked to (kh, kw, c) order + bias
+// (swin_transformer.py:263-275): prev [n][Hs][Ws][kDims[s - 1]] -> xcur [n][Hs / 2][Ws / 2][kDims[s]], both fp32 (the residual stream);
+// scratch: room for an f16 copy of prev (precision 1)
+static int swin_merge(reid_ctx* ctx, const SwinWeights& w, int s, const float* prev, int n, int Hs, int Ws, float* scratch, float* xcur) {
+    const int C = kDims[s];
+    if (ctx->precision == 1) {
+        f16* x16 = (f16*)scratch;   // f16 copy of the previous stage's output (the residual stream itself stays fp32)
+        REID_TRY(launch_f32_to_f16(ctx, prev, (size_t)n * Hs * Ws * kDims[s - 1], x16));
+        return conv16(ctx, w.zero_page, x16, n, Hs, Ws, kDims[s - 1], w.merge16[s], w.merge_b[s], C, 2, 2, 2, 0, 0, Hs / 2, Ws / 2, nullptr, nullptr,
+                      xcur);
+    }
+    return conv_bias(ctx, prev, n, Hs, Ws, kDims[s - 1], w.merge_w[s], w.merge_b[s], C, 2, 2, 2, 0, 0, Hs / 2, Ws / 2, nullptr, xcur, 0, 0, 0, 0,
+                     w.zero_page);
+}
+
+// top-down fusion (:405-412): a0 = stage4 + Conv8x8s8(sfe); then three ConvTranspose2d(4, 2, 1) + stage outputs -> f3, f2, f1.
+// sfe [n][H1][W1][96] and the stage outputs xs[0 .. 3] fp32; a0 [n][H1/8][W1/8][768], f3 [..][384], f2 [..][192] fp32 - precision 1: f16 maps
+// in the same buffers, every step adding its fp32 stage output in the epilogue - and f1 [n][H1][W1][96] fp32 in every mode.
+// scratch16: room for an f16 copy of sfe (precision 1)
+static int swin_fuse(reid_ctx* ctx, const SwinWeights& w, const float* sfe, float* const* xs, int n, int H1, int W1, float* scratch16, float* a0,
+                     float* f3, float* f2, float* f1) {
+    const int H4 = H1 / 8, W4 = W1 / 8;
+    if (ctx->precision == 1) {
+        f16* sfe16 = (f16*)scratch16;
+        f16* maps16[3] = {(f16*)a0, (f16*)f3, (f16*)f2};   // [n,7,7,768] -> [n,14,14,384] -> [n,28,28,192]
+        REID_TRY(launch_f32_to_f16(ctx, sfe, (size_t)n * H1 * W1 * 96, sfe16));
+        REID_TRY(conv16(ctx, w.zero_page, sfe16, n, H1, W1, 96, w.img16, w.img_b, 768, 8, 8, 8, 0, 0, H4, W4, xs[3], maps16[0], nullptr));
+        int Hi = H4, Wi = W4;
+        for (int t = 0; t < 3; ++t) {
+            const int ci = kDims[3 - t], co = kDims[2 - t];
+            const size_t wstride = (size_t)((co + 63) / 64 * 64) * 4 * ci;
+            // the four output parities of the ConvTranspose2d(4, 2, 1) as ONE launch (4 x the tile grid): a parity alone is 147-784
+            // blocks, too few for 256 CUs
+            REID_TRY(conv16(ctx, w.zero_page, maps16[t], n, Hi, Wi, ci, w.t16[t], w.t_b[t], co, 2, 2, 1, 1, 1, Hi, Wi, xs[2 - t],
+                            t < 2 ? maps16[t + 1] : nullptr, t < 2 ? nullptr : f1, Hi, Wi, 0, 0, (long long)wstride));
+            Hi *= 2;
+            Wi *= 2;
+        }
+        return REID_OK;
+    }
+    REID_TRY(conv_bias(ctx, sfe, n, H1, W1, 96, w.img_w, w.img_b, 768, 8, 8, 8, 0, 0, H4, W4, xs[3], a0, 0, 0, 0, 0, w.zero_page));
+    const float* fin = a0;
+    float* fouts[3] = {f3, f2, f1};
+    int Hi = H4, Wi = W4;
+    for (int t = 0; t < 3; ++t) {
+        const int ci = kDims[3 - t], co = kDims[2 - t];
+        REID_TRY(conv_transpose_parities(ctx, fin, n, Hi, Wi, ci, w.t_w[t], w.t_b[t], co, xs[2 - t], fouts[t], w.zero_page));
+        fin = fouts[t];
+        Hi *= 2;
+        Wi *= 2;
+    }
+    return REID_OK;
+}
+
+// The two steps above on the weights this context has loaded (reid_swin_load) and in its precision, on device operands: what
+// reid_debug_swin_merge / reid_debug_swin_fuse (libreid_hip_debug.so) run.  stage 2 .. 4: x [n][h][w][kDims[stage - 2]] -> out
+// [n][h / 2][w / 2][kDims[stage - 1]]; v1 and v2 checkpoints alike.
+int swin_loaded_merge(reid_ctx* ctx, int stage, const float* x, int n, int h, int w, float* scratch, float* out) {
+    const SwinWeights* sw = swin_find(ctx);
+    if (!sw || !sw->loaded || stage < 2 || stage > 4 || !x || !scratch || !out || n < 1 || h < 2 || w < 2 || (h & 1) || (w & 1)) {
+        reid_set_error("swin_loaded_merge: needs loaded Swin weights, stage 2 .. 4 and an even map (stage %d, %d x %d)", stage, h, w);
+        return sw && sw->loaded ? REID_ERR_ARG : REID_ERR_STATE;
+    }
+    return swin_merge(ctx, *sw, stage - 1, x, n, h, w, scratch, out);
+}
+int swin_loaded_fuse(reid_ctx* ctx, const float* sfe, float* const* xs, int n, int h1, int w1, float* scratch16, float* a0, float* f3, float* f2,
+                     float* f1) {
+    const SwinWeights* sw = swin_find(ctx);
+    if (!sw || !sw->loaded || !sfe || !xs || !scratch16 || !a0 || !f3 || !f2 || !f1 || n < 1 || h1 < 8 || w1 < 8 || h1 % 8 || w1 % 8) {
+        reid_set_error("swin_loaded_fuse: needs loaded Swin weights and a stage-1 map whose sides are multiples of 8 (%d x %d)", h1, w1);
+        return sw && sw->loaded ? REID_ERR_ARG : REID_ERR_STATE;
+    }
+    return swin_fuse(ctx, *sw, sfe, xs, n, h1, w1, scratch16, a0, f3, f2, f1);
+}
+
 // The common body: from c1 [n][h / 2][w / 2][12] to the embeddings.  x != nullptr (the float entries): c1 is still to be written, by the
 // stem from NCHW - sfe_conv1_kernel's launch, first in the stem's one profiling bracket, where it has always been.  x == nullptr (the
 // crops entries): the fused stem has filled c1 on this stream.  The side index (reid_ctx_set_side_index) is taken here, so it serves every
@@ -1712,11 +1870,9 @@ static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float*
     if (x)
         hipLaunchKernelGGL(sfe_conv1_kernel, dim3(grid_for((long long)n * (h / 2) * (wd / 2), 256)), dim3(256), 0, ctx->stream, x, n, h,
                            wd, w.c1_w, w.c1_b, c1);
-    hipLaunchKernelGGL(sfe_norm_kernel, dim3(n), dim3(256), 0, ctx->stream, c1, (h / 2) * (wd / 2), w.in_g, w.in_b, w.bn_s, w.bn_t, ab);
-    hipLaunchKernelGGL(sfe_conv2_fc_kernel, dim3(grid_for(T1, 256)), dim3(256), 0, ctx->stream, c1, ab, n, h / 2, wd / 2, w.c2_w,
-                       w.c2_b, w.fc_w, w.fc_b, sfe);
+    const int stem_rc = launch_sfe_norm_fc(ctx, c1, n, h / 2, wd / 2, w.in_g, w.in_b, w.bn_s, w.bn_t, w.c2_w, w.c2_b, w.fc_w, w.fc_b, ab, sfe);
     prof_end(ctx);
-    LAUNCH_CHECK();
+    REID_TRY(stem_rc);
     {   // SwinTransformer.forward(img, view_index): + side_info_coeff * side_info_embedding[view] on the SFE output (:301-302)
         const int32_t* d_view;
         REID_TRY(ctx_take_side(ctx, n, w.views, "reid_swin_embed (view index)", &d_view));
@@ -1734,16 +1890,7 @@ static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float*
             return REID_OK;
         }
         if (s > 0) {
-            // PatchMerging = conv2x2 s2 with weights repacked to (kh, kw, c) order + bias (swin_transformer.py:263-275)
-            if (ctx->precision == 1) {
-                f16* x16 = (f16*)lnb;   // f16 copy of the previous stage's output (the residual stream itself stays fp32)
-                REID_TRY(launch_f32_to_f16(ctx, prev, (size_t)n * Hs * Ws * kDims[s - 1], x16));
-                REID_TRY(conv16(ctx, w.zero_page, x16, n, Hs, Ws, kDims[s - 1], w.merge16[s], w.merge_b[s], C, 2, 2, 2, 0, 0, Hs / 2, Ws / 2,
-                                nullptr, nullptr, xcur));
-            } else {
-                REID_TRY(conv_bias(ctx, prev, n, Hs, Ws, kDims[s - 1], w.merge_w[s], w.merge_b[s], C, 2, 2, 2, 0, 0, Hs / 2, Ws / 2, nullptr, xcur, 0, 0,
-                                   0, 0, w.zero_page));
-            }
+            REID_TRY(swin_merge(ctx, w, s, prev, n, Hs, Ws, lnb, xcur));
             Hs /= 2;
             Ws /= 2;
         }
@@ -1756,7 +1903,6 @@ static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float*
             // the first block reads the ShadowFeatureExtraction output (kept for the top-down fusion) and writes stage 1's
             // residual stream; every later block updates that stream in place
             const float* xin = (s == 0 && j == 0) ? sfe : xcur;
-            const long long ntask = (long long)n * (Hs / 7) * (Ws / 7) * heads;
             if (w.version == 2) {   // post-norm blocks with cosine attention; REID_SWIN_STOP's phases inside a block are v1's only
                 REID_TRY(swin_block_v2(ctx, k, w.blk16[bi], xin, xcur, T, n, Hs, Ws, C, heads, shifted, j == 0, lnb, big, att, tmp));
                 continue;
@@ -1769,20 +1915,12 @@ static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float*
                 f16* big16 = (f16*)big;                // qkv [T][ldq] / MLP hidden [T][4C]
                 f16* att16 = (f16*)att;                // [T][C]
                 f16* tmp16 = (f16*)tmp;                // [T][C]
-                const int ldq = (3 * C + 63) / 64 * 64;
+                const int ldq = swin_attn_ldq(ctx, C);
                 prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T * C * 6);
                 launch_layernorm<f16>(ctx, xin, T, C, k.ln1_g, k.ln1_b, ln16);
                 prof_end(ctx);
                 REID_TRY(linear16(ctx, ln16, T, C, C, h.qkv, nullptr, 3 * C, 0, nullptr, big16, nullptr, ldq));
-                prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T * C * 8);
-                if (ctx->swin_attn_mfma)
-                    hipLaunchKernelGGL(window_attn_mfma_f16_kernel, dim3((unsigned)((ntask + 3) / 4)), dim3(256), 0, ctx->stream, big16, ldq,
-                                       n, Hs, Ws, heads, shifted, h.bias_tab, att16);
-                else
-                    hipLaunchKernelGGL(window_attn_kernel<f16>, dim3((unsigned)((ntask + 3) / 4)), dim3(256), 0, ctx->stream, big16, ldq, n,
-                                       Hs, Ws, heads, shifted, k.pos, att16);
-                prof_end(ctx);
-                LAUNCH_CHECK();
+                REID_TRY(launch_window_attn(ctx, big16, n, Hs, Ws, heads, shifted, k.pos, h.bias_tab, att16));
                 if (ctx->swin_fold) {   // to_out . post_proj as one Linear (folded at load time)
                     REID_TRY(linear16(ctx, att16, T, C, C, h.fold, h.fold_b, C, 0, xin, nullptr, xcur, C));
                 } else {
@@ -1814,15 +1952,7 @@ static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float*
                     prof_end(ctx);
                     REID_TRY(linear(ctx, nullptr, T, C, k.qkv_w, nullptr, 3 * C, 0, nullptr, big, ln16));
                 }
-                prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T * C * 16);
-                if (ctx->swin_attn_split)
-                    hipLaunchKernelGGL(window_attn_mfma_split_kernel, dim3((unsigned)((ntask + 3) / 4)), dim3(256), 0, ctx->stream, big, 3 * C, n,
-                                       Hs, Ws, heads, shifted, w.blk16[bi].bias_tab, att16, ctx->fault);
-                else
-                    hipLaunchKernelGGL(window_attn_kernel<float>, dim3((unsigned)((ntask + 3) / 4)), dim3(256), 0, ctx->stream, big, 3 * C, n,
-                                       Hs, Ws, heads, shifted, k.pos, (float*)nullptr, att16, ctx->fault);
-                prof_end(ctx);
-                LAUNCH_CHECK();
+                REID_TRY(launch_window_attn(ctx, big, n, Hs, Ws, heads, shifted, k.pos, w.blk16[bi].bias_tab, att16));
                 // each pair of linears as ONE launch where the hidden values fit the register file (two_linear_f16.hip): same
                 // roundings (the hidden layer is split into [hh | hl'] as the first launch's epilogue did), no [T][C] / [T][4C] trip
                 if (two_linear_supported(ctx, T, C, C)) {
@@ -1847,15 +1977,7 @@ static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float*
             launch_layernorm<float>(ctx, xin, T, C, k.ln1_g, k.ln1_b, lnb);
             prof_end(ctx);
             REID_TRY(linear(ctx, lnb, T, C, k.qkv_w, nullptr, 3 * C, 0, nullptr, big));
-            prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T * C * 16);
-            if (ctx->swin_attn_mfma == 2)   // fp32 MFMA runs at the fp32 VALU rate: measured 5 % slower than the VALU kernel, kept for A/B
-                hipLaunchKernelGGL(window_attn_mfma_f32_kernel, dim3((unsigned)((ntask + 1) / 2)), dim3(128), 0, ctx->stream, big, 3 * C, n,
-                                   Hs, Ws, heads, shifted, k.pos, att);
-            else
-                hipLaunchKernelGGL(window_attn_kernel<float>, dim3((unsigned)((ntask + 3) / 4)), dim3(256), 0, ctx->stream, big, 3 * C, n,
-                                   Hs, Ws, heads, shifted, k.pos, att);
-            prof_end(ctx);
-            LAUNCH_CHECK();
+            REID_TRY(launch_window_attn(ctx, big, n, Hs, Ws, heads, shifted, k.pos, w.blk16[bi].bias_tab, att));
             REID_TRY(linear(ctx, att, T, C, k.out_w, k.out_b, C, 0, nullptr, tmp));
             REID_TRY(linear(ctx, tmp, T, C, k.post_w, k.post_b, C, 0, xin, xcur));
             // x = x + fc2(gelu(fc1(LN(x))))
@@ -1868,48 +1990,11 @@ static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float*
         prev = xcur;
     }
     // top-down fusion (:405-412): f = stage4 + Conv8x8s8(sfe); then three ConvTranspose2d(4, 2, 1) + stage outputs
-    const int H4 = H1 / 8, W4 = W1 / 8;
-    const float* fin;
-    if (ctx->precision == 1) {
-        // same fusion with f16 feature maps between the steps; every step adds its fp32 stage output in the epilogue
-        f16* sfe16 = (f16*)att;
-        f16* maps16[3] = {(f16*)tmp, (f16*)f3, (f16*)f2};   // [n,7,7,768] -> [n,14,14,384] -> [n,28,28,192]
-        REID_TRY(launch_f32_to_f16(ctx, sfe, (size_t)T1 * 96, sfe16));
-        REID_TRY(conv16(ctx, w.zero_page, sfe16, n, H1, W1, 96, w.img16, w.img_b, 768, 8, 8, 8, 0, 0, H4, W4, xs[3], maps16[0], nullptr));
-        int Hi = H4, Wi = W4;
-        for (int t = 0; t < 3; ++t) {
-            const int ci = kDims[3 - t], co = kDims[2 - t];
-            const size_t wstride = (size_t)((co + 63) / 64 * 64) * 4 * ci;
-            // the four output parities of the ConvTranspose2d(4, 2, 1) as ONE launch (4 x the tile grid): a parity alone is 147-784
-            // blocks, too few for 256 CUs
-            REID_TRY(conv16(ctx, w.zero_page, maps16[t], n, Hi, Wi, ci, w.t16[t], w.t_b[t], co, 2, 2, 1, 1, 1, Hi, Wi, xs[2 - t],
-                            t < 2 ? maps16[t + 1] : nullptr, t < 2 ? nullptr : f1, Hi, Wi, 0, 0, (long long)wstride));
-            Hi *= 2;
-            Wi *= 2;
-        }
-        fin = f1;
-    } else {
-    REID_TRY(conv_bias(ctx, sfe, n, H1, W1, 96, w.img_w, w.img_b, 768, 8, 8, 8, 0, 0, H4, W4, xs[3], tmp, 0, 0, 0, 0, w.zero_page));
-    fin = tmp;
-    float* fouts[3] = {f3, f2, f1};
-    int Hi = H4, Wi = W4;
-    for (int t = 0; t < 3; ++t) {
-        const int ci = kDims[3 - t], co = kDims[2 - t];
-        REID_TRY(conv_transpose_parities(ctx, fin, n, Hi, Wi, ci, w.t_w[t], w.t_b[t], co, xs[2 - t], fouts[t], w.zero_page));
-        fin = fouts[t];
-        Hi *= 2;
-        Wi *= 2;
-    }
-    }
+    REID_TRY(swin_fuse(ctx, w, sfe, xs, n, H1, W1, att, tmp, f3, f2, f1));
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T1 * 96 * 4);
-    float* tail_part;
-    REID_TRY(ctx_ws(ctx, "swin.tailp", (size_t)n * TAIL_SLICES * 96 * 4, (void**)&tail_part));
-    hipLaunchKernelGGL(swin_tail_partial_kernel, dim3(n, TAIL_SLICES), dim3(256), 0, ctx->stream, fin, H1 * W1, w.tail_g, w.tail_b,
-                       w.tail_p, tail_part);
-    hipLaunchKernelGGL(swin_tail_final_kernel, dim3((n * 96 + 255) / 256), dim3(256), 0, ctx->stream, tail_part, n, H1 * W1, w.tail_p,
-                       w.neck_s, w.neck_t, gem, d_emb, ctx->fault);
+    const int tail_rc = launch_swin_tail(ctx, f1, n, H1 * W1, w.tail_g, w.tail_b, w.tail_p, w.neck_s, w.neck_t, gem, d_emb);
     prof_end(ctx);
-    LAUNCH_CHECK();
+    REID_TRY(tail_rc);
     if (d_logits) {
         if (!w.cls_w) {
             reid_set_error("logits requested but the Swin blob has no classifier");

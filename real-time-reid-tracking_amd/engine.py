@@ -689,6 +689,105 @@ class Engine:
         f = o16.view(np.float16)
         return out, (f[:, :c].astype(np.float64) + f[:, c:].astype(np.float64) / 2048.0) if side == 2 else f.astype(np.float32)
 
+    @staticmethod
+    def _unpack16(o16, c):
+        """[yh | yl'] uint16 f16 bits [t, 2c] -> float64 yh + yl' / 2^11."""
+        f = o16.view(np.float16)
+        return f[:, :c].astype(np.float64) + f[:, c:].astype(np.float64) / 2048.0
+
+    def debug_window_attn(self, form, qkv, pos, shifted, raw=False):
+        """One Swin v1 window-attention kernel through launch_window_attn (libreid_hip_debug.so reid_debug_window_attn; forms in
+        include/reid_hip_debug.h).  qkv [n, h, w, 3 * heads * 32] fp32, pos [13, 13].  Returns [n, h, w, C]: fp32 (forms 0, 5), the
+        [oh | ol'] pair decoded to float64 (1, 4), the f16 result as fp32 (2, 3); raw=True: the fp32 / uint16 array as the launch left it."""
+        qkv, pos = _f32(qkv), _f32(pos).reshape(-1)
+        n, h, w, c3 = qkv.shape
+        c = c3 // 3
+        if c3 != 3 * c or c % 32 or pos.size != 169:
+            raise ValueError("debug_window_attn expects qkv[n, h, w, 3 * heads * 32] and pos[13, 13]")
+        out = np.empty((n, h, w, c), np.float32) if form in (0, 5) else None
+        o16 = None if form in (0, 5) else np.empty((n * h * w, 2 * c if form in (1, 4) else c), np.uint16)
+        check(_ffi.debug_lib().reid_debug_window_attn(
+            self.h, C.c_int(form), _ptr(qkv), C.c_int(n), C.c_int(h), C.c_int(w), C.c_int(c // 32), C.c_int(int(bool(shifted))), _ptr(pos),
+            _ptr(out), _ptr(o16)))
+        if raw:
+            return out if o16 is None else o16
+        if o16 is None:
+            return out
+        if form in (1, 4):
+            return self._unpack16(o16, c).reshape(n, h, w, c)
+        return o16.view(np.float16).astype(np.float32).reshape(n, h, w, c)
+
+    def debug_layernorm(self, form, x, g, b):
+        """The Swin LayerNorm (eps 1e-5) through the forward's launchers (reid_debug_layernorm): x [t, c].  form 0 -> fp32 [t, c]; 1 -> uint16
+        f16 bits [t, c]; 2 -> uint16 [t, 2c] = [yh | yl']."""
+        x = _f32(x)
+        t, c = x.shape
+        out = np.empty((t, c), np.float32) if form == 0 else None
+        o16 = None if form == 0 else np.empty((t, 2 * c if form == 2 else c), np.uint16)
+        check(_ffi.debug_lib().reid_debug_layernorm(self.h, C.c_int(form), _ptr(x), C.c_int(t), C.c_int(c), _ptr(_f32(g)), _ptr(_f32(b)),
+                                                    _ptr(out), _ptr(o16)))
+        return out if form == 0 else o16
+
+    def debug_ln_linear(self, x, ln_g, ln_b, w, bias=None):
+        """LayerNorm 1 + to_qkv of the fp32-class mode in one kernel (reid_debug_ln_linear): x [t, c], w [n, c] -> fp32 [t, n]."""
+        x, w = _f32(x), _f32(w)
+        t, c = x.shape
+        n = w.shape[0]
+        out = np.empty((t, n), np.float32)
+        check(_ffi.debug_lib().reid_debug_ln_linear(self.h, _ptr(x), _ptr(_f32(ln_g)), _ptr(_f32(ln_b)), _ptr(w),
+                                                    _ptr(_f32(bias) if bias is not None else None), C.c_int(t), C.c_int(c), C.c_int(n), _ptr(out)))
+        return out
+
+    def debug_swin_sfe(self, c1, in_g, in_b, bn_s, bn_t, c2_w, c2_b, fc_w, fc_b):
+        """ShadowFeatureExtraction after its first convolution (reid_debug_swin_sfe): c1 [n, h1, w1, 12], c2_w [48, 48] in (kh, kw, c) order,
+        fc_w [96, 48].  Returns (ab [n, 24], tok [n, h1 / 2, w1 / 2, 96])."""
+        c1 = _f32(c1)
+        n, h1, w1, _ = c1.shape
+        prm = [_f32(a).reshape(-1) for a in (in_g, in_b, bn_s, bn_t, c2_w, c2_b, fc_w, fc_b)]
+        if c1.shape[3] != 12 or [a.size for a in prm] != [6, 6, 6, 6, 2304, 48, 4608, 96]:
+            raise ValueError("debug_swin_sfe: operand shapes")
+        ab, tok = np.empty((n, 24), np.float32), np.empty((n, h1 // 2, w1 // 2, 96), np.float32)
+        check(_ffi.debug_lib().reid_debug_swin_sfe(self.h, _ptr(c1), C.c_int(n), C.c_int(h1), C.c_int(w1), *[_ptr(a) for a in prm], _ptr(ab),
+                                                   _ptr(tok)))
+        return ab, tok
+
+    def debug_swin_tail(self, x, g, b, p, bn_s, bn_t):
+        """The Swin tail (reid_debug_swin_tail): x [n, ntok, 96] -> (gem [n, 96], emb [n, 96])."""
+        x = _f32(x)
+        n, ntok, c = x.shape
+        prm = [_f32(a).reshape(-1) for a in (g, b, bn_s, bn_t)]
+        if c != 96 or any(a.size != 96 for a in prm):
+            raise ValueError("debug_swin_tail expects x[n, ntok, 96] and 96-channel parameters")
+        gem, emb = np.empty((n, 96), np.float32), np.empty((n, 96), np.float32)
+        check(_ffi.debug_lib().reid_debug_swin_tail(self.h, _ptr(x), C.c_int(n), C.c_int(ntok), _ptr(prm[0]), _ptr(prm[1]), C.c_float(p),
+                                                    _ptr(prm[2]), _ptr(prm[3]), _ptr(gem), _ptr(emb)))
+        return gem, emb
+
+    def debug_swin_merge(self, stage, x):
+        """Patch merging in front of ``stage`` (2 .. 4) on the loaded Swin weights, in this context's precision (reid_debug_swin_merge):
+        x [n, h, w, 48 * 2^(stage - 1)] -> fp32 [n, h / 2, w / 2, 96 * 2^(stage - 1)]."""
+        x = _f32(x)
+        n, h, w, cin = x.shape
+        if cin != 48 << (stage - 1):
+            raise ValueError("debug_swin_merge: stage %d takes %d channels" % (stage, 48 << (stage - 1)))
+        out = np.empty((n, h // 2, w // 2, 2 * cin), np.float32)
+        check(_ffi.debug_lib().reid_debug_swin_merge(self.h, C.c_int(stage), _ptr(x), C.c_int(n), C.c_int(h), C.c_int(w), _ptr(out)))
+        return out
+
+    def debug_swin_fuse(self, sfe, x1, x2, x3, x4):
+        """The top-down fusion on the loaded Swin weights, in this context's precision (reid_debug_swin_fuse).  sfe / x1 [n, h1, w1, 96], x2 ..
+        x4 the later stage outputs.  Returns [a0, f3, f2, f1]; with the context in precision 1 the first three are f16 arrays."""
+        maps = [_f32(a) for a in (sfe, x1, x2, x3, x4)]
+        n, h1, w1, _ = maps[0].shape
+        shapes = [(n, h1 >> s, w1 >> s, 96 << s) for s in (0, 0, 1, 2, 3)]
+        if [a.shape for a in maps] != shapes:
+            raise ValueError("debug_swin_fuse: expected maps of shapes %r" % (shapes,))
+        dt = np.uint16 if self.precision == 1 else np.float32
+        outs = [np.empty(shapes[4], dt), np.empty(shapes[3], dt), np.empty(shapes[2], dt), np.empty(shapes[1], np.float32)]
+        check(_ffi.debug_lib().reid_debug_swin_fuse(self.h, *[_ptr(a) for a in maps], C.c_int(n), C.c_int(h1), C.c_int(w1),
+                                                    *[_ptr(a) for a in outs]))
+        return [a.view(np.float16) if a.dtype == np.uint16 else a for a in outs]
+
     def debug_swin_stage(self, stage, n, h=224, w=224):
         """Stage activations of the last Swin pass as NHWC arrays (0 sfe, 1..4 stage outputs, 5 GeM output [n,96])."""
         if stage == 5:
