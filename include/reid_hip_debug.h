@@ -76,6 +76,11 @@ int reid_debug_sibling_tail(reid_ctx* ctx, int arch, int n, int h, int w, int c,
 /* gem_neck: GeM (exponent p) + BNNeck, emb = gem * scale + shift, on fp32 x (f16 = 0) or f16 x (f16 = 1); gem_out may be null. */
 int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale, const float* shift,
                         float* gem_out, float* emb);
+/* gem_neck of the last block's tail in one launch (launch_gem_neck_tail; tests/test_gpu_tail_stream.py): GeM + BNNeck of
+ * relu(gate y + shortcut) with se_tail's gate, fp32 operands as in se_tail; equals se_tail form 4 followed by gem_neck bit for bit. */
+int reid_debug_gem_neck_fused(reid_ctx* ctx, int n, int hw, int c, int mid, int tiles, float p, const float* stats, const float* w1,
+                              const float* w2t, const float* y, const float* shortcut, const float* scale, const float* shift,
+                              float* gem_out, float* emb);
 /* The front end of a ResNet pass (correctness harness, tests/test_gpu_frontend.py), each through the launcher the forward calls, on host
  * operands.  Every output the launch leaves alone reads as NaN (0xffff); each call returns the context's fault status.
  * stem: conv 7x7 stride 2 pad 3 (3 -> 64) * scale + shift, no ReLU, + MaxPool(3, 2, 1).  x [n][256][128][3], uint8 crops (is_u8, normalised

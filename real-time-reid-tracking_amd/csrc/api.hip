@@ -858,6 +858,7 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
 
     const float* cur = b.pool;
     int H = 64, W = 32;
+    bool gem_done = false;
     if (split_mode && !stem_split) REID_TRY(launch_split_pack(ctx, b.pool, (long long)n * 64 * 32, 64, cur16));
     for (int i = 0; i < 8; ++i) {
         const Se18Block& k = w.blk[i];
@@ -950,8 +951,16 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
                 fp32_read = !(conv_split_path(ctx, n, Ho, Wo, nx.cin, nx.c, 3, 3, nx.stride, 1) &&
                               conv_split_path(ctx, n, Ho, Wo, nx.cin, nx.c, 1, 1, nx.stride, 0));
             }
-            REID_TRY(launch_se_tail(ctx, b.stats, n, tiles, k.c, k.mid, hw, k.se_w1, k.se_w2, y, shortcut, fp32_read ? out : nullptr,
-                                    i < 7 ? cur16 : nullptr));
+            // the last block of a large pass: GeM is the only reader of its output, and forms it from (y, shortcut, gate) itself - the
+            // tensor is neither written nor read back (debug-keep wants the stage tap; a small pass needs GeM's c / 64 blocks per image)
+            if (i == 7 && !keep && n >= ctx->gem_tail_min) {
+                REID_TRY(launch_gem_neck_tail(ctx, b.stats, n, tiles, k.c, k.mid, hw, k.se_w1, k.se_w2, y, shortcut, w.gem_p, w.neck_scale,
+                                              w.neck_shift, b.gem, d_emb));
+                gem_done = true;
+            } else {
+                REID_TRY(launch_se_tail(ctx, b.stats, n, tiles, k.c, k.mid, hw, k.se_w1, k.se_w2, y, shortcut, fp32_read ? out : nullptr,
+                                        i < 7 ? cur16 : nullptr));
+            }
         } else {
             REID_TRY(launch_se_finalize(ctx, b.stats, n, tiles, k.c, k.mid, hw, k.se_w1, k.se_w2, b.se));
             REID_TRY(launch_se_combine(ctx, y, shortcut, b.se, n, hw, k.c, out));
@@ -961,7 +970,7 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
         H = Ho;
         W = Wo;
     }
-    REID_TRY(launch_gem_neck(ctx, cur, n, H * W, 512, w.gem_p, w.neck_scale, w.neck_shift, b.gem, d_emb));
+    if (!gem_done) REID_TRY(launch_gem_neck(ctx, cur, n, H * W, 512, w.gem_p, w.neck_scale, w.neck_shift, b.gem, d_emb));
     {   // SERse18_IBN.forward(x, cam): + cam_factor * cam_bias[cam] on the BNNeck output, before the classifier (:269-271)
         const int32_t* d_cam;
         REID_TRY(ctx_take_side(ctx, n, w.num_cams, "reid_embed (camera bias)", &d_cam));

@@ -24,7 +24,7 @@ const Switch kSwitches[] = {
     {"f16_se_tail", &reid_ctx::f16_se_tail}, {"f16_c64", &reid_ctx::f16_c64}, {"swin_chunk_cap", &reid_ctx::swin_chunk_cap},
     {"split_x3", &reid_ctx::split_x3}, {"x3_ablate", &reid_ctx::x3_ablate}, {"x3_unroll", &reid_ctx::x3_unroll}, {"x3_narrow", &reid_ctx::x3_narrow}, {"conv_x3s", &reid_ctx::conv_x3s}, {"x3s_sk_cap", &reid_ctx::x3s_sk_cap}, {"x3_l4_narrow_nmt", &reid_ctx::x3_l4_narrow_nmt}, {"split_x3_small", &reid_ctx::split_x3_small}, {"split_x3_min_blocks", &reid_ctx::split_x3_min_blocks}, {"f32_dist_bk16", &reid_ctx::f32_dist_bk16}, {"lin_x3", &reid_ctx::lin_x3},
     {"host_pipeline", &reid_ctx::host_pipeline}, {"x3_sk_cap", &reid_ctx::x3_sk_cap}, {"chain", &reid_ctx::chain}, {"split_gemm_min_tiles", &reid_ctx::split_gemm_min_tiles},
-    {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc},
+    {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc}, {"gem_tail_min", &reid_ctx::gem_tail_min},
 };
 }  // namespace
 
@@ -666,6 +666,32 @@ extern "C" int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c,
         REID_TRY(dbg_upload(ctx, "dbgt.x", (const float*)x, nx, &dx));
         REID_TRY(launch_gem_neck(ctx, dx, n, hw, c, dp, dsc, dsh, dg, de));
     }
+    if (dg) REID_TRY(dbg_download(ctx, gem_out, dg, ne));
+    REID_TRY(dbg_download(ctx, emb, de, ne));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// GeM + BNNeck of the last block's tail in one launch (launch_gem_neck_tail): what reid_debug_se_tail form 4 followed by
+// reid_debug_gem_neck computes, without the tensor between them.
+extern "C" int reid_debug_gem_neck_fused(reid_ctx* ctx, int n, int hw, int c, int mid, int tiles, float p, const float* stats, const float* w1,
+                                         const float* w2t, const float* y, const float* shortcut, const float* scale, const float* shift,
+                                         float* gem_out, float* emb) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && mid >= 1 && tiles >= 1 && stats && w1 && w2t && y && shortcut && scale && shift && emb);
+    CTX_ENTER(ctx);
+    const size_t ny = (size_t)n * hw * c, ne = (size_t)n * c;
+    float *dst, *dw1, *dw2, *dy, *dsc, *dp, *dbs, *dbh, *dg = nullptr, *de;
+    REID_TRY(dbg_upload(ctx, "dbgt.stats", stats, (size_t)n * tiles * c * 2, &dst));
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", w1, (size_t)mid * c, &dw1));
+    REID_TRY(dbg_upload(ctx, "dbgt.w2", w2t, (size_t)mid * c, &dw2));
+    REID_TRY(dbg_upload(ctx, "dbgt.x", y, ny, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgt.sc", shortcut, ny, &dsc));
+    REID_TRY(dbg_upload(ctx, "dbgt.p", &p, 1, &dp));
+    REID_TRY(dbg_upload(ctx, "dbgt.bns", scale, (size_t)c, &dbs));
+    REID_TRY(dbg_upload(ctx, "dbgt.bnh", shift, (size_t)c, &dbh));
+    if (gem_out) REID_TRY(dbg_output(ctx, "dbgt.a", ne, &dg));
+    REID_TRY(dbg_output(ctx, "dbgt.b", ne, &de));
+    REID_TRY(launch_gem_neck_tail(ctx, dst, n, tiles, c, mid, hw, dw1, dw2, dy, dsc, dp, dbs, dbh, dg, de));
     if (dg) REID_TRY(dbg_download(ctx, gem_out, dg, ne));
     REID_TRY(dbg_download(ctx, emb, de, ne));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -299,6 +299,10 @@ int launch_in_apply_pack(reid_ctx*, const float* x, const float* stats, int n_im
                          bool in_half_only = false);   // the BatchNorm half was packed by the conv epilogue already
 int launch_gem_neck(reid_ctx*, const float* x, int n_img, int hw, int c, const float* p, const float* scale,
                     const float* shift, float* gem_out, float* emb);
+// the same of relu(gate * y + sc) with the gate of launch_se_tail: the last block's tail and GeM in one kernel, no activation tensor between
+int launch_gem_neck_tail(reid_ctx*, const float* stats, int n_img, int tiles, int c, int mid, int hw, const float* w1, const float* w2,
+                         const float* y, const float* sc, const float* p, const float* scale, const float* shift, float* gem_out,
+                         float* emb);
 int launch_row_sqnorm(reid_ctx*, const float* x, int m, int d, long long ld, float* out);
 // selection kernels (select.hip)
 int launch_argmin_rows(reid_ctx*, const float* dist, int m, int n, long long ld, int32_t* idx, float* val);
@@ -394,6 +398,8 @@ struct reid_ctx {
                               // the plain f16 build loses 0.6 %), 2 = all, 0 = none (REID_F16_LOADER_PRIO)
     int f16_loader_waves = 1; // LDS-halo kernel: 8 compute + 4 dedicated loader waves (REID_F16_LOADERS)
     int f16_halo = 1;        // 3x3 stride-1 convs of the fp16 path use the LDS-halo kernel (REID_F16_HALO=0: implicit GEMM)
+    int gem_tail_min = 120;  // fp32-class ResNet18-SE: from this many images the last block's tail runs inside GeM (launch_gem_neck_tail):
+                             // 120 crops 25.4 us against 28.9 + 8.1, 30 crops 16.3 against 12.6 + 4.9 (profiles/tails_stream_ab.txt)
     int f16_se_tail = 1;     // fp16 path: SE gate + combine in one launch per block (REID_F16_SETAIL=0: se_finalize + se_combine)
     int f16_c64 = 2;         // fp16 path: layer-1 convs on the register-resident-weight kernel, 2 = with the SE tail fused
                              // into conv2 (REID_F16_C64=1: separate se_finalize / se_combine kernels, 0: implicit GEMM)

@@ -583,6 +583,18 @@ class Engine:
             _ptr(_f32(shift)), _ptr(g), _ptr(e)))
         return g, e
 
+    def debug_gem_neck_fused(self, stats, w1, w2t, y, shortcut, p, scale, shift):
+        """GeM + BNNeck of the last block's tail in one launch (libreid_hip_debug.so reid_debug_gem_neck_fused): operands as in
+        debug_se_tail (fp32) and debug_gem_neck.  Returns (gem [n, c], emb [n, c])."""
+        stats = _f32(stats)
+        n, tiles, c, _ = stats.shape
+        y, shortcut = _f32(y), _f32(shortcut)
+        g, e = np.empty((n, c), np.float32), np.empty((n, c), np.float32)
+        check(_ffi.debug_lib().reid_debug_gem_neck_fused(
+            self.h, C.c_int(n), C.c_int(y.shape[1]), C.c_int(c), C.c_int(w1.shape[0]), C.c_int(tiles), C.c_float(p), _ptr(stats),
+            _ptr(_f32(w1)), _ptr(_f32(w2t)), _ptr(y), _ptr(shortcut), _ptr(_f32(scale)), _ptr(_f32(shift)), _ptr(g), _ptr(e)))
+        return g, e
+
     def debug_stem(self, form, x, w, scale, shift):
         """The stem + max-pool through the forward's launchers (libreid_hip_debug.so reid_debug_stem; forms in include/reid_hip_debug.h).
         x [n, 256, 128, 3] uint8 crops or fp32 (already normalised), w [64, 7, 7, 3].  Returns (out, out16), None where the form has no
