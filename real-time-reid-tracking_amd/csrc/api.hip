@@ -997,6 +997,36 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
     return REID_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ side libraries
+// The one loader of the libraries that lie beside this one and are opened on first use: libreid_hip_siblings_f16.so (below),
+// libreid_hip_swin_v2.so and libreid_hip_swin_crops.so (swin.hip).  Contract: reid_internal.h.
+int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns) {
+    Dl_info info;
+    std::string path = file;
+    if (dladdr((const void*)&open_beside_self, &info) && info.dli_fname) {
+        const std::string self = info.dli_fname;
+        const size_t slash = self.rfind('/');
+        if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
+    }
+    void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+    if (!h) {
+        reid_set_error("%s %s beside libreid_hip.so: %s", what, path.c_str(), dlerror());
+        return REID_ERR_STATE;
+    }
+    std::string listed;
+    bool all = true;
+    for (const char* name : names) {
+        all = (*fns++ = dlsym(h, name)) != nullptr && all;
+        listed += listed.empty() ? name : std::string(" / ") + name;
+    }
+    if (!all) {
+        dlclose(h);
+        reid_set_error("%s lacks %s", path.c_str(), listed.c_str());
+        return REID_ERR_STATE;
+    }
+    return REID_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ fp16 forward
 // libreid_hip_siblings_f16.so (siblings_f16.h), opened from the directory this library lies in the first time a sibling backbone
 // (CARes18_IBN / EMARes18_IBN) runs in the fp16-storage mode: a process that never does never opens it.  Missing library or symbol:
@@ -1011,29 +1041,12 @@ static int siblings_f16_api(const SiblingsF16Api** out) {
     static SiblingsF16Api api;
     std::lock_guard<std::mutex> lk(m);
     if (!api.ta) {
-        Dl_info info;
-        std::string path = "libreid_hip_siblings_f16.so";
-        if (dladdr((const void*)&siblings_f16_api, &info) && info.dli_fname) {
-            const std::string self = info.dli_fname;
-            const size_t slash = self.rfind('/');
-            if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
-        }
-        void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) {
-            reid_set_error("CARes18-IBN / EMARes18-IBN in the fp16-storage mode need %s beside libreid_hip.so: %s", path.c_str(), dlerror());
-            return REID_ERR_STATE;
-        }
-        auto b = (decltype(api.ta_bytes))dlsym(h, "siblings_f16_ta_workspace_bytes");
-        auto t = (decltype(api.ta))dlsym(h, "siblings_f16_ta_tail");
-        auto e = (decltype(api.ema))dlsym(h, "siblings_f16_ema_tail");
-        if (!b || !t || !e) {
-            dlclose(h);
-            reid_set_error("%s lacks siblings_f16_ta_workspace_bytes / siblings_f16_ta_tail / siblings_f16_ema_tail", path.c_str());
-            return REID_ERR_STATE;
-        }
-        api.ta_bytes = b;
-        api.ema = e;
-        api.ta = t;
+        void* f[3];
+        REID_TRY(open_beside_self("libreid_hip_siblings_f16.so", "CARes18-IBN / EMARes18-IBN in the fp16-storage mode need",
+                                  {"siblings_f16_ta_workspace_bytes", "siblings_f16_ta_tail", "siblings_f16_ema_tail"}, f));
+        api.ta_bytes = (decltype(api.ta_bytes))f[0];
+        api.ema = (decltype(api.ema))f[2];
+        api.ta = (decltype(api.ta))f[1];
     }
     *out = &api;
     return REID_OK;
@@ -1275,140 +1288,187 @@ int ctx_pipe_events(reid_ctx* ctx, int passes) {
     return REID_OK;
 }
 
+// ---- the pieces of the host entry points (reid_internal.h)
+int EmbedOut::alloc(reid_ctx* ctx, const char* tag, int n, int pad_rows, bool want_logits) {
+    const std::string t(tag);
+    REID_TRY(ctx_ws(ctx, (t + ".emb").c_str(), (size_t)(n + pad_rows) * dim * 4, (void**)&d_emb));
+    if (want_logits) REID_TRY(ctx_ws(ctx, (t + ".logits").c_str(), (size_t)n * nc * 4 + 16, (void**)&d_log));
+    return REID_OK;
+}
+
+int EmbedOut::down(int i, int m, hipStream_t s) const {
+    HIP_TRY(hipMemcpyAsync(emb + (size_t)i * dim, d_emb + (size_t)i * dim, (size_t)m * dim * 4, hipMemcpyDeviceToHost, s));
+    if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
+    return REID_OK;
+}
+
+int RaggedSrc::check() {
+    total = 0;
+    for (int i = 0; i < n; ++i) {
+        ARG_CHECK(hw[2 * i] >= 1 && hw[2 * i + 1] >= 1 && offsets[i] >= 0);
+        const size_t end = (size_t)offsets[i] + (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
+        if (end > total) total = end;
+    }
+    return REID_OK;
+}
+
+int windows_from_boxes(const int32_t* boxes_xyxy, int n, int fh, int fw, int64_t* off, int32_t* hw) {
+    for (int i = 0; i < n; ++i) {
+        const int x1 = boxes_xyxy[4 * i], y1 = boxes_xyxy[4 * i + 1], x2 = boxes_xyxy[4 * i + 2], y2 = boxes_xyxy[4 * i + 3];
+        ARG_CHECK(x1 >= 0 && y1 >= 0 && x2 <= fw && y2 <= fh && x2 > x1 && y2 > y1);   // an empty slice fails in cv2.resize too
+        off[i] = ((int64_t)y1 * fw + x1) * 3;
+        hw[2 * i] = y2 - y1;
+        hw[2 * i + 1] = x2 - x1;
+    }
+    return REID_OK;
+}
+
+int RaggedSrc::frame(const uint8_t* frame_u8, int fh, int fw, const int32_t* boxes_xyxy, int n_boxes) {
+    win.resize(2 * (size_t)n_boxes);
+    src = frame_u8;
+    n = n_boxes;
+    offsets = win.data();
+    hw = (const int32_t*)(win.data() + n);
+    pitch = fw;
+    total = (size_t)fh * fw * 3;
+    return windows_from_boxes(boxes_xyxy, n, fh, fw, win.data(), (int32_t*)(win.data() + n));
+}
+
+int RaggedSrc::alloc(reid_ctx* ctx, const char* tag) {
+    const std::string t(tag);
+    char* d_meta;
+    REID_TRY(ctx_ws(ctx, (t + ".in").c_str(), total, (void**)&d_src));
+    REID_TRY(ctx_ws(ctx, (t + ".meta").c_str(), (size_t)n * 16, (void**)&d_meta));
+    d_off = (long long*)d_meta;
+    d_hw = (int*)(d_meta + (size_t)n * 8);
+    return REID_OK;
+}
+
+int RaggedSrc::up(int i, int m, hipStream_t s) const {
+    size_t lo = (size_t)-1, hi = 0;
+    if (pitch) {
+        lo = 0;
+        hi = i == 0 ? total : 0;
+    } else {
+        for (int j = i; j < i + m; ++j) {
+            const size_t b = (size_t)offsets[j], e = b + (size_t)hw[2 * j] * hw[2 * j + 1] * 3;
+            if (b < lo) lo = b;
+            if (e > hi) hi = e;
+        }
+    }
+    // pixels, then metadata: the order of the frame pipeline's upload (embed_ragged_enqueue) for every caller
+    if (hi > lo) HIP_TRY(hipMemcpyAsync(d_src + lo, src + lo, hi - lo, hipMemcpyHostToDevice, s));
+    if (i != 0) return REID_OK;
+    if ((const char*)hw == (const char*)offsets + (size_t)n * 8) {
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, (size_t)n * 16, hipMemcpyHostToDevice, s));
+    } else {
+        HIP_TRY(hipMemcpyAsync(d_off, offsets, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_hw, hw, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    }
+    return REID_OK;
+}
+
+// ---- the "run one pass" steps of the six ResNet18-SE entry points
+static const size_t kCropElems = (size_t)IMG_H * IMG_W * 3;
+
+static int se_run_nchw(reid_ctx* ctx, const float* d_x, int m, float* d_emb, float* d_log) {
+    float* nhwc;
+    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * kCropElems * 4, (void**)&nhwc));
+    REID_TRY(launch_nchw_to_nhwc3(ctx, d_x, m, IMG_H, IMG_W, nhwc));
+    return seres18_run(ctx, nhwc, false, m, d_emb, d_log);
+}
+
+// windows [i, i + m) of an uploaded RaggedSrc: device-side resize + normalise, forward
+static int se_run_windows(reid_ctx* ctx, const RaggedSrc& src, int i, int m, float* d_emb, float* d_log) {
+    float* nhwc;
+    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * kCropElems * 4, (void**)&nhwc));
+    REID_TRY(launch_resize_norm(ctx, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, IMG_H, IMG_W, src.pitch, nhwc));
+    return seres18_run(ctx, nhwc, false, m, d_emb, d_log);
+}
+
+static int se_embed_windows(reid_ctx* ctx, RaggedSrc& src, float* emb, float* logits) {
+    EmbedOut out{emb, logits, 512, ctx->se18.num_class};
+    REID_TRY(src.alloc(ctx, "io"));
+    REID_TRY(out.alloc(ctx, "io", src.n, 0, logits != nullptr));
+    return embed_host(
+        ctx, src.n, ctx->chunk, [&](int i, int m, hipStream_t s) -> int { return src.up(i, m, s); },
+        [&](int i, int m, float* d_emb, float* d_log) -> int { return se_run_windows(ctx, src, i, m, d_emb, d_log); }, out);
+}
+
 extern "C" int reid_embed_u8_dev(reid_ctx* ctx, const uint8_t* d_crops, int n, float* d_emb, float* d_logits) {
     ARG_CHECK(ctx && d_crops && d_emb && n >= 0);
     CTX_ENTER(ctx);
     const int nc = ctx->se18.num_class;
-    for (int i = 0; i < n; i += ctx->chunk) {
-        const int m = n - i < ctx->chunk ? n - i : ctx->chunk;
-        REID_TRY(seres18_run(ctx, d_crops + (size_t)i * IMG_H * IMG_W * 3, true, m, d_emb + (size_t)i * 512,
-                                 d_logits ? d_logits + (size_t)i * nc : nullptr));
-    }
-    return REID_OK;
+    return embed_dev_passes(n, ctx->chunk, [&](int i, int m) -> int {
+        return seres18_run(ctx, d_crops + (size_t)i * kCropElems, true, m, d_emb + (size_t)i * 512, d_logits ? d_logits + (size_t)i * nc : nullptr);
+    });
 }
 
 extern "C" int reid_embed_u8(reid_ctx* ctx, const uint8_t* crops, int n, float* emb, float* logits) {
     ARG_CHECK(ctx && crops && emb && n >= 0);
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
-    const int nc = ctx->se18.num_class;
     uint8_t* d_in;
-    float *d_emb, *d_log = nullptr;
-    const size_t crop_b = (size_t)IMG_H * IMG_W * 3;
-    REID_TRY(ctx_ws(ctx, "io.in", (size_t)n * crop_b, (void**)&d_in));
-    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 512 * 4, (void**)&d_emb));
-    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
-    REID_TRY(host_passes(
+    EmbedOut out{emb, logits, 512, ctx->se18.num_class};
+    REID_TRY(ctx_ws(ctx, "io.in", (size_t)n * kCropElems, (void**)&d_in));
+    REID_TRY(out.alloc(ctx, "io", n, 0, logits != nullptr));
+    return embed_host(
         ctx, n, ctx->chunk,
         [&](int i, int m, hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(d_in + (size_t)i * crop_b, crops + (size_t)i * crop_b, (size_t)m * crop_b, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(d_in + (size_t)i * kCropElems, crops + (size_t)i * kCropElems, (size_t)m * kCropElems, hipMemcpyHostToDevice, s));
             return REID_OK;
         },
-        [&](int i, int m) -> int {
-            return seres18_run(ctx, d_in + (size_t)i * crop_b, true, m, d_emb + (size_t)i * 512, d_log ? d_log + (size_t)i * nc : nullptr);
-        },
-        [&](int i, int m, hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(emb + (size_t)i * 512, d_emb + (size_t)i * 512, (size_t)m * 512 * 4, hipMemcpyDeviceToHost, s));
-            if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
-            return REID_OK;
-        }));
-    return ctx_fault_status(ctx);
+        [&](int i, int m, float* d_emb, float* d_log) -> int { return seres18_run(ctx, d_in + (size_t)i * kCropElems, true, m, d_emb, d_log); },
+        out);
 }
 
 extern "C" int reid_embed_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, float* d_emb, float* d_logits) {
     ARG_CHECK(ctx && d_x && d_emb && n >= 0);
     CTX_ENTER(ctx);
     const int nc = ctx->se18.num_class;
-    const size_t img = (size_t)IMG_H * IMG_W * 3;
-    for (int i = 0; i < n; i += ctx->chunk) {
-        const int m = n - i < ctx->chunk ? n - i : ctx->chunk;
-        float* nhwc;
-        REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * img * 4, (void**)&nhwc));
-        REID_TRY(launch_nchw_to_nhwc3(ctx, d_x + (size_t)i * img, m, IMG_H, IMG_W, nhwc));
-        REID_TRY(seres18_run(ctx, nhwc, false, m, d_emb + (size_t)i * 512, d_logits ? d_logits + (size_t)i * nc : nullptr));
-    }
-    return REID_OK;
+    return embed_dev_passes(n, ctx->chunk, [&](int i, int m) -> int {
+        return se_run_nchw(ctx, d_x + (size_t)i * kCropElems, m, d_emb + (size_t)i * 512, d_logits ? d_logits + (size_t)i * nc : nullptr);
+    });
 }
 
 extern "C" int reid_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, float* emb, float* logits) {
     ARG_CHECK(ctx && x && emb && n >= 0);
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
-    const int nc = ctx->se18.num_class;
-    const size_t img = (size_t)IMG_H * IMG_W * 3;
-    float *d_in, *d_emb, *d_log = nullptr;
-    REID_TRY(ctx_ws(ctx, "io.in", (size_t)n * img * 4, (void**)&d_in));
-    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 512 * 4, (void**)&d_emb));
-    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
-    REID_TRY(host_passes(
+    float* d_in;
+    EmbedOut out{emb, logits, 512, ctx->se18.num_class};
+    REID_TRY(ctx_ws(ctx, "io.in", (size_t)n * kCropElems * 4, (void**)&d_in));
+    REID_TRY(out.alloc(ctx, "io", n, 0, logits != nullptr));
+    return embed_host(
         ctx, n, ctx->chunk,
         [&](int i, int m, hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(d_in + (size_t)i * img, x + (size_t)i * img, (size_t)m * img * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(d_in + (size_t)i * kCropElems, x + (size_t)i * kCropElems, (size_t)m * kCropElems * 4, hipMemcpyHostToDevice, s));
             return REID_OK;
         },
-        [&](int i, int m) -> int {
-            float* nhwc;
-            REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * img * 4, (void**)&nhwc));
-            REID_TRY(launch_nchw_to_nhwc3(ctx, d_in + (size_t)i * img, m, IMG_H, IMG_W, nhwc));
-            return seres18_run(ctx, nhwc, false, m, d_emb + (size_t)i * 512, d_log ? d_log + (size_t)i * nc : nullptr);
-        },
-        [&](int i, int m, hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(emb + (size_t)i * 512, d_emb + (size_t)i * 512, (size_t)m * 512 * 4, hipMemcpyDeviceToHost, s));
-            if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
-            return REID_OK;
-        }));
-    return ctx_fault_status(ctx);
+        [&](int i, int m, float* d_emb, float* d_log) -> int { return se_run_nchw(ctx, d_in + (size_t)i * kCropElems, m, d_emb, d_log); }, out);
 }
 
-// Enqueue only (no synchronisation): upload of the ragged crops, device-side resize + normalise, forward.  `tag` names the
-// device buffers (the frame pipeline keeps one set per frame slot); offsets / hw must be pinned or outlive the stream's work.
 int embed_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
                          float** d_emb_out, float** d_log_out, bool side_copy) {
-    const int nc = ctx->se18.num_class;
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        ARG_CHECK(hw[2 * i] >= 1 && hw[2 * i + 1] >= 1 && offsets[i] >= 0);
-        const size_t end = (size_t)offsets[i] + (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
-        if (end > total) total = end;
-    }
-    uint8_t* d_pk;
-    char* d_meta;
-    float *d_emb, *d_log = nullptr;
-    const std::string t(tag);
-    REID_TRY(ctx_ws(ctx, (t + ".in").c_str(), total, (void**)&d_pk));
-    REID_TRY(ctx_ws(ctx, (t + ".meta").c_str(), (size_t)n * 16, (void**)&d_meta));
-    long long* d_off = (long long*)d_meta;
-    int* d_hw = (int*)(d_meta + (size_t)n * 8);
-    REID_TRY(ctx_ws(ctx, (t + ".emb").c_str(), (size_t)(n + 1) * 512 * 4, (void**)&d_emb));   // + 1: the padding row of reid_frame_gather
-    if (d_log_out) REID_TRY(ctx_ws(ctx, (t + ".logits").c_str(), (size_t)n * nc * 4 + 16, (void**)&d_log));
-    // side_copy (frame pipeline, pinned sources): the upload runs on a copy stream beside the previous frame's kernels
-    hipStream_t cs = ctx->stream;
-    if (side_copy) {
+    RaggedSrc src{packed, offsets, hw, n};
+    REID_TRY(src.check());
+    REID_TRY(src.alloc(ctx, tag));
+    EmbedOut out{nullptr, nullptr, 512, ctx->se18.num_class};
+    REID_TRY(out.alloc(ctx, tag, n, 1, d_log_out != nullptr));
+    if (side_copy) {   // frame pipeline, pinned sources
         if (!ctx->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         if (!ctx->copy_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->copy_ev, hipEventDisableTiming));
-        cs = ctx->copy_stream;
-    }
-    HIP_TRY(hipMemcpyAsync(d_pk, packed, total, hipMemcpyHostToDevice, cs));
-    if ((const char*)hw == (const char*)offsets + (size_t)n * 8) {
-        HIP_TRY(hipMemcpyAsync(d_meta, offsets, (size_t)n * 16, hipMemcpyHostToDevice, cs));
-    } else {
-        HIP_TRY(hipMemcpyAsync(d_off, offsets, (size_t)n * 8, hipMemcpyHostToDevice, cs));
-        HIP_TRY(hipMemcpyAsync(d_hw, hw, (size_t)n * 8, hipMemcpyHostToDevice, cs));
-    }
-    if (side_copy) {
-        HIP_TRY(hipEventRecord(ctx->copy_ev, cs));
+        REID_TRY(src.up(0, n, ctx->copy_stream));
+        HIP_TRY(hipEventRecord(ctx->copy_ev, ctx->copy_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->copy_ev, 0));
+    } else {
+        REID_TRY(src.up(0, n, ctx->stream));
     }
-    const size_t img = (size_t)IMG_H * IMG_W * 3;
-    for (int i = 0; i < n; i += ctx->chunk) {
-        const int m = n - i < ctx->chunk ? n - i : ctx->chunk;
-        float* nhwc;
-        REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * img * 4, (void**)&nhwc));
-        REID_TRY(launch_resize_norm(ctx, d_pk, d_off + i, d_hw + 2 * i, m, IMG_H, IMG_W, 0, nhwc));
-        REID_TRY(seres18_run(ctx, nhwc, false, m, d_emb + (size_t)i * 512, d_log ? d_log + (size_t)i * nc : nullptr));
-    }
-    *d_emb_out = d_emb;
-    if (d_log_out) *d_log_out = d_log;
+    REID_TRY(embed_dev_passes(n, ctx->chunk, [&](int i, int m) -> int {
+        return se_run_windows(ctx, src, i, m, out.d_emb + (size_t)i * 512, out.d_log ? out.d_log + (size_t)i * out.nc : nullptr);
+    }));
+    *d_emb_out = out.d_emb;
+    if (d_log_out) *d_log_out = out.d_log;
     return REID_OK;
 }
 
@@ -1417,60 +1477,9 @@ extern "C" int reid_embed_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const 
     ARG_CHECK(ctx && packed && offsets && hw && emb && n >= 0);
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
-    const int nc = ctx->se18.num_class;
-    float *d_emb, *d_log = nullptr;
-    if (n <= ctx->chunk || !ctx->host_pipeline) {
-        REID_TRY(embed_ragged_enqueue(ctx, "io", packed, offsets, hw, n, &d_emb, logits ? &d_log : nullptr, false));
-        HIP_TRY(hipMemcpyAsync(emb, d_emb, (size_t)n * 512 * 4, hipMemcpyDeviceToHost, ctx->stream));
-        if (logits) HIP_TRY(hipMemcpyAsync(logits, d_log, (size_t)n * nc * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return ctx_fault_status(ctx);
-    }
-    // several passes: the bytes a pass reads are the span [lowest offset, highest end) of its crops (the usual packing - crop after
-    // crop - makes the spans a partition of the buffer; any other layout copies some bytes twice, which is harmless)
-    const int passes = (n + ctx->chunk - 1) / ctx->chunk;
-    std::vector<size_t> lo(passes, (size_t)-1), hi(passes, 0);
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        ARG_CHECK(hw[2 * i] >= 1 && hw[2 * i + 1] >= 1 && offsets[i] >= 0);
-        const size_t b = (size_t)offsets[i], e = b + (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
-        const int k = i / ctx->chunk;
-        if (b < lo[k]) lo[k] = b;
-        if (e > hi[k]) hi[k] = e;
-        if (e > total) total = e;
-    }
-    uint8_t* d_pk;
-    char* d_meta;
-    REID_TRY(ctx_ws(ctx, "io.in", total, (void**)&d_pk));
-    REID_TRY(ctx_ws(ctx, "io.meta", (size_t)n * 16, (void**)&d_meta));
-    long long* d_off = (long long*)d_meta;
-    int* d_hw = (int*)(d_meta + (size_t)n * 8);
-    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)(n + 1) * 512 * 4, (void**)&d_emb));
-    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
-    const size_t img = (size_t)IMG_H * IMG_W * 3;
-    REID_TRY(host_passes(
-        ctx, n, ctx->chunk,
-        [&](int i, int m, hipStream_t s) -> int {
-            const int k = i / ctx->chunk;
-            if (i == 0) {
-                HIP_TRY(hipMemcpyAsync(d_off, offsets, (size_t)n * 8, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(d_hw, hw, (size_t)n * 8, hipMemcpyHostToDevice, s));
-            }
-            HIP_TRY(hipMemcpyAsync(d_pk + lo[k], packed + lo[k], hi[k] - lo[k], hipMemcpyHostToDevice, s));
-            return REID_OK;
-        },
-        [&](int i, int m) -> int {
-            float* nhwc;
-            REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * img * 4, (void**)&nhwc));
-            REID_TRY(launch_resize_norm(ctx, d_pk, d_off + i, d_hw + 2 * i, m, IMG_H, IMG_W, 0, nhwc));
-            return seres18_run(ctx, nhwc, false, m, d_emb + (size_t)i * 512, d_log ? d_log + (size_t)i * nc : nullptr);
-        },
-        [&](int i, int m, hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(emb + (size_t)i * 512, d_emb + (size_t)i * 512, (size_t)m * 512 * 4, hipMemcpyDeviceToHost, s));
-            if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
-            return REID_OK;
-        }));
-    return ctx_fault_status(ctx);
+    RaggedSrc src{packed, offsets, hw, n};
+    REID_TRY(src.check());
+    return se_embed_windows(ctx, src, emb, logits);
 }
 
 // Crops given as windows of ONE frame: DeepSort._get_features ([external] deep_sort.py) slices ori_img[y1:y2, x1:x2] per box
@@ -1481,42 +1490,9 @@ extern "C" int reid_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame, int fh, 
     ARG_CHECK(ctx && frame && boxes_xyxy && emb && fh >= 1 && fw >= 1 && n >= 0);
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
-    const int nc = ctx->se18.num_class;
-    std::vector<long long> off(n);
-    std::vector<int> hw(2 * n);
-    for (int i = 0; i < n; ++i) {
-        const int x1 = boxes_xyxy[4 * i], y1 = boxes_xyxy[4 * i + 1], x2 = boxes_xyxy[4 * i + 2], y2 = boxes_xyxy[4 * i + 3];
-        ARG_CHECK(x1 >= 0 && y1 >= 0 && x2 <= fw && y2 <= fh && x2 > x1 && y2 > y1);   // an empty slice fails in cv2.resize too
-        off[i] = ((long long)y1 * fw + x1) * 3;
-        hw[2 * i] = y2 - y1;
-        hw[2 * i + 1] = x2 - x1;
-    }
-    uint8_t* d_fr;
-    long long* d_off;
-    int* d_hw;
-    float *d_emb, *d_log = nullptr;
-    const size_t total = (size_t)fh * fw * 3;
-    REID_TRY(ctx_ws(ctx, "io.in", total, (void**)&d_fr));
-    REID_TRY(ctx_ws(ctx, "io.off", (size_t)n * 8, (void**)&d_off));
-    REID_TRY(ctx_ws(ctx, "io.hw", (size_t)n * 8, (void**)&d_hw));
-    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 512 * 4, (void**)&d_emb));
-    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
-    HIP_TRY(hipMemcpyAsync(d_fr, frame, total, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_hw, hw.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));   // off / hw are locals
-    const size_t img = (size_t)IMG_H * IMG_W * 3;
-    for (int i = 0; i < n; i += ctx->chunk) {
-        const int m = n - i < ctx->chunk ? n - i : ctx->chunk;
-        float* nhwc;
-        REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * img * 4, (void**)&nhwc));
-        REID_TRY(launch_resize_norm(ctx, d_fr, d_off + i, d_hw + 2 * i, m, IMG_H, IMG_W, fw, nhwc));
-        REID_TRY(seres18_run(ctx, nhwc, false, m, d_emb + (size_t)i * 512, d_log ? d_log + (size_t)i * nc : nullptr));
-    }
-    HIP_TRY(hipMemcpyAsync(emb, d_emb, (size_t)n * 512 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (logits) HIP_TRY(hipMemcpyAsync(logits, d_log, (size_t)n * nc * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ctx_fault_status(ctx);
+    RaggedSrc src{};
+    REID_TRY(src.frame(frame, fh, fw, boxes_xyxy, n));
+    return se_embed_windows(ctx, src, emb, logits);
 }
 
 // ------------------------------------------------------------------------------------------------ matching

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <stdio.h>
+#include <initializer_list>
 #include <string>
 #include <map>
 #include <tuple>
@@ -647,8 +648,79 @@ int host_passes(reid_ctx* ctx, int n, int pass, Up up, Run run, Down down) {
     }
     return rc;
 }
+
+// ---- The host entry points of both backbones (api.hip, swin.hip) are built from the pieces below: a source that knows how to bring items
+// [i, i + m) to the device (a dense array: a lambda in the entry; ragged crops or windows of one frame: RaggedSrc), the entry's own
+// "run one pass" lambda, and EmbedOut for the way back.  Definitions of the non-templates: api.hip.
+
+// Where the embeddings [n][dim] (and logits [n][nc], optional) of a call go on the host, and their device buffers.
+struct EmbedOut {
+    float *emb, *logits;   // host (the entry's arguments; logits may be null)
+    int dim, nc;
+    float *d_emb = nullptr, *d_log = nullptr;
+    // <tag>.emb for n + pad_rows rows and, when wanted, <tag>.logits (16 bytes of slack: the classifier GEMM stores whole vectors)
+    int alloc(reid_ctx* ctx, const char* tag, int n, int pad_rows, bool want_logits);
+    int down(int i, int m, hipStream_t s) const;   // queues the download of rows [i, i + m)
+};
+
+// n uint8 windows of one host buffer: packed crops (pitch 0: window i is hw[2i] x hw[2i + 1] pixels at byte offsets[i], its rows one after
+// the other) or windows of ONE frame `pitch` pixels wide (frame()).  On the device: <tag>.in and <tag>.meta = [offsets n x 8 | hw n x 8].
+struct RaggedSrc {
+    const uint8_t* src = nullptr;
+    const int64_t* offsets = nullptr;
+    const int32_t* hw = nullptr;
+    int n = 0;
+    int pitch = 0;
+    size_t total = 0;   // bytes of src that go up: the highest end of a crop, or the whole frame
+    uint8_t* d_src = nullptr;
+    long long* d_off = nullptr;
+    int* d_hw = nullptr;
+    std::vector<int64_t> win;   // a frame source's own [offsets | hw]: offsets / hw point into it, so a RaggedSrc is not copied
+    RaggedSrc() = default;
+    RaggedSrc(const uint8_t* packed, const int64_t* offsets_, const int32_t* hw_, int n_) : src(packed), offsets(offsets_), hw(hw_), n(n_) {}
+    RaggedSrc(const RaggedSrc&) = delete;
+    RaggedSrc& operator=(const RaggedSrc&) = delete;
+    int check();                // packed crops: every crop has pixels and a non-negative offset (REID_ERR_ARG); sets total
+    int frame(const uint8_t* frame_u8, int fh, int fw, const int32_t* boxes_xyxy, int n_boxes);   // windows_from_boxes into `win`
+    int alloc(reid_ctx* ctx, const char* tag);
+    // The bytes items [i, i + m) read: packed crops, the span [lowest offset, highest end) - crop after crop, the usual packing, makes
+    // the passes' spans a partition of the buffer, any other layout copies some bytes twice, which is harmless; a frame, all of it at
+    // i == 0 and nothing afterwards.  Behind them, at i == 0, the metadata of all n items, in one copy when hw directly follows offsets
+    // (Engine._pack_ragged's arrays need not; the frame pipeline's pinned block and a frame source do).
+    int up(int i, int m, hipStream_t s) const;
+};
+// boxes (x1, y1, x2, y2) inside an fh x fw frame -> byte offsets and (h, w) of the windows frame[y1:y2, x1:x2]; REID_ERR_ARG for an empty
+// or out-of-frame box
+int windows_from_boxes(const int32_t* boxes_xyxy, int n, int fh, int fw, int64_t* off, int32_t* hw);
+
+// host_passes, the embeddings (and logits) back through `out`, and the fault word.  run(i, m, d_emb_i, d_log_i) queues the kernels of
+// items [i, i + m) on ctx->stream; d_log_i is null when no logits are wanted.
+template <class Up, class Run>
+int embed_host(reid_ctx* ctx, int n, int pass, Up up, Run run, const EmbedOut& out) {
+    const int rc = host_passes(
+        ctx, n, pass, up,
+        [&](int i, int m) -> int { return run(i, m, out.d_emb + (size_t)i * out.dim, out.d_log ? out.d_log + (size_t)i * out.nc : nullptr); },
+        [&](int i, int m, hipStream_t s) -> int { return out.down(i, m, s); });
+    if (rc != REID_OK) {   // host_passes' one-pass branch returns at the first error: no copy from the caller's buffers, or from a
+        (void)hipStreamSynchronize(ctx->stream);   // frame source's own metadata, stays queued behind this call
+        return rc;
+    }
+    return ctx_fault_status(ctx);
+}
+// the passes of an entry whose operands are on the device already: run(i, m), nothing else
+template <class Run>
+int embed_dev_passes(int n, int pass, Run run) {
+    for (int i = 0; i < n; i += pass) REID_TRY(run(i, n - i < pass ? n - i : pass));
+    return REID_OK;
+}
+// RaggedSrc + the ResNet18-SE pass loop under `tag` with NO synchronisation and no download (reid_frame_submit, bank.hip: one buffer set
+// per frame slot).  side_copy: the upload runs on the context's copy stream, beside the previous frame's kernels.  offsets / hw must be
+// pinned or outlive the stream's work.  <tag>.emb has one row more than n: the padding row of reid_frame_gather.
 int embed_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
-                         float** d_emb_out, float** d_log_out, bool side_copy);   // api.hip: upload + resize + forward, no synchronisation
+                         float** d_emb_out, float** d_log_out, bool side_copy);
+// The library `file` in the directory this library lies in: opened (RTLD_NOW | RTLD_LOCAL), fns[k] = its symbol names[k].  A missing file
+// ("<what> <path> beside libreid_hip.so: <dlerror>") or symbol ("<path> lacks a / b", the handle closed again) is REID_ERR_STATE.
+int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns);
 void prof_begin(reid_ctx* ctx, int kind, double flops, double bytes);
 void prof_end(reid_ctx* ctx);
 

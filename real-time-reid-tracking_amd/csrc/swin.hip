@@ -9,7 +9,6 @@
 #include "reid_internal.h"
 #include "swin_v2.h"
 #include "swin_crops.h"
-#include <dlfcn.h>
 #include <mutex>
 #include <math.h>
 #include <string.h>
@@ -1222,26 +1221,10 @@ static int swin_v2_api(const SwinV2Api** out) {
     static SwinV2Api api;
     std::lock_guard<std::mutex> lk(m);
     if (!api.attn) {
-        Dl_info info;
-        std::string path = "libreid_hip_swin_v2.so";
-        if (dladdr((const void*)&swin_v2_api, &info) && info.dli_fname) {
-            const std::string self = info.dli_fname;
-            const size_t slash = self.rfind('/');
-            if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
-        }
-        void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) {
-            reid_set_error("Swin v2 needs %s beside libreid_hip.so: %s", path.c_str(), dlerror());
-            return REID_ERR_STATE;
-        }
-        auto a = (decltype(api.attn))dlsym(h, "swin_v2_window_attn_cos");
-        auto p = (decltype(api.post_norm))dlsym(h, "swin_v2_post_norm");
-        if (!a || !p) {
-            reid_set_error("%s lacks swin_v2_window_attn_cos / swin_v2_post_norm", path.c_str());
-            return REID_ERR_STATE;
-        }
-        api.post_norm = p;
-        api.attn = a;
+        void* f[2];
+        REID_TRY(open_beside_self("libreid_hip_swin_v2.so", "Swin v2 needs", {"swin_v2_window_attn_cos", "swin_v2_post_norm"}, f));
+        api.post_norm = (decltype(api.post_norm))f[1];
+        api.attn = (decltype(api.attn))f[0];
     }
     *out = &api;
     return REID_OK;
@@ -1255,24 +1238,9 @@ static int swin_crops_api(decltype(&swin_crops_front)* out) {
     static decltype(&swin_crops_front) front = nullptr;
     std::lock_guard<std::mutex> lk(m);
     if (!front) {
-        Dl_info info;
-        std::string path = "libreid_hip_swin_crops.so";
-        if (dladdr((const void*)&swin_crops_api, &info) && info.dli_fname) {
-            const std::string self = info.dli_fname;
-            const size_t slash = self.rfind('/');
-            if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
-        }
-        void* h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) {
-            reid_set_error("Swin from uint8 crops needs %s beside libreid_hip.so: %s", path.c_str(), dlerror());
-            return REID_ERR_STATE;
-        }
-        auto f = (decltype(front))dlsym(h, "swin_crops_front");
-        if (!f) {
-            reid_set_error("%s lacks swin_crops_front", path.c_str());
-            return REID_ERR_STATE;
-        }
-        front = f;
+        void* f;
+        REID_TRY(open_beside_self("libreid_hip_swin_crops.so", "Swin from uint8 crops needs", {"swin_crops_front"}, &f));
+        front = (decltype(front))f;
     }
     *out = front;
     return REID_OK;
@@ -2030,62 +1998,49 @@ extern "C" int reid_debug_swin_stage(reid_ctx* ctx, int stage, float* out, size_
     return REID_OK;
 }
 
-extern "C" int reid_swin_embed_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits) {
-    ARG_CHECK(ctx && d_x && d_emb && n >= 0 && h > 0 && w > 0 && h % 224 == 0 && w % 224 == 0);
-    CTX_ENTER(ctx);
-    const SwinWeights* swp = swin_find(ctx);
-    if (!swp || !swp->loaded) {
+// images per pass: ~13 MB of fp32 activations per 224x224 image, 13 GB at the cap.  Passes of 1024 instead of 256 images run
+// 8 % faster in the fp32-class mode (14.6 -> 15.7 k img/s): the stage 3-4 linears of a 256-image pass are 294-588 tiles for 512
+// block slots.  Results are bit-identical for every pass size (tools/swin_chunk_check.py).  REID_SWIN_CHUNK_MAX lowers the cap.
+static int swin_pass(const reid_ctx* ctx) { return ctx->chunk < ctx->swin_chunk_cap ? ctx->chunk : ctx->swin_chunk_cap; }
+
+static int swin_loaded(reid_ctx* ctx, const SwinWeights** sw) {
+    *sw = swin_find(ctx);
+    if (!*sw || !(*sw)->loaded) {
         reid_set_error("reid_swin_embed_*: call reid_swin_load first");
         return REID_ERR_STATE;
     }
-    const SwinWeights& sw = *swp;
-    // images per pass: ~13 MB of fp32 activations per 224x224 image, 13 GB at the cap.  Passes of 1024 instead of 256 images run
-    // 8 % faster in the fp32-class mode (14.6 -> 15.7 k img/s): the stage 3-4 linears of a 256-image pass are 294-588 tiles for 512
-    // block slots.  Results are bit-identical for every pass size (tools/swin_chunk_check.py).  REID_SWIN_CHUNK_MAX lowers the cap.
-    const int cap = ctx->swin_chunk_cap;
-    const int chunk = ctx->chunk < cap ? ctx->chunk : cap;
-    const size_t img = (size_t)3 * h * w;
-    for (int i = 0; i < n; i += chunk) {
-        const int m = n - i < chunk ? n - i : chunk;
-        REID_TRY(swin_forward(ctx, sw, d_x + (size_t)i * img, m, h, w, d_emb + (size_t)i * 96,
-                              d_logits ? d_logits + (size_t)i * sw.num_class : nullptr));
-    }
     return REID_OK;
+}
+
+extern "C" int reid_swin_embed_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits) {
+    ARG_CHECK(ctx && d_x && d_emb && n >= 0 && h > 0 && w > 0 && h % 224 == 0 && w % 224 == 0);
+    CTX_ENTER(ctx);
+    const SwinWeights* sw;
+    REID_TRY(swin_loaded(ctx, &sw));
+    const size_t img = (size_t)3 * h * w;
+    return embed_dev_passes(n, swin_pass(ctx), [&](int i, int m) -> int {
+        return swin_forward(ctx, *sw, d_x + (size_t)i * img, m, h, w, d_emb + (size_t)i * 96, d_logits ? d_logits + (size_t)i * sw->num_class : nullptr);
+    });
 }
 
 extern "C" int reid_swin_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits) {
     ARG_CHECK(ctx && x && emb && n >= 0 && h > 0 && w > 0 && h % 224 == 0 && w % 224 == 0);
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
-    const SwinWeights* swp = swin_find(ctx);
-    if (!swp || !swp->loaded) {
-        reid_set_error("reid_swin_embed_*: call reid_swin_load first");
-        return REID_ERR_STATE;
-    }
-    const SwinWeights& sw = *swp;
-    const int nc = sw.num_class;
+    const SwinWeights* sw;
+    REID_TRY(swin_loaded(ctx, &sw));
     const size_t img = (size_t)3 * h * w;
-    float *d_in, *d_emb, *d_log = nullptr;
+    float* d_in;
+    EmbedOut out{emb, logits, 96, sw->num_class};
     REID_TRY(ctx_ws(ctx, "io.in", (size_t)n * img * 4, (void**)&d_in));
-    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 512 * 4, (void**)&d_emb));
-    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
-    const int chunk = ctx->chunk < ctx->swin_chunk_cap ? ctx->chunk : ctx->swin_chunk_cap;   // = reid_swin_embed_f32_nchw_dev's passes
-    // host in -> host out: pass k + 1's images go up and pass k - 1's embeddings come down under pass k (host_passes, reid_internal.h)
-    REID_TRY(host_passes(
-        ctx, n, chunk,
+    REID_TRY(out.alloc(ctx, "io", n, 0, logits != nullptr));
+    return embed_host(
+        ctx, n, swin_pass(ctx),
         [&](int i, int m, hipStream_t s) -> int {
             HIP_TRY(hipMemcpyAsync(d_in + (size_t)i * img, x + (size_t)i * img, (size_t)m * img * 4, hipMemcpyHostToDevice, s));
             return REID_OK;
         },
-        [&](int i, int m) -> int {
-            return swin_forward(ctx, sw, d_in + (size_t)i * img, m, h, w, d_emb + (size_t)i * 96, d_log ? d_log + (size_t)i * nc : nullptr);
-        },
-        [&](int i, int m, hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(emb + (size_t)i * 96, d_emb + (size_t)i * 96, (size_t)m * 96 * 4, hipMemcpyDeviceToHost, s));
-            if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
-            return REID_OK;
-        }));
-    return ctx_fault_status(ctx);
+        [&](int i, int m, float* d_emb, float* d_log) -> int { return swin_forward(ctx, *sw, d_in + (size_t)i * img, m, h, w, d_emb, d_log); }, out);
 }
 
 // ---- uint8 crops in, embeddings out: the tracker's way of feeding a ReID model (Extractor.__call__, feature_extractor.py:48-53, and
@@ -2098,64 +2053,30 @@ static int swin_crops_args(int out_h, int out_w, const float** mean_std6) {
     return swin_crops_check(out_h, out_w, *mean_std6);
 }
 
+// the common end of the two crops entries, their arguments checked: fault word, weights, then the windows of `src` in passes
+static int swin_embed_windows(reid_ctx* ctx, RaggedSrc& src, int out_h, int out_w, const float* mean_std6, float* emb, float* logits) {
+    CTX_ENTER(ctx);
+    const SwinWeights* sw;
+    REID_TRY(swin_loaded(ctx, &sw));
+    if (src.n == 0) return REID_OK;
+    EmbedOut out{emb, logits, 96, sw->num_class};
+    REID_TRY(src.alloc(ctx, "io"));
+    REID_TRY(out.alloc(ctx, "io", src.n, 0, logits != nullptr));
+    return embed_host(
+        ctx, src.n, swin_pass(ctx), [&](int i, int m, hipStream_t s) -> int { return src.up(i, m, s); },
+        [&](int i, int m, float* d_emb, float* d_log) -> int {
+            return swin_forward_crops(ctx, *sw, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, out_h, out_w, src.pitch, mean_std6, d_emb, d_log);
+        },
+        out);
+}
+
 extern "C" int reid_swin_embed_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
                                          int out_w, const float* mean_std6, float* emb, float* logits) {
     ARG_CHECK(ctx && packed && offsets && hw && emb && n >= 0);
     REID_TRY(swin_crops_args(out_h, out_w, &mean_std6));
-    size_t total = 0;
-    for (int i = 0; i < n; ++i) {
-        ARG_CHECK(hw[2 * i] >= 1 && hw[2 * i + 1] >= 1 && offsets[i] >= 0);
-        const size_t e = (size_t)offsets[i] + (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
-        if (e > total) total = e;
-    }
-    CTX_ENTER(ctx);
-    const SwinWeights* swp = swin_find(ctx);
-    if (!swp || !swp->loaded) {
-        reid_set_error("reid_swin_embed_*: call reid_swin_load first");
-        return REID_ERR_STATE;
-    }
-    if (n == 0) return REID_OK;
-    const SwinWeights& sw = *swp;
-    const int nc = sw.num_class;
-    uint8_t* d_pk;
-    char* d_meta;
-    float *d_emb, *d_log = nullptr;
-    REID_TRY(ctx_ws(ctx, "io.in", total, (void**)&d_pk));
-    REID_TRY(ctx_ws(ctx, "io.meta", (size_t)n * 16, (void**)&d_meta));
-    long long* d_off = (long long*)d_meta;
-    int* d_hw = (int*)(d_meta + (size_t)n * 8);
-    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 96 * 4, (void**)&d_emb));
-    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
-    const int chunk = ctx->chunk < ctx->swin_chunk_cap ? ctx->chunk : ctx->swin_chunk_cap;   // = reid_swin_embed_f32_nchw's passes
-    // host in -> host out as reid_embed_ragged_u8: the bytes a pass reads are the span [lowest offset, highest end) of its crops (crop after
-    // crop, the usual packing, makes the spans a partition of the buffer); pass k + 1's span goes up and pass k - 1's embeddings come
-    // down under pass k's kernels (host_passes).  One pass, or host_pipeline = 0: one span, everything on the compute stream.
-    REID_TRY(host_passes(
-        ctx, n, chunk,
-        [&](int i, int m, hipStream_t s) -> int {
-            size_t lo = (size_t)-1, hi = 0;
-            for (int j = i; j < i + m; ++j) {
-                const size_t b = (size_t)offsets[j], e = b + (size_t)hw[2 * j] * hw[2 * j + 1] * 3;
-                if (b < lo) lo = b;
-                if (e > hi) hi = e;
-            }
-            if (i == 0) {
-                HIP_TRY(hipMemcpyAsync(d_off, offsets, (size_t)n * 8, hipMemcpyHostToDevice, s));
-                HIP_TRY(hipMemcpyAsync(d_hw, hw, (size_t)n * 8, hipMemcpyHostToDevice, s));
-            }
-            HIP_TRY(hipMemcpyAsync(d_pk + lo, packed + lo, hi - lo, hipMemcpyHostToDevice, s));
-            return REID_OK;
-        },
-        [&](int i, int m) -> int {
-            return swin_forward_crops(ctx, sw, d_pk, d_off + i, d_hw + 2 * i, m, out_h, out_w, 0, mean_std6, d_emb + (size_t)i * 96,
-                                      d_log ? d_log + (size_t)i * nc : nullptr);
-        },
-        [&](int i, int m, hipStream_t s) -> int {
-            HIP_TRY(hipMemcpyAsync(emb + (size_t)i * 96, d_emb + (size_t)i * 96, (size_t)m * 96 * 4, hipMemcpyDeviceToHost, s));
-            if (logits) HIP_TRY(hipMemcpyAsync(logits + (size_t)i * nc, d_log + (size_t)i * nc, (size_t)m * nc * 4, hipMemcpyDeviceToHost, s));
-            return REID_OK;
-        }));
-    return ctx_fault_status(ctx);
+    RaggedSrc src{packed, offsets, hw, n};
+    REID_TRY(src.check());
+    return swin_embed_windows(ctx, src, out_h, out_w, mean_std6, emb, logits);
 }
 
 // Windows frame[y1:y2, x1:x2] of ONE frame, as reid_embed_frame_u8: the frame goes up once, every window is resized straight out of it
@@ -2164,46 +2085,7 @@ extern "C" int reid_swin_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame, int
                                         int out_w, const float* mean_std6, float* emb, float* logits) {
     ARG_CHECK(ctx && frame && boxes_xyxy && emb && fh >= 1 && fw >= 1 && n >= 0);
     REID_TRY(swin_crops_args(out_h, out_w, &mean_std6));
-    std::vector<long long> off(n);
-    std::vector<int> hw(2 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        const int x1 = boxes_xyxy[4 * i], y1 = boxes_xyxy[4 * i + 1], x2 = boxes_xyxy[4 * i + 2], y2 = boxes_xyxy[4 * i + 3];
-        ARG_CHECK(x1 >= 0 && y1 >= 0 && x2 <= fw && y2 <= fh && x2 > x1 && y2 > y1);   // an empty slice fails in cv2.resize too
-        off[i] = ((long long)y1 * fw + x1) * 3;
-        hw[2 * i] = y2 - y1;
-        hw[2 * i + 1] = x2 - x1;
-    }
-    CTX_ENTER(ctx);
-    const SwinWeights* swp = swin_find(ctx);
-    if (!swp || !swp->loaded) {
-        reid_set_error("reid_swin_embed_*: call reid_swin_load first");
-        return REID_ERR_STATE;
-    }
-    if (n == 0) return REID_OK;
-    const SwinWeights& sw = *swp;
-    const int nc = sw.num_class;
-    uint8_t* d_fr;
-    long long* d_off;
-    int* d_hw;
-    float *d_emb, *d_log = nullptr;
-    const size_t total = (size_t)fh * fw * 3;
-    REID_TRY(ctx_ws(ctx, "io.in", total, (void**)&d_fr));
-    REID_TRY(ctx_ws(ctx, "io.off", (size_t)n * 8, (void**)&d_off));
-    REID_TRY(ctx_ws(ctx, "io.hw", (size_t)n * 8, (void**)&d_hw));
-    REID_TRY(ctx_ws(ctx, "io.emb", (size_t)n * 96 * 4, (void**)&d_emb));
-    if (logits) REID_TRY(ctx_ws(ctx, "io.logits", (size_t)n * nc * 4 + 16, (void**)&d_log));
-    HIP_TRY(hipMemcpyAsync(d_fr, frame, total, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_off, off.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_hw, hw.data(), (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));   // off / hw are locals
-    const int chunk = ctx->chunk < ctx->swin_chunk_cap ? ctx->chunk : ctx->swin_chunk_cap;
-    for (int i = 0; i < n; i += chunk) {
-        const int m = n - i < chunk ? n - i : chunk;
-        REID_TRY(swin_forward_crops(ctx, sw, d_fr, d_off + i, d_hw + 2 * i, m, out_h, out_w, fw, mean_std6, d_emb + (size_t)i * 96,
-                                    d_log ? d_log + (size_t)i * nc : nullptr));
-    }
-    HIP_TRY(hipMemcpyAsync(emb, d_emb, (size_t)n * 96 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (logits) HIP_TRY(hipMemcpyAsync(logits, d_log, (size_t)n * nc * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ctx_fault_status(ctx);
+    RaggedSrc src{};
+    REID_TRY(src.frame(frame, fh, fw, boxes_xyxy, n));
+    return swin_embed_windows(ctx, src, out_h, out_w, mean_std6, emb, logits);
 }

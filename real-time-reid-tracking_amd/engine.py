@@ -195,10 +195,9 @@ class Engine:
         if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] % 224 or x.shape[3] % 224:
             raise ValueError("swin_embed_f32_nchw expects float32[n,3,224k,224m], got %s" % (x.shape,))
         n = x.shape[0]
-        emb = np.empty((n, self.swin_dim), np.float32)
-        lg = np.empty((n, self.swin_num_class), np.float32) if logits else None
+        emb, lg = self._outs(n, logits, self.swin_dim, self.swin_num_class)
         check(self.lib.reid_swin_embed_f32_nchw(self.h, _ptr(x), n, x.shape[2], x.shape[3], _ptr(emb), _ptr(lg)))
-        return (emb, lg) if logits else emb
+        return self._ret(emb, lg, logits)
 
     def swin_embed_dev(self, d_x, n, h, w, d_emb, d_logits=None):
         check(self.lib.reid_swin_embed_f32_nchw_dev(self.h, C.c_void_p(d_x), int(n), int(h), int(w), C.c_void_p(d_emb),
@@ -227,10 +226,9 @@ class Engine:
         h, w, ms = self._swin_crop_args(size, mean_std)
         n = len(crops)
         src, offs, hw, _keep = self._pack_ragged(crops)
-        emb = np.empty((n, self.swin_dim), np.float32)
-        lg = np.empty((n, self.swin_num_class), np.float32) if logits else None
+        emb, lg = self._outs(n, logits, self.swin_dim, self.swin_num_class)
         check(self.lib.reid_swin_embed_ragged_u8(self.h, src, _ptr(offs), _ptr(hw), n, h, w, _ptr(ms), _ptr(emb), _ptr(lg)))
-        return (emb, lg) if logits else emb
+        return self._ret(emb, lg, logits)
 
     def swin_embed_frame_u8(self, frame, boxes_xyxy, size=(224, 224), mean_std=None, logits=False):
         """uint8[H,W,3] frame + int boxes [n,4] (x1,y1,x2,y2; crop = frame[y1:y2, x1:x2]) -> float32[n,96] (and logits); ``size`` and
@@ -241,17 +239,21 @@ class Engine:
             raise ValueError("frame must be uint8[H,W,3], got %s" % (frame.shape,))
         boxes = np.ascontiguousarray(boxes_xyxy, dtype=np.int32).reshape(-1, 4)
         n = boxes.shape[0]
-        emb = np.empty((n, self.swin_dim), np.float32)
-        lg = np.empty((n, self.swin_num_class), np.float32) if logits else None
+        emb, lg = self._outs(n, logits, self.swin_dim, self.swin_num_class)
         check(self.lib.reid_swin_embed_frame_u8(self.h, _ptr(frame), frame.shape[0], frame.shape[1], _ptr(boxes), n, h, w, _ptr(ms), _ptr(emb),
                                                 _ptr(lg)))
-        return (emb, lg) if logits else emb
+        return self._ret(emb, lg, logits)
 
     # ---- embedding
-    def _outs(self, n, want_logits):
-        emb = np.empty((n, self.embed_dim), np.float32)
-        logits = np.empty((n, self.num_class), np.float32) if want_logits else None
+    def _outs(self, n, want_logits, dim=None, num_class=None):
+        """Host arrays an embed call fills: emb[n, dim] and logits[n, num_class] or None (default sizes: the ResNet18-SE family's)."""
+        emb = np.empty((n, self.embed_dim if dim is None else dim), np.float32)
+        logits = np.empty((n, self.num_class if num_class is None else num_class), np.float32) if want_logits else None
         return emb, logits
+
+    @staticmethod
+    def _ret(emb, lg, logits):
+        return (emb, lg) if logits else emb
 
     def embed_u8(self, crops, logits=False):
         """uint8[n,256,128,3] -> float32[n,512] (and logits[n,num_class])."""
@@ -260,7 +262,7 @@ class Engine:
             raise ValueError("embed_u8 expects uint8[n,%d,%d,3], got %s" % (IMG_H, IMG_W, crops.shape))
         emb, lg = self._outs(crops.shape[0], logits)
         check(self.lib.reid_embed_u8(self.h, _ptr(crops), crops.shape[0], _ptr(emb), _ptr(lg)))
-        return (emb, lg) if logits else emb
+        return self._ret(emb, lg, logits)
 
     @staticmethod
     def _pack_ragged(crops):
@@ -298,7 +300,7 @@ class Engine:
         src, offs, hw, _keep = self._pack_ragged(crops)
         emb, lg = self._outs(n, logits)
         check(self.lib.reid_embed_ragged_u8(self.h, src, _ptr(offs), _ptr(hw), n, _ptr(emb), _ptr(lg)))
-        return (emb, lg) if logits else emb
+        return self._ret(emb, lg, logits)
 
     # ---- frame pipeline (csrc/bank.hip): submit (asynchronous) / cost (the frame's one synchronisation) / update (asynchronous)
     def pinned(self, nbytes):
@@ -440,7 +442,7 @@ class Engine:
         emb, lg = self._outs(n, logits)
         check(self.lib.reid_embed_frame_u8(self.h, _ptr(frame), frame.shape[0], frame.shape[1], _ptr(boxes), n, _ptr(emb),
                                            _ptr(lg)))
-        return (emb, lg) if logits else emb
+        return self._ret(emb, lg, logits)
 
     def embed_f32_nchw(self, x, logits=False):
         x = _f32(x)
@@ -448,7 +450,7 @@ class Engine:
             raise ValueError("embed_f32_nchw expects float32[n,3,%d,%d], got %s" % (IMG_H, IMG_W, x.shape))
         emb, lg = self._outs(x.shape[0], logits)
         check(self.lib.reid_embed_f32_nchw(self.h, _ptr(x), x.shape[0], _ptr(emb), _ptr(lg)))
-        return (emb, lg) if logits else emb
+        return self._ret(emb, lg, logits)
 
     def embed_f32_nchw_dev(self, d_x, n, d_emb, d_logits=None):
         check(self.lib.reid_embed_f32_nchw_dev(self.h, C.c_void_p(d_x), int(n), C.c_void_p(d_emb), C.c_void_p(d_logits or 0)))
