@@ -52,6 +52,27 @@ int reid_debug_conv_layer(reid_ctx* ctx, const float* x, int n, int h, int w, in
                           int pad, const float* scale, const float* shift, const float* residual, int relu, int relu_from, int pack_from,
                           int want_stats, const float* a_scale, const float* a_shift, int a_relu, float* out, uint16_t* packed,
                           float* stats, int* packed_written);
+/* One convolution of the fp16-storage trunk through conv_gemm16(A16_IM2COL, ...), the call the forward makes (correctness harness,
+ * tests/test_gpu_conv_f16.py).  Operands are raw f16 bits, so the caller owns the exact values: x [n][h][w][cin], wgt [cout][r][r][cin],
+ * residual [m][cout] (may be null), m = n ho wo; scale / shift fp32 [cout] (both or neither).  out = ReLU (if relu) of conv * scale + shift
+ * (+ residual) as raw f16 bits [m][cout]; want_stats: per-128-row column sums [m / 128][cout][2] (sum, sum of squares) of the fp32 values
+ * before the f16 rounding.  The context's switches (f16_halo, f16_cfg, f16_split_k, ...) pick the kernel as in the forward; the context
+ * must hold a loaded ResNet checkpoint (its zero page).  Every output the launch leaves alone reads as NaN (0xffff).  Arguments the
+ * launchers refuse (m % 128, cin % 32, cout % 64 != 0) return REID_ERR_ARG with nothing launched; else the context's fault status.
+ * *form names the launch that was made (reid_ctx::conv_form, written by the launchers on the host; 0 = none):
+ *   launch_gemm_f16 (implicit GEMM):   the tile configuration BN * 1000 + BK * 10 + NST: 64642, 64323, 128323, 128642, 256324, 256642;
+ *   launch_conv3x3_f16 (LDS halo):     BN * 10 + split K: 641, 642, 644 (64-wide tiles), 1281 (128-wide; 1282 .. 1284 with f16_wide_splitk);
+ *   launch_conv3x3_c64_f16:            1 plain, 2 with the fused SE tail. */
+int reid_debug_conv_layer_f16(reid_ctx* ctx, const uint16_t* x, int n, int h, int w, int cin, const uint16_t* wgt, int cout, int r, int stride,
+                              int pad, const float* scale, const float* shift, const uint16_t* residual, int relu, int want_stats,
+                              uint16_t* out, float* stats, int* form);
+/* launch_conv3x3_c64_f16 (layer 1: 3x3, 64 -> 64 channels on 64 x 32 maps) on raw f16 bits: x / residual (may be null) / out [n][64][32][64],
+ * w_folded [64][576] with the BN scale already folded in (f16(w * scale), what scale_rows_f16_kernel makes), shift fp32 [64] (may be null).
+ * se_w1 / se_w2t fp32 [8][64] set: conv2 with the fused SE tail, out = relu(gate y + residual), y = relu(conv + shift + residual) (needs
+ * shift and residual).  Both null: the plain launch on the same operands; stats (may be null) [n][64][2] then holds the per-image sums.
+ * Unwritten outputs read as NaN (0xffff); returns the context's fault status; *form (may be null) as above. */
+int reid_debug_conv_c64_se(reid_ctx* ctx, int n, const uint16_t* x, const uint16_t* w_folded, const float* shift, const uint16_t* residual,
+                           int relu, const float* se_w1, const float* se_w2t, uint16_t* out, float* stats, int* form);
 /* The kernels that finish a residual block and the neck (correctness harness, tests/test_gpu_tail.py), each through the launcher the
  * forward calls, on host operands.  stats [n][tiles][c][2] (per-group sum, sum of squares), activations NHWC [n][hw][c]; f16 operands
  * and results are raw f16 bits.  Every output the launch leaves alone reads as NaN (0xffff); each call returns the context's fault status.

@@ -303,6 +303,7 @@ int launch_conv3x3_c64_f16(reid_ctx* ctx, const f16* in, int n, const f16* w_sca
     else if (shift) hipLaunchKernelGGL((conv3x3_c64_f16_kernel<false, true>), dim3(grid), dim3(512), 0, ctx->stream, p);
     else hipLaunchKernelGGL((conv3x3_c64_f16_kernel<false, false>), dim3(grid), dim3(512), 0, ctx->stream, p);
     prof_end(ctx);
+    ctx->conv_form = se_w1 ? 2 : 1;
     LAUNCH_CHECK();
     return REID_OK;
 }

@@ -862,6 +862,7 @@ int launch_geom(reid_ctx* ctx, const Gemm16Params& p0) {
             if (pair) hipLaunchKernelGGL((conv3x3_f16_kernel<TW, IMGS, 128, LW, SPLIT, true>), dim3(tiles128), dim3(threads), 0, ctx->stream, p);
         }
         if (!pair) hipLaunchKernelGGL((conv3x3_f16_kernel<TW, IMGS, 128, LW, SPLIT>), dim3(tiles128), dim3(threads), 0, ctx->stream, p);
+        ctx->conv_form = 1281;
     } else {
         // Few output tiles (a tracking frame): the launch leaves CUs idle and its K loop is latency-bound at ~0.65 us per (chunk, tap)
         // tile of a 64-wide block and ~1.3 us of a 128-wide one, so its length is what the launch costs.  Split the input channels
@@ -893,6 +894,7 @@ int launch_geom(reid_ctx* ctx, const Gemm16Params& p0) {
         }
         const int tiles = best_bn == 128 ? tiles128 : tiles64;
         REID_TRY(splitk(tiles, best_bn, best_sk));
+        ctx->conv_form = best_bn * 10 + best_sk;
         if (best_bn == 128) {
             if constexpr (CAN_PAIR) {
                 if (pair) hipLaunchKernelGGL((conv3x3_f16_kernel<TW, IMGS, 128, LW, SPLIT, true>), dim3(tiles * best_sk), dim3(threads), 0, ctx->stream, p);

@@ -698,6 +698,81 @@ extern "C" int reid_debug_gem_neck_fused(reid_ctx* ctx, int n, int hw, int c, in
     return ctx_fault_status(ctx);
 }
 
+// ------------------------------------------------------------------------------------------------ fp16-storage convolutions (tests/test_gpu_conv_f16.py)
+// One convolution of the fp16-storage trunk through conv_gemm16(A16_IM2COL, ...) - the call seres18_forward_f16 makes - on raw f16 bits, so
+// that the caller owns the exact operands.  The context's switches pick the kernel; what conv_gemm16's launchers refuse comes back as their
+// REID_ERR_ARG, nothing launched.  *form = reid_ctx::conv_form of the launch (0: none).
+extern "C" int reid_debug_conv_layer_f16(reid_ctx* ctx, const uint16_t* x, int n, int h, int w, int cin, const uint16_t* wgt, int cout, int r,
+                                         int stride, int pad, const float* scale, const float* shift, const uint16_t* residual, int relu,
+                                         int want_stats, uint16_t* out, float* stats, int* form) {
+    ARG_CHECK(ctx && x && wgt && out && form && n >= 1 && h >= 1 && w >= 1 && cin >= 1 && cout >= 1 && r >= 1 && stride >= 1 && pad >= 0);
+    ARG_CHECK((scale == nullptr) == (shift == nullptr) && (!want_stats || stats) && ctx->se18.zero_page);
+    CTX_ENTER(ctx);
+    typedef _Float16 f16;
+    const int ho = (h + 2 * pad - r) / stride + 1, wo = (w + 2 * pad - r) / stride + 1;
+    ARG_CHECK(ho >= 1 && wo >= 1 && (long long)n * ho * wo < (1LL << 31) / cout && (long long)n * h * w < (1LL << 31) / cin);
+    const size_t m = (size_t)n * ho * wo, nout = m * cout, nstats = (m + 127) / 128 * cout * 2;
+    uint16_t *dx, *dw, *dres, *dout;
+    float *dsc, *dsh, *dstats = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgh.x", x, (size_t)n * h * w * cin, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgh.w", wgt, (size_t)cout * r * r * cin, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgh.scale", scale, (size_t)cout, &dsc));
+    REID_TRY(dbg_upload(ctx, "dbgh.shift", shift, (size_t)cout, &dsh));
+    REID_TRY(dbg_upload(ctx, "dbgh.res", residual, nout, &dres));
+    REID_TRY(dbg_output(ctx, "dbgh.out", nout, &dout));
+    if (want_stats) REID_TRY(dbg_output(ctx, "dbgh.stats", nstats, &dstats));
+    ctx->conv_form = 0;
+    *form = 0;
+    const int st = conv_gemm16(ctx, A16_IM2COL, (const f16*)dx, n, h, w, cin, (const f16*)dw, cout, r, r, stride, pad, r * r * cin, dsc, dsh,
+                               (const f16*)dres, relu, dstats, (f16*)dout);
+    *form = ctx->conv_form;
+    if (st != REID_OK) {   // refused: the uploads above still read the caller's arrays
+        (void)hipStreamSynchronize(ctx->stream);
+        return st;
+    }
+    REID_TRY(dbg_download(ctx, out, dout, nout));
+    if (want_stats) REID_TRY(dbg_download(ctx, stats, dstats, (size_t)(m / 128) * cout * 2));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// launch_conv3x3_c64_f16 on raw f16 bits: x / residual [n][64][32][64], w_folded [64][576] (the BN scale already folded in, as
+// scale_rows_f16_kernel leaves it), fp32 shift [64].  With se_w1 / se_w2t [8][64] the launch is conv2 with the fused SE tail (`out` = the
+// block output); with both null it is the plain launch, which also returns the per-image stats [n][64][2] when asked.
+extern "C" int reid_debug_conv_c64_se(reid_ctx* ctx, int n, const uint16_t* x, const uint16_t* w_folded, const float* shift,
+                                      const uint16_t* residual, int relu, const float* se_w1, const float* se_w2t, uint16_t* out, float* stats,
+                                      int* form) {
+    ARG_CHECK(ctx && x && w_folded && out && n >= 1 && n <= 4096 && (se_w1 == nullptr) == (se_w2t == nullptr));
+    CTX_ENTER(ctx);
+    typedef _Float16 f16;
+    const size_t nact = (size_t)n * 64 * 32 * 64, nstats = (size_t)n * 64 * 2;
+    uint16_t *dx, *dw, *dres, *dout, *zp;
+    float *dsh, *dw1, *dw2, *dstats = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgh.x", x, nact, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgh.w", w_folded, (size_t)64 * 576, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgh.shift", shift, (size_t)64, &dsh));
+    REID_TRY(dbg_upload(ctx, "dbgh.res", residual, nact, &dres));
+    REID_TRY(dbg_upload(ctx, "dbgh.w1", se_w1, (size_t)8 * 64, &dw1));
+    REID_TRY(dbg_upload(ctx, "dbgh.w2", se_w2t, (size_t)8 * 64, &dw2));
+    REID_TRY(dbg_output(ctx, "dbgh.out", nact, &dout));
+    if (stats) REID_TRY(dbg_output(ctx, "dbgh.stats", nstats, &dstats));
+    REID_TRY(ctx_ws(ctx, "dbg64.zp", 256, (void**)&zp));
+    HIP_TRY(hipMemsetAsync(zp, 0, 256, ctx->stream));
+    ctx->conv_form = 0;
+    if (form) *form = 0;
+    const int st = launch_conv3x3_c64_f16(ctx, (const f16*)dx, n, (const f16*)dw, dsh, (const f16*)dres, relu, dstats, (f16*)dout, (const f16*)zp,
+                                          dw1, dw2);
+    if (form) *form = ctx->conv_form;
+    if (st != REID_OK) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return st;
+    }
+    REID_TRY(dbg_download(ctx, out, dout, nact));
+    if (stats) REID_TRY(dbg_download(ctx, stats, dstats, nstats));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 // Timing experiments on the fused pair of linears: bit 0 = no weight refills after the first two steps, bit 1 = no block barriers.
 // The results are WRONG while a bit is set (which is why this lives here and not behind an environment variable of the library).
 extern "C" int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits) {

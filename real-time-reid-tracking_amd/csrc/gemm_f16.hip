@@ -742,6 +742,7 @@ int launch_cfg(reid_ctx* ctx, const Gemm16Params& p) {
     }
     hipLaunchKernelGGL((gemm_f16_kernel<AMODE, BN, BK, NST, STAG, LIN>), dim3(((p.M + 255) / 256) * (p.N / BN) * (p.par4 ? 4 : 1)), dim3(512), 0,
                        ctx->stream, p);
+    ctx->conv_form = STAG * 1000000 + BN * 1000 + BK * 10 + NST;   // the cfg code of launch_any
     LAUNCH_CHECK();
     return REID_OK;
 }

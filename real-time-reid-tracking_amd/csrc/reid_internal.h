@@ -482,6 +482,10 @@ struct reid_ctx {
     const char* frame_out[2] = {nullptr, nullptr};
     float* stage_ptr[11] = {nullptr};
     unsigned long long* conv_diag = nullptr;   // experiments (debug.hip): stamps of the loader-wave conv kernel
+    // Which launch the last f16 convolution launcher made, written on the host only (harnesses read it, include/reid_hip_debug.h:
+    // reid_debug_conv_layer_f16).  launch_gemm_f16: the tile configuration BN*1000 + BK*10 + NST; launch_conv3x3_f16: BN*10 + split K;
+    // launch_conv3x3_c64_f16: 1 plain, 2 with the fused SE tail.  No kernel sees it and no launch depends on it.
+    int conv_form = 0;
     // precision 2 guards (include/reid_hip.h, reid_ctx_set_precision): the first conv / linear weight of the loaded checkpoint that
     // cannot be split ([wh 2^11 | wh | wl'] needs |w| 2^11 < 65504), empty when all can ...
     std::string split_bad_se18, split_bad_swin;

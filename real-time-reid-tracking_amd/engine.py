@@ -521,6 +521,50 @@ class Engine:
             _ptr(pk), _ptr(st), C.byref(written)))
         return out, (pk if written.value else None), st
 
+    def debug_conv_layer_f16(self, x, w, stride=1, pad=0, scale=None, shift=None, residual=None, relu=False, stats=False):
+        """One convolution of the fp16-storage trunk through conv_gemm16, the forward's call (libreid_hip_debug.so
+        reid_debug_conv_layer_f16).  x [n,h,w,cin], w [cout,r,r,cin], residual [n,ho,wo,cout]: float16 arrays (or their uint16 bits),
+        handed over bit for bit.  Returns (out [n,ho,wo,cout] float16, stats [m / 128, cout, 2] fp32 or None, form): form names the
+        launch that was made (include/reid_hip_debug.h).  What the launch does not write reads as NaN."""
+        bits = lambda a: None if a is None else np.ascontiguousarray(a).view(np.uint16)
+        xb, wb, rb = bits(x), bits(w), bits(residual)
+        n, h, ww, cin = xb.shape
+        cout, r, s, wc = wb.shape
+        if r != s or wc != cin:
+            raise ValueError("debug_conv_layer_f16 expects w[cout, r, r, cin] matching x")
+        ho, wo = (h + 2 * pad - r) // stride + 1, (ww + 2 * pad - r) // stride + 1
+        if rb is not None and rb.size != n * ho * wo * cout:
+            raise ValueError("debug_conv_layer_f16: residual must be [n, ho, wo, cout]")
+        out = np.empty((n, ho, wo, cout), np.uint16)
+        st = np.empty((n * ho * wo // 128, cout, 2), np.float32) if stats else None
+        sc, sh = (None if a is None else _f32(a) for a in (scale, shift))
+        form = C.c_int(0)
+        check(_ffi.debug_lib().reid_debug_conv_layer_f16(
+            self.h, _ptr(xb), C.c_int(n), C.c_int(h), C.c_int(ww), C.c_int(cin), _ptr(wb), C.c_int(cout), C.c_int(r), C.c_int(stride),
+            C.c_int(pad), _ptr(sc), _ptr(sh), _ptr(rb), C.c_int(int(bool(relu))), C.c_int(int(bool(stats))), _ptr(out), _ptr(st),
+            C.byref(form)))
+        return out.view(np.float16), st, form.value
+
+    def debug_conv_c64_se(self, x, w_folded, shift=None, residual=None, relu=False, se_w1=None, se_w2t=None, stats=False):
+        """The layer-1 kernel (conv3x3_c64_f16.hip) on raw operands (libreid_hip_debug.so reid_debug_conv_c64_se): x / residual
+        [n,64,32,64] and w_folded [64,576] float16 (or uint16 bits), shift [64] fp32; se_w1 / se_w2t [8,64] fp32 ask for the fused SE
+        tail.  Returns (out [n,64,32,64] float16, stats [n,64,2] or None, form)."""
+        bits = lambda a: None if a is None else np.ascontiguousarray(a).view(np.uint16)
+        xb, wb, rb = bits(x), bits(w_folded), bits(residual)
+        n = xb.shape[0]
+        if xb.shape[1:] != (64, 32, 64) or wb.size != 64 * 576 or (rb is not None and rb.shape != xb.shape):
+            raise ValueError("debug_conv_c64_se expects x / residual [n, 64, 32, 64] and w_folded [64, 576]")
+        out = np.empty(xb.shape, np.uint16)
+        st = np.empty((n, 64, 2), np.float32) if stats else None
+        sh, w1, w2 = (None if a is None else _f32(a) for a in (shift, se_w1, se_w2t))
+        if (sh is not None and sh.size != 64) or any(a is not None and a.size != 512 for a in (w1, w2)):
+            raise ValueError("debug_conv_c64_se expects shift [64] and se_w1 / se_w2t [8, 64]")
+        form = C.c_int(0)
+        check(_ffi.debug_lib().reid_debug_conv_c64_se(
+            self.h, C.c_int(n), _ptr(xb), _ptr(wb), _ptr(sh), _ptr(rb), C.c_int(int(bool(relu))), _ptr(w1), _ptr(w2), _ptr(out), _ptr(st),
+            C.byref(form)))
+        return out.view(np.float16), st, form.value
+
     def debug_norm_finish(self, form, x, stats, in_gamma, in_beta, bn_scale=None, bn_shift=None, hw=None):
         """The IBN finish of conv1 through the forward's launcher (libreid_hip_debug.so reid_debug_norm_finish).  x [n, hw, c] (fp32,
         or uint16 f16 bits for forms 4 and 5) or None for form 0; stats [n, tiles, c, 2]; in_gamma / in_beta [half].  Returns
