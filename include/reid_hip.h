@@ -262,9 +262,21 @@ int reid_bank_cost_dev(reid_ctx* ctx, reid_bank* bank, const int32_t* slots, int
  * cost (asynchronous): appearance cost as reid_bank_cost over track slots[t] (bank NULL: skipped), DIoU cost as
  *   reid_diou_cost over tlwh boxes tracks_t4[t] / dets_m4[m] (NULL: skipped), embeddings when want_emb != 0.  The full
  *   t x m matrices serve every subset the matching cascade asks for.
- * fetch (waits for the slot's cost stage only): emb fp32[m][512], cost_tm fp32[t][m], iou_tm fp64[t][m]; NULL = not wanted.
- * update (asynchronous): partial_fit with row rows[i] of the slot's embeddings appended to track slots[i]. */
+ * fetch (waits for the slot's cost stage only): emb fp32[m][d], cost_tm fp32[t][m], iou_tm fp64[t][m]; NULL = not wanted.
+ * update (asynchronous): partial_fit with row rows[i] of the slot's embeddings appended to track slots[i].
+ * A slot remembers the width d of its embeddings - 512 after reid_frame_submit, the loaded Swin's embed_dim (96) after
+ * reid_frame_submit_swin - and cost / fetch / update work at that width: a bank of another width is REID_ERR_ARG naming both. */
 int reid_frame_submit(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m);
+/* submit for the reference's swin_transformer tracker model (modification_tracking/models/__init__.py:80, reid_model_factory.py:9; the
+ * frame's crops as Extractor.__call__ gets them from DeepSort._get_features, feature_extractor.py:31-53): as reid_frame_submit -
+ * asynchronous, the same slot state, uploads and stream order - with the forward of reid_swin_embed_ragged_u8 on the loaded v1 / v2
+ * weights in the context's precision, in passes of min(chunk, the Swin pass cap) crops.  out_h, out_w (multiples of 224) and mean_std6
+ * (NULL = ImageNet) as there; mean_std6 is read before the call returns.  reid_ctx_set_side_index applies as to the other Swin entries.
+ * The slot's cost stage then runs bank_cost96_kernel of libreid_hip_bank96.so, which must lie beside this library like
+ * libreid_hip_swin_crops.so.  Refused before anything is queued or the slot is touched: no Swin weights or a missing side library
+ * (REID_ERR_STATE, naming the file), a bad size or mean_std6 (REID_ERR_ARG). */
+int reid_frame_submit_swin(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m, int out_h,
+                           int out_w, const float* mean_std6);
 int reid_frame_cost(reid_ctx* ctx, int slot, reid_bank* bank, const int32_t* slots, int t, int metric, float max_dist,
                     const double* tracks_t4, const double* dets_m4, int want_emb);
 int reid_frame_fetch(reid_ctx* ctx, int slot, float* emb, float* cost_tm, double* iou_tm);
@@ -279,7 +291,8 @@ int reid_frame_cost_groups(reid_ctx* ctx, int slot, int groups, reid_bank* const
 /* multi-GPU frames (every rank embeds its round-robin share of the frame's crops): between submit and
  * cost, gather the ranks' embeddings into the slot as equal blocks of per = ceil(n / world) rows - one ncclAllGather; the slot
  * then holds world * per rows (row r * per + i = detection r + i * world; rows past a rank's share are padding) on every rank.
- * Asynchronous; without a communicator (reid_comm_init) a no-op. */
+ * Asynchronous; without a communicator (reid_comm_init) a no-op.  For slots of reid_frame_submit (512-wide rows): REID_ERR_ARG after
+ * reid_frame_submit_swin. */
 int reid_frame_gather(reid_ctx* ctx, int slot, int per);
 int reid_frame_update(reid_ctx* ctx, int slot, reid_bank* bank, const int32_t* rows, const int32_t* slots, int n);
 /* Look-ahead streams (a video file / detection dump whose detections are known F frames ahead: F frames' crops are submitted as one

@@ -173,6 +173,12 @@ int reid_debug_swin_tail(reid_ctx* ctx, const float* x, int n, int ntok, const f
 int reid_debug_swin_merge(reid_ctx* ctx, int stage, const float* x, int n, int h, int w, float* out);
 int reid_debug_swin_fuse(reid_ctx* ctx, const float* sfe, const float* x1, const float* x2, const float* x3, const float* x4, int n, int h1,
                          int w1, void* a0, void* f3, void* f2, float* f1);
+/* bank_cost96: the cost stage of the frame pipeline for a 96-wide bank (NearestNeighborDistanceMetric.distance, [external]
+ * deep_sort/sort/nn_matching.py, for the swin_transformer tracker model) through the launch reid_frame_cost makes: bank_cost96_kernel of
+ * libreid_hip_bank96.so, or bank_cost_kernel with the `bank_fast` switch at 0.  slots [t] (host) of a bank with d = 96, dets [m][96] ->
+ * out [t][m]; metric REID_METRIC_COS / REID_METRIC_L2SQR, gate < 0 raw, else cost > gate -> gate + 1e-5. */
+int reid_debug_bank_cost96(reid_ctx* ctx, reid_bank* bank, const int32_t* slots, int t, const float* dets_host, int m, int metric, float gate,
+                           float* out_host);
 /* Timing experiments on that kernel (WRONG results while set): bit 0 = no weight refills after the first two steps, bit 1 = no block
  * barriers.  0 restores the product behaviour. */
 int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits);

@@ -999,7 +999,7 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
 
 // ------------------------------------------------------------------------------------------------ side libraries
 // The one loader of the libraries that lie beside this one and are opened on first use: libreid_hip_siblings_f16.so (below),
-// libreid_hip_swin_v2.so and libreid_hip_swin_crops.so (swin.hip).  Contract: reid_internal.h.
+// libreid_hip_swin_v2.so and libreid_hip_swin_crops.so (swin.hip), libreid_hip_bank96.so (bank.hip).  Contract: reid_internal.h.
 int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns) {
     Dl_info info;
     std::string path = file;
@@ -1448,22 +1448,27 @@ extern "C" int reid_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, float* 
         [&](int i, int m, float* d_emb, float* d_log) -> int { return se_run_nchw(ctx, d_in + (size_t)i * kCropElems, m, d_emb, d_log); }, out);
 }
 
-int embed_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
-                         float** d_emb_out, float** d_log_out, bool side_copy) {
-    RaggedSrc src{packed, offsets, hw, n};
+int ragged_enqueue_begin(reid_ctx* ctx, const char* tag, RaggedSrc& src, EmbedOut& out, bool want_logits, bool side_copy) {
     REID_TRY(src.check());
     REID_TRY(src.alloc(ctx, tag));
-    EmbedOut out{nullptr, nullptr, 512, ctx->se18.num_class};
-    REID_TRY(out.alloc(ctx, tag, n, 1, d_log_out != nullptr));
+    REID_TRY(out.alloc(ctx, tag, src.n, 1, want_logits));
     if (side_copy) {   // frame pipeline, pinned sources
         if (!ctx->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
         if (!ctx->copy_ev) HIP_TRY(hipEventCreateWithFlags(&ctx->copy_ev, hipEventDisableTiming));
-        REID_TRY(src.up(0, n, ctx->copy_stream));
+        REID_TRY(src.up(0, src.n, ctx->copy_stream));
         HIP_TRY(hipEventRecord(ctx->copy_ev, ctx->copy_stream));
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->copy_ev, 0));
     } else {
-        REID_TRY(src.up(0, n, ctx->stream));
+        REID_TRY(src.up(0, src.n, ctx->stream));
     }
+    return REID_OK;
+}
+
+int embed_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
+                         float** d_emb_out, float** d_log_out, bool side_copy) {
+    RaggedSrc src{packed, offsets, hw, n};
+    EmbedOut out{nullptr, nullptr, 512, ctx->se18.num_class};
+    REID_TRY(ragged_enqueue_begin(ctx, tag, src, out, d_log_out != nullptr, side_copy));
     REID_TRY(embed_dev_passes(n, ctx->chunk, [&](int i, int m) -> int {
         return se_run_windows(ctx, src, i, m, out.d_emb + (size_t)i * 512, out.d_log ? out.d_log + (size_t)i * out.nc : nullptr);
     }));

@@ -12,7 +12,9 @@
 // launch: block = (track, 16 detections), the 16 detection rows sit in LDS, each wave streams bank rows once (coalesced)
 // against all 16 and keeps the running minimum in registers.  The minimum is order-free, so ring order does not matter.
 #include "reid_internal.h"
+#include "bank96.h"
 #include <string.h>
+#include <mutex>
 #include <utility>
 
 struct reid_bank {
@@ -414,8 +416,34 @@ extern "C" int reid_bank_clear(reid_ctx* ctx, reid_bank* b, const int32_t* slots
     return REID_OK;
 }
 
+// libreid_hip_bank96.so (bank96.h), opened from the directory this library lies in on the first reid_frame_submit_swin (or by the
+// kernel's harness): a process that never tracks with a Swin never opens it.  Missing library or symbol: REID_ERR_STATE naming the file.
+static int bank96_api(decltype(&bank96_cost)* out) {
+    static std::mutex mu;
+    static decltype(&bank96_cost) cost = nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!cost) {
+        void* f;
+        REID_TRY(open_beside_self("libreid_hip_bank96.so", "the frame pipeline of a Swin tracker needs", {"bank96_cost"}, &f));
+        cost = (decltype(cost))f;
+    }
+    *out = cost;
+    return REID_OK;
+}
+
+// frame96: the caller is the frame pipeline's cost stage, which takes bank_cost96_kernel for a 96-wide bank; reid_bank_cost / _dev
+// keep bank_cost_kernel there, as before
 static int bank_cost_launch(reid_ctx* ctx, reid_bank* b, const int32_t* d_slots, int t, const float* d_dets, int m, int metric,
-                            float max_dist, float* d_out) {
+                            float max_dist, float* d_out, bool frame96 = false) {
+    if (frame96 && b->d == 96 && ctx->bank_fast) {
+        decltype(&bank96_cost) cost96;
+        REID_TRY(bank96_api(&cost96));
+        prof_begin(ctx, REID_K_SELECT, 2.0 * t * m * b->budget * b->d, 4.0 * ((double)t * b->budget * b->d + (double)m * b->d));
+        const hipError_t e = cost96(ctx->stream, b->feat, b->sq, b->count, b->budget, d_slots, t, d_dets, m, metric, max_dist, d_out);
+        prof_end(ctx);
+        HIP_TRY(e);
+        return REID_OK;
+    }
     if (b->d == 512 && ctx->bank_fast) {
         prof_begin(ctx, REID_K_SELECT, 2.0 * t * m * b->budget * b->d, 4.0 * ((double)t * b->budget * b->d + (double)m * b->d));
         hipLaunchKernelGGL(bank_cost512_kernel, dim3(t, (m + DT - 1) / DT), dim3(NW5 * 64), 0, ctx->stream, b->feat, b->sq, b->count,
@@ -432,6 +460,22 @@ static int bank_cost_launch(reid_ctx* ctx, reid_bank* b, const int32_t* d_slots,
                        b->budget, b->d, d_slots, d_dets, m, metric, max_dist, d_out);
     LAUNCH_CHECK();
     prof_end(ctx);
+    return REID_OK;
+}
+
+// The cost stage's launch on device operands of the caller (reid_debug_bank_cost96, libreid_hip_debug.so): d_slots [t] checked by the
+// caller against nothing - they must be slots of `b`; metric 0 cosine / 1 squared euclidean; on the stream every access to a bank runs on.
+int bank_frame_cost_launch(reid_ctx* ctx, reid_bank* b, const int32_t* d_slots, int t, const float* d_dets, int m, int metric, float max_dist,
+                           float* d_out) {
+    ARG_CHECK(ctx && b && b->ctx == ctx && d_slots && d_dets && d_out && t >= 1 && m >= 1 && (metric == 0 || metric == 1));
+    MatchStream ms(ctx, true, true);
+    return bank_cost_launch(ctx, b, d_slots, t, d_dets, m, metric, max_dist, d_out, true);
+}
+int bank_geometry(const reid_bank* b, int* max_tracks, int* budget, int* d) {
+    ARG_CHECK(b && max_tracks && budget && d);
+    *max_tracks = b->max_tracks;
+    *budget = b->budget;
+    *d = b->d;
     return REID_OK;
 }
 
@@ -488,6 +532,13 @@ extern "C" int reid_bank_cost(reid_ctx* ctx, reid_bank* b, const int32_t* slots,
 // Two frame slots own their device-side crops and embeddings, so frame f+1 is uploaded and embedded while the host still
 // runs the assignment of frame f.  Small inputs go through pinned staging buffers: a hipMemcpyAsync from pageable memory
 // would block the caller until everything queued before it has finished.
+// A bank meets a frame slot only at the slot's width: 512 after reid_frame_submit, the Swin's embed_dim after reid_frame_submit_swin.
+static int frame_width_check(const char* who, const reid_bank* b, int slot, int d) {
+    if (b->d == d) return REID_OK;
+    reid_set_error("%s: the bank holds %d-wide features, frame slot %d %d-wide embeddings", who, b->d, slot, d);
+    return REID_ERR_ARG;
+}
+
 extern "C" int reid_frame_match_stream(reid_ctx* ctx, int on) {
     ARG_CHECK(ctx);
     CTX_GUARD(ctx);
@@ -512,9 +563,10 @@ extern "C" int reid_frame_match_stream(reid_ctx* ctx, int on) {
     return REID_OK;
 }
 
-extern "C" int reid_frame_submit(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m) {
-    ARG_CHECK(ctx && (slot == 0 || slot == 1) && m >= 0 && (m == 0 || (packed && offsets && hw)));
-    CTX_ENTER(ctx);
+// The two submits: the slot's state reset, offsets / hw into the slot's pinned block, then `enqueue(tag, offsets, hw, &d_emb)` - the
+// backbone's upload + pass loop (reid_internal.h) - and the slot remembers m, the embeddings and their width d.
+template <class Enqueue>
+static int frame_submit_impl(reid_ctx* ctx, int slot, const int64_t* offsets, const int32_t* hw, int m, int d, Enqueue enqueue) {
     if (ctx->frame_pending[slot]) {   // resubmitted without reid_frame_fetch: its staging is still in use
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (ctx->match_stream) HIP_TRY(hipStreamSynchronize(ctx->match_stream));
@@ -525,6 +577,7 @@ extern "C" int reid_frame_submit(reid_ctx* ctx, int slot, const uint8_t* packed,
     ctx->frame_pending[slot] = 0;
     ctx->frame_m[slot] = 0;
     ctx->frame_emb[slot] = nullptr;
+    ctx->frame_d[slot] = d;
     if (m == 0) return REID_OK;
     char* pin;
     const std::string tag = slot ? "frame1" : "frame0";
@@ -532,13 +585,35 @@ extern "C" int reid_frame_submit(reid_ctx* ctx, int slot, const uint8_t* packed,
     memcpy(pin, offsets, (size_t)m * 8);
     memcpy(pin + (size_t)m * 8, hw, (size_t)m * 8);
     float* d_emb;
-    REID_TRY(embed_ragged_enqueue(ctx, tag.c_str(), packed, (const int64_t*)pin, (const int32_t*)(pin + (size_t)m * 8), m, &d_emb, nullptr,
-                                  ctx->side_copy != 0 && ctx->stream != nullptr));
+    REID_TRY(enqueue(tag.c_str(), (const int64_t*)pin, (const int32_t*)(pin + (size_t)m * 8), &d_emb));
     ctx->frame_m[slot] = m;
     ctx->frame_emb[slot] = d_emb;
     ctx->frame_pending[slot] = 1;
     if (ctx->match_async && ctx->match_stream) HIP_TRY(hipEventRecord(ctx->fwd_ev[slot], ctx->stream));
     return REID_OK;
+}
+
+extern "C" int reid_frame_submit(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m) {
+    ARG_CHECK(ctx && (slot == 0 || slot == 1) && m >= 0 && (m == 0 || (packed && offsets && hw)));
+    CTX_ENTER(ctx);
+    return frame_submit_impl(ctx, slot, offsets, hw, m, 512, [&](const char* tag, const int64_t* off, const int32_t* hw_, float** d_emb) -> int {
+        return embed_ragged_enqueue(ctx, tag, packed, off, hw_, m, d_emb, nullptr, ctx->side_copy != 0 && ctx->stream != nullptr);
+    });
+}
+
+// The same for a Swin tracker (swin_ragged_enqueue: the forward of reid_swin_embed_ragged_u8).  Everything that can be refused is
+// refused before the slot is touched or anything is queued: arguments, missing weights, a missing side library.
+extern "C" int reid_frame_submit_swin(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m,
+                                      int out_h, int out_w, const float* mean_std6) {
+    ARG_CHECK(ctx && (slot == 0 || slot == 1) && m >= 0 && (m == 0 || (packed && offsets && hw)));
+    CTX_ENTER(ctx);
+    int d = 0;
+    REID_TRY(swin_ragged_ready(ctx, out_h, out_w, &mean_std6, &d));
+    decltype(&bank96_cost) cost96;
+    REID_TRY(bank96_api(&cost96));
+    return frame_submit_impl(ctx, slot, offsets, hw, m, d, [&](const char* tag, const int64_t* off, const int32_t* hw_, float** d_emb) -> int {
+        return swin_ragged_enqueue(ctx, tag, packed, off, hw_, m, out_h, out_w, mean_std6, d_emb, ctx->side_copy != 0 && ctx->stream != nullptr);
+    });
 }
 
 // Cost stage for `groups` camera streams batched into one frame slot (reid_frame_cost is the one-group case): the slot's m
@@ -560,20 +635,23 @@ extern "C" int reid_frame_cost_groups(reid_ctx* ctx, int slot, int groups, reid_
     }
     ARG_CHECK(msum == m);
     const bool want_cost = banks && slots && tm > 0, want_iou = tracks_t4 && dets_m4 && tm > 0;
-    MatchStream ms(ctx);
-    if (ms.on() && m > 0) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->fwd_ev[slot], 0));     // the slot's embeddings
+    const int d = ctx->frame_d[slot];
+    const size_t row = (size_t)d * 4;   // bytes of one embedding
     if (want_cost) {
         ARG_CHECK(metric == REID_METRIC_COS || metric == REID_METRIC_L2SQR);
         for (int g = 0, i = 0; g < groups; ++g) {
             if (t_counts[g] == 0 || m_counts[g] == 0) { i += t_counts[g]; continue; }
-            ARG_CHECK(banks[g] && banks[g]->ctx == ctx && banks[g]->d == 512);
+            ARG_CHECK(banks[g] && banks[g]->ctx == ctx);
+            REID_TRY(frame_width_check("reid_frame_cost", banks[g], slot, d));
             for (int e = i + t_counts[g]; i < e; ++i) ARG_CHECK(slots[i] >= 0 && slots[i] < banks[g]->max_tracks);
         }
     }
+    MatchStream ms(ctx);
+    if (ms.on() && m > 0) HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->fwd_ev[slot], 0));     // the slot's embeddings
     const std::string tag = slot ? "frame1" : "frame0";
-    // inputs: [tracks 32 t][dets 32 m][slots 4 t]; outputs: [iou 8 tm][cost 4 tm][emb 2048 m]
+    // inputs: [tracks 32 t][dets 32 m][slots 4 t]; outputs: [iou 8 tm][cost 4 tm][emb 4 d m]
     const size_t in_bytes = (size_t)t * 32 + (size_t)m * 32 + (size_t)t * 4;
-    const size_t out_bytes = tm * 12 + (size_t)m * 2048;
+    const size_t out_bytes = tm * 12 + (size_t)m * row;
     char *pin_in, *pin_out, *d_in, *d_out;
     REID_TRY(ctx_pinned(ctx, (tag + ".cin").c_str(), in_bytes + 8, (void**)&pin_in));
     REID_TRY(ctx_pinned(ctx, (tag + ".cout").c_str(), out_bytes + 8, (void**)&pin_out));
@@ -595,8 +673,8 @@ extern "C" int reid_frame_cost_groups(reid_ctx* ctx, int slot, int groups, reid_
         const int tg = t_counts[g], mg = m_counts[g];
         if (tg > 0 && mg > 0) {
             if (want_cost)
-                REID_TRY(bank_cost_launch(ctx, banks[g], d_slots + t_off, tg, ctx->frame_emb[slot] + m_off * 512, mg, metric == REID_METRIC_COS ? 0 : 1,
-                                          max_dist, d_cost + tm_off));
+                REID_TRY(bank_cost_launch(ctx, banks[g], d_slots + t_off, tg, ctx->frame_emb[slot] + m_off * d, mg, metric == REID_METRIC_COS ? 0 : 1,
+                                          max_dist, d_cost + tm_off, true));
             if (want_iou) REID_TRY(launch_diou_cost(ctx, d_tracks + t_off * 4, tg, d_dets + m_off * 4, mg, d_iou + tm_off, 1));
         }
         t_off += tg;
@@ -607,7 +685,7 @@ extern "C" int reid_frame_cost_groups(reid_ctx* ctx, int slot, int groups, reid_
     else if (want_iou) HIP_TRY(hipMemcpyAsync(pin_out, d_iou, tm * 8, hipMemcpyDeviceToHost, ctx->stream));
     else if (want_cost) HIP_TRY(hipMemcpyAsync(pin_out + tm * 8, d_cost, tm * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (want_emb && m > 0)
-        HIP_TRY(hipMemcpyAsync(pin_out + tm * 12, ctx->frame_emb[slot], (size_t)m * 2048, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(pin_out + tm * 12, ctx->frame_emb[slot], (size_t)m * row, hipMemcpyDeviceToHost, ctx->stream));
     if (!ctx->frame_ev[slot]) HIP_TRY(hipEventCreateWithFlags(&ctx->frame_ev[slot], hipEventDisableTiming));
     HIP_TRY(hipEventRecord(ctx->frame_ev[slot], ctx->stream));
     if (ms.on()) HIP_TRY(hipEventRecord(ctx->match_ev[slot], ctx->stream));
@@ -641,12 +719,13 @@ extern "C" int reid_frame_fetch(reid_ctx* ctx, int slot, float* emb, float* cost
     ARG_CHECK((!iou_tm || (has & 1)) && (!cost_tm || (has & 2)) && (!emb || (has & 4) || ctx->frame_m[slot] == 0));
     if (iou_tm) memcpy(iou_tm, pin_out, tm * 8);
     if (cost_tm) memcpy(cost_tm, pin_out + tm * 8, tm * 4);
-    if (emb && (has & 4)) memcpy(emb, pin_out + tm * 12, (size_t)ctx->frame_m[slot] * 2048);
+    if (emb && (has & 4)) memcpy(emb, pin_out + tm * 12, (size_t)ctx->frame_m[slot] * ctx->frame_d[slot] * 4);
     return ctx_fault_status(ctx);   // the frame's forward has completed: a fault it raised is reported with its results
 }
 
 extern "C" int reid_frame_update(reid_ctx* ctx, int slot, reid_bank* b, const int32_t* rows, const int32_t* slots, int n) {
-    ARG_CHECK(ctx && (slot == 0 || slot == 1) && b && b->ctx == ctx && b->d == 512 && n >= 0 && (n == 0 || (rows && slots)));
+    ARG_CHECK(ctx && (slot == 0 || slot == 1) && b && b->ctx == ctx && n >= 0 && (n == 0 || (rows && slots)));
+    REID_TRY(frame_width_check("reid_frame_update", b, slot, ctx->frame_d[slot]));
     CTX_GUARD(ctx);
     if (n == 0) return REID_OK;
     for (int i = 0; i < n; ++i) ARG_CHECK(rows[i] >= 0 && rows[i] < ctx->frame_m[slot]);

@@ -223,6 +223,10 @@ extern "C" int reid_frame_gather(reid_ctx* ctx, int slot, int per) {
     CTX_GUARD(ctx);
     const int world = ctx->comm ? ctx->comm->world : 1;
     ARG_CHECK(ctx->frame_m[slot] <= per && per <= ctx->frame_m[slot] + 1);   // round-robin shares differ by at most one crop
+    if (ctx->frame_d[slot] != 512) {   // the gather moves 512-wide rows: sharded frames are the ResNet's (reid_frame_submit)
+        reid_set_error("reid_frame_gather: frame slot %d holds %d-wide embeddings, the gather serves 512-wide ones", slot, ctx->frame_d[slot]);
+        return REID_ERR_ARG;
+    }
     if (!ctx->comm || (!ctx->comm->comm && !ctx->comm->loop) || per == 0) return REID_OK;   // (a 1-rank communicator still runs the collective: tests)
     const std::string tag = slot ? "frame1" : "frame0";
     const int mine = ctx->frame_m[slot];

@@ -1376,3 +1376,32 @@ extern "C" int reid_debug_swin_fuse(reid_ctx* ctx, const float* sfe, const float
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }
+
+// bank_cost96_kernel (bank96.hip, libreid_hip_bank96.so) through the launch the frame pipeline's cost stage makes (bank.hip), on host
+// operands: the costs of the bank's track slots[t] against dets [m][96] -> out [t][m], set to 0xff bytes first (an entry the launch leaves alone reads NaN); metric
+// REID_METRIC_COS / REID_METRIC_L2SQR, gate < 0 raw.  With the `bank_fast` switch at 0 the same call runs bank_cost_kernel, as the pipeline does.  The bank must be 96 wide.
+extern "C" int reid_debug_bank_cost96(reid_ctx* ctx, reid_bank* bank, const int32_t* slots, int t, const float* dets, int m, int metric,
+                                      float gate, float* out) {
+    ARG_CHECK(ctx && bank && slots && dets && out && t >= 1 && m >= 1 && (metric == REID_METRIC_COS || metric == REID_METRIC_L2SQR));
+    int max_tracks, budget, d;
+    REID_TRY(bank_geometry(bank, &max_tracks, &budget, &d));
+    ARG_CHECK(d == 96);
+    for (int i = 0; i < t; ++i) ARG_CHECK(slots[i] >= 0 && slots[i] < max_tracks);
+    CTX_ENTER(ctx);
+    int32_t* dslots;
+    float *ddets, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgb.slots", slots, (size_t)t, &dslots));
+    REID_TRY(dbg_upload(ctx, "dbgb.dets", dets, (size_t)m * 96, &ddets));
+    REID_TRY(dbg_output(ctx, "dbgb.out", (size_t)t * m + 16, &dout));
+    REID_TRY(bank_frame_cost_launch(ctx, bank, dslots, t, ddets, m, metric == REID_METRIC_COS ? 0 : 1, gate, dout));
+    uint32_t guard[16];   // the 16 words behind the matrix: a launch that wrote past its t x m entries is an error of this call
+    REID_TRY(dbg_download(ctx, out, dout, (size_t)t * m));
+    REID_TRY(dbg_download(ctx, guard, (const uint32_t*)(dout + (size_t)t * m), (size_t)16));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 16; ++i)
+        if (guard[i] != 0xffffffffu) {
+            reid_set_error("reid_debug_bank_cost96: the launch wrote word %d past its %d x %d outputs", i, t, m);
+            return REID_ERR_STATE;
+        }
+    return ctx_fault_status(ctx);
+}

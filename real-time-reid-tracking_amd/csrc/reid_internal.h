@@ -463,6 +463,7 @@ struct reid_ctx {
     int f16_cfg = 0;         // fp16 GEMM tile/ring override: BN*1000 + BK*10 + NST, 0 = heuristic (REID_F16_CFG)
     int frame_m[2] = {0, 0};                        // frame pipeline (bank.hip): detections / device embeddings per frame slot
     float* frame_emb[2] = {nullptr, nullptr};
+    int frame_d[2] = {512, 512};                    // width of the slot's embeddings: 512 after reid_frame_submit, the Swin's embed_dim after reid_frame_submit_swin
     int frame_pending[2] = {0, 0}, frame_has[2] = {0, 0};
     size_t frame_tm[2] = {0, 0};        // elements of the cost stage's output (sum over the camera groups of tracks x detections)
     hipEvent_t frame_ev[2] = {nullptr, nullptr};
@@ -717,11 +718,24 @@ int embed_dev_passes(int n, int pass, Run run) {
     for (int i = 0; i < n; i += pass) REID_TRY(run(i, n - i < pass ? n - i : pass));
     return REID_OK;
 }
-// RaggedSrc + the ResNet18-SE pass loop under `tag` with NO synchronisation and no download (reid_frame_submit, bank.hip: one buffer set
-// per frame slot).  side_copy: the upload runs on the context's copy stream, beside the previous frame's kernels.  offsets / hw must be
-// pinned or outlive the stream's work.  <tag>.emb has one row more than n: the padding row of reid_frame_gather.
+// The frame pipeline's way in (bank.hip: one buffer set per frame slot): RaggedSrc + EmbedOut under `tag` with NO synchronisation and no
+// download.  ragged_enqueue_begin checks the crops, allocates <tag>.in / .meta / .emb (one row more than n: the padding row of
+// reid_frame_gather) / .logits and queues the upload - side_copy: on the context's copy stream, beside the previous frame's kernels, the
+// compute stream waiting for it.  offsets / hw must be pinned or outlive the stream's work.  The pass loop that follows is the backbone's:
+// embed_ragged_enqueue (api.hip) runs ResNet18-SE passes of `chunk` crops, swin_ragged_enqueue (swin.hip) swin_forward_crops in passes
+// of swin_pass(ctx) crops to out_h x out_w (*dim_out = the loaded Swin's embed_dim).  swin_ragged_ready: everything the latter would
+// refuse, checked with nothing queued - arguments (REID_ERR_ARG), loaded weights and libreid_hip_swin_crops.so (REID_ERR_STATE).
+int ragged_enqueue_begin(reid_ctx* ctx, const char* tag, RaggedSrc& src, EmbedOut& out, bool want_logits, bool side_copy);
 int embed_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
                          float** d_emb_out, float** d_log_out, bool side_copy);
+int swin_ragged_ready(reid_ctx* ctx, int out_h, int out_w, const float** mean_std6, int* dim_out);
+int swin_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                        int out_w, const float* mean_std6, float** d_emb_out, bool side_copy);
+// bank.hip: the launch of the frame pipeline's cost stage on the caller's device operands (metric 0 cosine / 1 squared euclidean; a
+// 96-wide bank with bank_fast on takes bank_cost96_kernel of libreid_hip_bank96.so), and a bank's sizes - for reid_debug_bank_cost96
+int bank_frame_cost_launch(reid_ctx* ctx, reid_bank* b, const int32_t* d_slots, int t, const float* d_dets, int m, int metric, float max_dist,
+                           float* d_out);
+int bank_geometry(const reid_bank* b, int* max_tracks, int* budget, int* d);
 // The library `file` in the directory this library lies in: opened (RTLD_NOW | RTLD_LOCAL), fns[k] = its symbol names[k].  A missing file
 // ("<what> <path> beside libreid_hip.so: <dlerror>") or symbol ("<path> lacks a / b", the handle closed again) is REID_ERR_STATE.
 int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns);

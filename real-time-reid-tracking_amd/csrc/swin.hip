@@ -2070,6 +2070,32 @@ static int swin_embed_windows(reid_ctx* ctx, RaggedSrc& src, int out_h, int out_
         out);
 }
 
+// The frame pipeline's Swin submit (reid_frame_submit_swin, bank.hip; contract: reid_internal.h)
+int swin_ragged_ready(reid_ctx* ctx, int out_h, int out_w, const float** mean_std6, int* dim_out) {
+    REID_TRY(swin_crops_args(out_h, out_w, mean_std6));
+    const SwinWeights* sw;
+    REID_TRY(swin_loaded(ctx, &sw));
+    decltype(&swin_crops_front) front;
+    REID_TRY(swin_crops_api(&front));
+    *dim_out = 96;
+    return REID_OK;
+}
+
+int swin_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                        int out_w, const float* mean_std6, float** d_emb_out, bool side_copy) {
+    const SwinWeights* sw;
+    REID_TRY(swin_loaded(ctx, &sw));
+    RaggedSrc src{packed, offsets, hw, n};
+    EmbedOut out{nullptr, nullptr, 96, sw->num_class};
+    REID_TRY(ragged_enqueue_begin(ctx, tag, src, out, false, side_copy));
+    REID_TRY(embed_dev_passes(n, swin_pass(ctx), [&](int i, int m) -> int {
+        return swin_forward_crops(ctx, *sw, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, out_h, out_w, src.pitch, mean_std6,
+                                  out.d_emb + (size_t)i * 96, nullptr);
+    }));
+    *d_emb_out = out.d_emb;
+    return REID_OK;
+}
+
 extern "C" int reid_swin_embed_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
                                          int out_w, const float* mean_std6, float* emb, float* logits) {
     ARG_CHECK(ctx && packed && offsets && hw && emb && n >= 0);

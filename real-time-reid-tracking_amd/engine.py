@@ -311,8 +311,8 @@ class Engine:
         self._pinned.append(p)
         return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(int(nbytes),))
 
-    def frame_submit(self, slot, crops):
-        """Stage 1: pack the ragged uint8 crops into the slot's pinned slab, enqueue upload + resize + forward; returns at once."""
+    def _frame_pack(self, slot, crops):
+        """The ragged uint8 crops of a frame into the slot's pinned slab: (slab, offsets int64[n], hw int32[n,2], n)."""
         n = len(crops)
         hw = np.empty((n, 2), np.int32)
         offs = np.empty(n, np.int64)
@@ -336,9 +336,29 @@ class Engine:
             slab = slabs[slot] = self.pinned(max(2 * total, 1 << 22))
         for i, c in enumerate(crops):   # straight into pinned memory: the only host copy of the pixels
             slab[offs[i]: offs[i] + c.size].reshape(c.shape)[...] = c
+        return slab, offs, hw, n
+
+    def frame_submit(self, slot, crops):
+        """Stage 1: pack the ragged uint8 crops into the slot's pinned slab, enqueue upload + resize + forward; returns at once."""
+        slab, offs, hw, n = self._frame_pack(slot, crops)
         check(self.lib.reid_frame_submit(self.h, int(slot), _ptr(slab), _ptr(offs), _ptr(hw), n))
         self.__dict__.setdefault("_frame_n", {})[slot] = n
+        self.__dict__.setdefault("_frame_d", {})[slot] = 512
         return n
+
+    def frame_submit_swin(self, slot, crops, size=(224, 224), mean_std=None):
+        """Stage 1 for a Swin tracker (reid_frame_submit_swin): as frame_submit, with the forward of swin_embed_ragged_u8 - ``size`` and
+        ``mean_std`` as there, checked before any device call.  The slot's embeddings are [n, swin_dim] (96) wide."""
+        h, w, ms = self._swin_crop_args(size, mean_std)
+        slab, offs, hw, n = self._frame_pack(slot, crops)
+        check(self.lib.reid_frame_submit_swin(self.h, int(slot), _ptr(slab), _ptr(offs), _ptr(hw), n, h, w, _ptr(ms)))
+        self.__dict__.setdefault("_frame_n", {})[slot] = n
+        self.__dict__.setdefault("_frame_d", {})[slot] = self.swin_dim
+        return n
+
+    def frame_dim(self, slot):
+        """Width d of the embeddings of the frame last submitted to ``slot``: 512 (frame_submit) or the Swin's 96 (frame_submit_swin)."""
+        return self.__dict__.get("_frame_d", {}).get(slot, 512)
 
     def frame_gather(self, slot, per, world):
         """Multi-GPU frames: all-gather the ranks' embeddings of the submitted frame into the slot (equal blocks of `per` rows);
@@ -372,9 +392,9 @@ class Engine:
                                                           tb is not None and t and m)
 
     def frame_fetch(self, slot):
-        """The frame's one wait: (emb[m,512] | None, cost[t,m] float32 | None, iou_cost[t,m] float64 | None)."""
+        """The frame's one wait: (emb[m,d] | None, cost[t,m] float32 | None, iou_cost[t,m] float64 | None); d = frame_dim(slot)."""
         m, t, want_emb, has_cost, has_iou = self._frame_q.pop(slot)
-        emb = np.empty((m, 512), np.float32) if want_emb else None
+        emb = np.empty((m, self.frame_dim(slot)), np.float32) if want_emb else None
         cost = np.empty((t, m), np.float32) if has_cost else None
         iou = np.empty((t, m), np.float64) if has_iou else None
         check(self.lib.reid_frame_fetch(self.h, int(slot), _ptr(emb) if m else None, _ptr(cost), _ptr(iou)))
@@ -416,9 +436,9 @@ class Engine:
         self.__dict__.setdefault("_frame_q", {})[slot] = (self._frame_n[slot], tm, want_emb, sl is not None and tm > 0, boxes and tm > 0, tc, mc)
 
     def frame_fetch_groups(self, slot):
-        """The one wait of a batched frame: (emb[m,512] | None, [cost_g[t_g,m_g] float32 | None], [iou_g float64 | None])."""
+        """The one wait of a batched frame: (emb[m,d] | None, [cost_g[t_g,m_g] float32 | None], [iou_g float64 | None]); d = frame_dim(slot)."""
         m, tm, want_emb, has_cost, has_iou, tc, mc = self._frame_q.pop(slot)
-        emb = np.empty((m, 512), np.float32) if want_emb else None
+        emb = np.empty((m, self.frame_dim(slot)), np.float32) if want_emb else None
         cost = np.empty(tm, np.float32) if has_cost else None
         iou = np.empty(tm, np.float64) if has_iou else None
         check(self.lib.reid_frame_fetch(self.h, int(slot), _ptr(emb) if m else None, _ptr(cost), _ptr(iou)))
@@ -669,6 +689,16 @@ class Engine:
             raise ValueError("debug_resize_norm: a window leaves the buffer")
         out = np.empty((n, IMG_H, IMG_W, 3), np.float32)
         check(_ffi.debug_lib().reid_debug_resize_norm(self.h, _ptr(packed), _ptr(offsets), _ptr(hw), C.c_int(n), C.c_int(int(pitch)), _ptr(out)))
+        return out
+
+    def debug_bank_cost96(self, bank, slots, dets, metric=_ffi.METRIC_COS, gate=None):
+        """reid_debug_bank_cost96: the frame pipeline's cost launch for a 96-wide bank handle on host operands -> cost[t, m] float32
+        (entries the launch leaves alone read NaN)."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        x = np.ascontiguousarray(dets, np.float32).reshape(-1, 96)
+        out = np.full((len(sl), len(x)), np.nan, np.float32)
+        check(_ffi.debug_lib().reid_debug_bank_cost96(self.h, bank, _ptr(sl), len(sl), _ptr(x), len(x), int(metric),
+                                                      C.c_float(-1.0 if gate is None else gate), _ptr(out)))
         return out
 
     def debug_swin_crop_front(self, packed, offsets, hw, c1_w, c1_b, size=(224, 224), mean_std=None, pitch=0):

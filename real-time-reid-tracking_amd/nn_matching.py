@@ -126,17 +126,18 @@ class NearestNeighborDistanceMetric:
 
     def frame_distance_begin(self, slot, targets, max_distance=None, track_boxes=None, det_boxes=None):
         """Enqueue `distance` (and, given tlwh boxes, iou_matching.iou_cost) for the frame submitted with
-        `engine.frame_submit(slot, crops)`, whose embeddings never leave the device in between.  Asynchronous: submit the
+        `engine.frame_submit(slot, crops)` or `engine.frame_submit_swin(slot, crops)`, whose embeddings [m, d] never leave the device in between.  Asynchronous: submit the
         next frame, then collect with `frame_distance_end`."""
         targets = list(targets)
-        self._ensure(512)
+        self._ensure(self._eng.frame_dim(slot))
         slots = self._slots_for(targets, False) if targets else None
         self._eng.frame_cost(slot, self._bank, slots, self._metric, -1.0 if max_distance is None else max_distance,
                              track_boxes, det_boxes)
         self._pending_targets = len(targets)
 
     def frame_distance_end(self, slot):
-        """(features[m,512], cost[len(targets),m], iou_cost | None) of `frame_distance_begin`: the frame's one wait."""
+        """(features[m,d], cost[len(targets),m], iou_cost | None) of `frame_distance_begin`: the frame's one wait; d is the width of the
+        slot's embeddings (512 after `frame_submit`, the Swin's 96 after `frame_submit_swin`)."""
         emb, cost, iou = self._eng.frame_fetch(slot)
         if cost is None:
             cost = np.zeros((self._pending_targets, emb.shape[0]), np.float32)
@@ -150,7 +151,7 @@ class NearestNeighborDistanceMetric:
         """`partial_fit` with features = rows `rows` of the submitted frame's embeddings (asynchronous)."""
         targets = list(targets)
         if len(targets):
-            self._ensure(512)
+            self._ensure(self._eng.frame_dim(slot))
             self._eng.frame_update(slot, self._bank, rows, self._slots_for(targets, True))
         active = set(active_targets)
         gone = [t for t in self._slot if t not in active]

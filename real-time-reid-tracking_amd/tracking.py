@@ -31,6 +31,35 @@ def _two_streams(stream, on):
     stream.eng.frame_match_stream(stream.match_stream)
 
 
+def _check_arch(arch, size, mean_std):
+    """`arch`, `size`, `mean_std` of the stream classes, checked before any device call (ValueError)."""
+    if arch == "swin":
+        Engine._swin_crop_args(size, mean_std)
+    elif arch != "seres18":
+        raise ValueError("arch must be 'seres18' or 'swin', got %r" % (arch,))
+    elif tuple(size) != (224, 224) or mean_std is not None:
+        raise ValueError("size / mean_std belong to arch='swin' (a ResNet18-SE crop is always 256x128, ImageNet-normalised)")
+
+
+def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std):
+    """`arch` of the stream classes: "seres18" (default) loads a ResNet18-SE family checkpoint, frames are 512 wide; "swin" - the
+    reference's swin_transformer tracker model, modification_tracking/models/__init__.py:80 - loads with `Engine.load_swin`, every crop
+    is resized to ``size`` = (H, W) multiples of 224 and normalised with ``mean_std`` (None: ImageNet), and the embeddings, the bank
+    and the cost stage are 96 wide."""
+    if arch == "swin":
+        stream.eng.load_swin(weights_blob, manifest)
+    else:
+        stream.eng.load_seres18(weights_blob, manifest)
+    stream.arch, stream.size, stream.mean_std = arch, size, mean_std
+
+
+def _frame_submit(stream, slot, crops):
+    """What every class's `_submit` hook ends in: the frame's crops into `slot` through the stream's backbone."""
+    if getattr(stream, "arch", "seres18") == "swin":
+        return stream.eng.frame_submit_swin(slot, crops, stream.size, stream.mean_std)
+    return stream.eng.frame_submit(slot, crops)
+
+
 def _one_stream_again(stream):
     if stream.match_stream and not stream._own:
         stream.eng.frame_match_stream(False)      # a shared context goes back to one stream
@@ -38,28 +67,32 @@ def _one_stream_again(stream):
 
 class CameraStream:
     def __init__(self, weights_blob, manifest, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0, own_context=True,
-                 max_tracks=4096, match_stream=True):
+                 max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None):
+        _check_arch(arch, size, mean_std)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        self.eng.load_seres18(weights_blob, manifest)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
         self.metric = NearestNeighborDistanceMetric(metric, max_dist, budget, max_tracks=max_tracks, engine=self.eng)
         self._frame = 0
 
+    def _submit(self, slot, crops):
+        _frame_submit(self, slot, crops)
+
     def submit(self, crops):
         """Queue upload + embedding of the FIRST frame's crops (returns at once); later frames ride on `step(next_crops=...)`."""
-        self.eng.frame_submit(self._frame & 1, crops)
+        self._submit(self._frame & 1, crops)
 
     def step(self, targets, track_boxes, det_boxes, next_crops=None):
         """Costs of the submitted frame against the confirmed tracks `targets` (tlwh boxes for the DIoU cost), with the next
         frame's crops submitted in between so that the device works under the host's assignment.  Returns
-        (features[m,512], appearance_cost[t,m] gated at max_dist, iou_cost[t,m] | None)."""
+        (features[m,d], appearance_cost[t,m] gated at max_dist, iou_cost[t,m] | None); d = 512, or 96 with arch="swin"."""
         slot = self._frame & 1
         self.metric.frame_distance_begin(slot, targets, self.max_dist, track_boxes, det_boxes)
         if next_crops is not None:
-            self.eng.frame_submit(slot ^ 1, next_crops)
+            self._submit(slot ^ 1, next_crops)
         return self.metric.frame_distance_end(slot)
 
     def commit(self, rows, targets, active_targets):
@@ -91,10 +124,11 @@ class MultiCameraStream:
     with one list entry per camera everywhere; one host thread, one wait per frame time."""
 
     def __init__(self, weights_blob, manifest, cameras, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True):
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None):
+        _check_arch(arch, size, mean_std)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        self.eng.load_seres18(weights_blob, manifest)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -108,7 +142,7 @@ class MultiCameraStream:
         if len(crops_per_camera) != self.cameras:
             raise ValueError("expected %d crop lists, got %d" % (self.cameras, len(crops_per_camera)))
         self._m[slot] = [len(c) for c in crops_per_camera]
-        self.eng.frame_submit(slot, [c for cam in crops_per_camera for c in cam])
+        _frame_submit(self, slot, [c for cam in crops_per_camera for c in cam])
 
     def submit(self, crops_per_camera):
         """Queue upload + embedding of the FIRST frame time's crops (one list per camera); later ones ride on `step`."""
@@ -117,12 +151,12 @@ class MultiCameraStream:
     def step(self, targets, track_boxes, det_boxes, next_crops=None):
         """Per camera c: costs of its submitted detections against its confirmed tracks ``targets[c]`` (tlwh boxes for the DIoU
         cost; ``track_boxes`` / ``det_boxes`` None = no DIoU), the next frame time's crops submitted in between.  Returns one
-        (features[m_c,512], appearance_cost[t_c,m_c] gated at max_dist, iou_cost[t_c,m_c] | None) per camera."""
+        (features[m_c,d], appearance_cost[t_c,m_c] gated at max_dist, iou_cost[t_c,m_c] | None) per camera."""
         slot = self._frame & 1
         ms = self._m[slot]
         groups = []
         for c, met in enumerate(self.metrics):
-            met._ensure(512)
+            met._ensure(self.eng.frame_dim(slot))
             tg = list(targets[c])
             groups.append((met._bank, met._slots_for(tg, False) if tg else np.empty(0, np.int32),
                            None if track_boxes is None else track_boxes[c], None if det_boxes is None else det_boxes[c], ms[c]))
@@ -179,10 +213,11 @@ class LookaheadCameraStream:
     """
 
     def __init__(self, weights_blob, manifest, frames_per_pass=2, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True):
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None):
+        _check_arch(arch, size, mean_std)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        self.eng.load_seres18(weights_blob, manifest)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -195,7 +230,7 @@ class LookaheadCameraStream:
         if not 1 <= len(group) <= self.frames_per_pass:
             raise ValueError("a group holds 1..%d frames, got %d" % (self.frames_per_pass, len(group)))
         self._m[slot] = [len(c) for c in group]
-        self.eng.frame_submit(slot, [c for fr in group for c in fr])
+        _frame_submit(self, slot, [c for fr in group for c in fr])
 
     def submit_group(self, group):
         """Queue upload + embedding of the FIRST group of frames (a list of crop lists); later groups ride on the step of frame
@@ -211,11 +246,11 @@ class LookaheadCameraStream:
         return 0 if self.match_stream else len(self._m[self._group & 1]) - 1
 
     def step(self, j, targets, track_boxes, det_boxes, next_group=None):
-        """Frame j of the submitted group: (features[m_j,512], appearance_cost[t,m_j] gated at max_dist, iou_cost[t,m_j] | None) against
+        """Frame j of the submitted group: (features[m_j,d], appearance_cost[t,m_j] gated at max_dist, iou_cost[t,m_j] | None) against
         the confirmed tracks as the previous frame's commit left the bank."""
         slot = self._group & 1
         ms = self._m[slot]
-        self.metric._ensure(512)
+        self.metric._ensure(self.eng.frame_dim(slot))
         tg = list(targets)
         slots = self.metric._slots_for(tg, False) if tg else np.empty(0, np.int32)
         boxes = track_boxes is not None and det_boxes is not None
@@ -256,7 +291,9 @@ class ShardedCameraStream:
     slot on EVERY rank, and every rank then computes the full cost matrices and keeps its own copy of the feature bank up to
     date - as DeepSORT would on every rank.  Same call order as `CameraStream` (submit, then per frame step + commit); all
     arguments and results are in DETECTION order, the mapping to rows of the gathered slot (`parallel.frame_rows`) stays inside.
-    `engine` carries the rank's communicator (`RcclComm`); with world 1 this is `CameraStream` on an existing engine."""
+    `engine` carries the rank's communicator (`RcclComm`); with world 1 this is `CameraStream` on an existing engine.
+    ResNet18-SE family only: `reid_frame_gather` moves 512-wide rows, a Swin tracker (`arch="swin"` of the other stream classes) is
+    not sharded over ranks."""
 
     def __init__(self, engine, comm, max_dist=0.15, budget=100, metric="cosine", max_tracks=4096, match_stream=None):
         self.eng, self.rank, self.world = engine, int(comm.rank), int(comm.world)
