@@ -187,6 +187,30 @@ int reid_swin_embed_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_
                               const float* mean_std6, float* emb, float* logits);
 int reid_swin_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame_hwc, int fh, int fw, const int32_t* boxes_xyxy, int n, int out_h, int out_w,
                              const float* mean_std6, float* emb, float* logits);
+/* The evaluation script's retrieval descriptor for this backbone - reid/image_reid_inference.py offers --backbone swin_v1 | swin_v2
+ * beside seres18 | cares18 (:145-152, :202-208) and runs the Swin at 448x224 with ImageNet normalisation (data_transforms.py:78-84).
+ * In eval mode SwinTransformer.forward returns (logits, x_norm) (swin_transformer.py:422-423; SERes18 returns (x_norm, logits)), and
+ * inference_efficient concatenates normalize(first) | normalize(second), so a Swin row is [normalize(logits) (num_class) |
+ * normalize(x_norm) (96)], the logits part FIRST: out fp32[n][num_class + 96].  flip_tta == 0: that row of the plain view, not
+ * renormalised (as reid_descriptor_*); flip_tta != 0: normalize((d(x) + d(hflip x)) / 2) (:252-253).  normalize is F.normalize,
+ * v / max(||v||, 1e-12).  The loaded v1 or v2 weights, every precision; h, w / out_h, out_w multiples of 224; passes of min(chunk, the
+ * Swin pass cap) images.  With --sie the script passes an image's camera index as the view_index of both views (inference_efficient
+ * :117-120, model(img, cam.repeat(2))): pending side indices (reid_ctx_set_side_index, n of them) apply to the plain AND the mirrored
+ * view of the same image at every pass size, and nothing is left pending afterwards, also on error.
+ * The mirrored view is never materialised: the stem reads the source with reversed columns, and one kernel runs the classifier of both
+ * views in exact fp32, the four norms, the average and the renormalisation - the logits never reach memory.  In precisions 1 and 2 the
+ * descriptor's logits therefore come from exact-fp32 arithmetic on x_norm, while the logits reid_swin_embed_* returns come from that
+ * mode's GEMM.  These kernels are libreid_hip_swin_eval.so, which must lie beside this library.
+ * ragged_u8: crops, out_h, out_w and mean_std6 as reid_swin_embed_ragged_u8; the mirror is taken AFTER the resize, the order of the
+ * reference's transforms (Resize -> flip -> ToTensor -> Normalize); bit-identical to reid_swin_descriptor_f32_nchw on the same crops
+ * resized and normalised in fp32 on the host.
+ * Refused before anything is queued: no Swin weights, a blob without classifier, or a missing side library (REID_ERR_STATE, the latter
+ * naming the file); a bad size or mean_std6, a side-index count other than n or an index outside the table, or more than 4096 classes
+ * (the descriptor kernel's limit: both views' logits are held on chip) (REID_ERR_ARG).  n == 0 returns REID_OK. */
+int reid_swin_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, int h, int w, int flip_tta, float* out);
+int reid_swin_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out);
+int reid_swin_descriptor_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                   int out_w, const float* mean_std6, int flip_tta, float* out);
 
 /* ---- matching ----------------------------------------------------------------------------- */
 /* out[m][n] = metric(x[m][d], y[n][d])        reid/losses/utils.py:12-35, reid/evaluate.py:58 */

@@ -124,6 +124,16 @@ int reid_debug_resize_norm(reid_ctx* ctx, const uint8_t* packed, const long long
 int reid_debug_swin_crop_front(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch, int out_h,
                                int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out);
 int reid_debug_swin_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out);
+/* The three kernels of libreid_hip_swin_eval.so (csrc/swin_eval.hip; tests/test_gpu_swin_eval.py), each through the launcher the Swin
+ * descriptor entry points call, on host operands.  swin_conv1_mirror / swin_crop_front_mirror: the arguments of swin_conv1 /
+ * swin_crop_front, the result of the horizontally mirrored (resized) image.  swin_descriptor: e1, e2 (NULL: one view) [n][96] and cls_w
+ * [num_class][96] -> rows [0, n) x columns [0, num_class + 96) of out [out_rows][ld] (out_rows >= n, ld >= num_class + 96); everything
+ * else of out reads NaN afterwards. */
+int reid_debug_swin_conv1_mirror(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out);
+int reid_debug_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch, int out_h,
+                                      int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out);
+int reid_debug_swin_descriptor(reid_ctx* ctx, const float* e1, const float* e2, const float* cls_w, int n, int num_class, int out_rows, int ld,
+                               float* out);
 /* maxpool: MaxPool(3, 2, 1) of x NHWC [n][h][w][c] -> out [n][(h - 1) / 2 + 1][(w - 1) / 2 + 1][c], fp32 (f16 = 0) or raw f16 bits. */
 int reid_debug_maxpool(reid_ctx* ctx, int f16, const void* x, int n, int h, int w, int c, void* out);
 /* The two kernels of the Swin "v2" blocks alone (csrc/swin_v2.hip; correctness harnesses, tests/test_gpu_swin_v2.py), each through the

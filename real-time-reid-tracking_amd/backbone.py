@@ -381,6 +381,34 @@ class SwinT:
 
     forward = __call__
 
+    def descriptor(self, x, view_index=None, flip_tta=True):
+        """The evaluation script's retrieval descriptor (reid/image_reid_inference.py:112-123,252-253 with --backbone swin_*):
+        float [N,3,H,W] (numpy or CPU / CUDA torch tensor, H, W multiples of 224) -> numpy float32 [N, num_classes + 96] =
+        [normalize(logits) | normalize(x_norm)], averaged with the mirrored image's and renormalised when ``flip_tta``.
+        ``view_index`` (the script's --sie: the camera index) serves the plain and the mirrored view of an image alike."""
+        x_np = x.detach().float().cpu().numpy() if hasattr(x, "detach") else np.asarray(x, np.float32)
+        if x_np.ndim != 4 or x_np.shape[1] != 3 or x_np.shape[2] <= 0 or x_np.shape[3] <= 0 or x_np.shape[2] % 224 or x_np.shape[3] % 224:
+            raise ValueError("expected float[n,3,224k,224m], got %s" % (tuple(x_np.shape),))
+        if view_index is not None and not (self.side_info and self.views > 0):
+            if self.side_info:
+                raise AttributeError("SwinTransformer was built without camera / sequence: no side_info_embedding")
+            view_index = None
+        idx = None
+        if view_index is not None:
+            idx = _index_array(view_index, x_np.shape[0])
+            if idx.size and (idx.min() < 0 or idx.max() >= self.views):
+                raise ValueError("view_index must lie in [0, %d), got %d .. %d" % (self.views, idx.min(), idx.max()))
+
+        def run(eng):
+            if idx is not None:
+                eng.set_side_index(idx)
+            return eng.swin_descriptor_f32_nchw(x_np, flip_tta=flip_tta)
+        try:
+            return self._run(run)
+        finally:
+            if idx is not None:
+                get_engine(self._device).set_side_index(None)
+
     def embed_crops(self, crops, size=(224, 224)):
         """uint8 HxWx3 crops of any size -> float32[N,96]: bilinear resize to ``size`` = (H, W) (multiples of 224), ImageNet
         normalisation (reid/data_transforms.py:64) and the stem's first convolution in one kernel on the device."""

@@ -1096,8 +1096,8 @@ extern "C" int reid_debug_resize_norm(reid_ctx* ctx, const uint8_t* packed, cons
 // swin_crop_front_kernel (swin_crops.hip) through the launcher the crops entry points call, on host operands: windows as for
 // reid_debug_resize_norm, c1_w [12][(kh, kw, c)], c1_b [12] -> out [n][out_h / 2][out_w / 2][12].  Every window is checked against the
 // bytes uploaded before anything is launched.
-extern "C" int reid_debug_swin_crop_front(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch,
-                                          int out_h, int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out) {
+static int debug_swin_crop_front(reid_ctx* ctx, bool mirror, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch,
+                                 int out_h, int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out) {
     ARG_CHECK(ctx && packed && offsets && hw && n >= 1 && pitch >= 0 && mean_std6 && c1_w && c1_b && out);
     REID_TRY(swin_crops_check(out_h, out_w, mean_std6));
     size_t bytes = 0;                                        // the source bytes the n windows span
@@ -1119,14 +1119,23 @@ extern "C" int reid_debug_swin_crop_front(reid_ctx* ctx, const uint8_t* packed, 
     REID_TRY(dbg_upload(ctx, "dbgf.c1w", c1_w, (size_t)144, &dw));
     REID_TRY(dbg_upload(ctx, "dbgf.c1b", c1_b, (size_t)12, &db));
     REID_TRY(dbg_output(ctx, "dbgf.c1", nout, &dout));
-    REID_TRY(launch_swin_crop_front(ctx, dpk, doff, dhw, n, out_h, out_w, pitch, mean_std6, dw, db, dout));
+    REID_TRY((mirror ? launch_swin_crop_front_mirror : launch_swin_crop_front)(ctx, dpk, doff, dhw, n, out_h, out_w, pitch, mean_std6, dw, db, dout));
     REID_TRY(dbg_download(ctx, out, dout, nout));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }
+extern "C" int reid_debug_swin_crop_front(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch,
+                                          int out_h, int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out) {
+    return debug_swin_crop_front(ctx, false, packed, offsets, hw, n, pitch, out_h, out_w, mean_std6, c1_w, c1_b, out);
+}
+// swin_crop_front_mirror_kernel (swin_eval.hip): the same windows, the resized image's columns reversed
+extern "C" int reid_debug_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int pitch,
+                                                 int out_h, int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out) {
+    return debug_swin_crop_front(ctx, true, packed, offsets, hw, n, pitch, out_h, out_w, mean_std6, c1_w, c1_b, out);
+}
 
 // sfe_conv1_kernel (swin.hip), the stem the float entry points run, through its launcher: x fp32 NCHW [n][3][h][w] -> out [n][h / 2][w / 2][12]
-extern "C" int reid_debug_swin_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out) {
+static int debug_swin_conv1(reid_ctx* ctx, bool mirror, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out) {
     ARG_CHECK(ctx && x && n >= 1 && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && c1_w && c1_b && out);
     CTX_ENTER(ctx);
     float *dx, *dw, *db, *dout;
@@ -1135,8 +1144,32 @@ extern "C" int reid_debug_swin_conv1(reid_ctx* ctx, const float* x, int n, int h
     REID_TRY(dbg_upload(ctx, "dbgf.c1w", c1_w, (size_t)144, &dw));
     REID_TRY(dbg_upload(ctx, "dbgf.c1b", c1_b, (size_t)12, &db));
     REID_TRY(dbg_output(ctx, "dbgf.c1", nout, &dout));
-    REID_TRY(launch_sfe_conv1(ctx, dx, n, h, w, dw, db, dout));
+    REID_TRY((mirror ? launch_sfe_conv1_mirror : launch_sfe_conv1)(ctx, dx, n, h, w, dw, db, dout));
     REID_TRY(dbg_download(ctx, out, dout, nout));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+extern "C" int reid_debug_swin_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out) {
+    return debug_swin_conv1(ctx, false, x, n, h, w, c1_w, c1_b, out);
+}
+// sfe_conv1_mirror_kernel (swin_eval.hip): the same image read with reversed columns
+extern "C" int reid_debug_swin_conv1_mirror(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* out) {
+    return debug_swin_conv1(ctx, true, x, n, h, w, c1_w, c1_b, out);
+}
+
+// swin_descriptor_kernel (swin_eval.hip) through launch_swin_descriptor: e1 / e2 (nullptr: one view) [n][96], cls_w [num_class][96] ->
+// rows [0, n) x columns [0, num_class + 96) of out [out_rows][ld]; the rest of out keeps the 0xff fill (NaN)
+extern "C" int reid_debug_swin_descriptor(reid_ctx* ctx, const float* e1, const float* e2, const float* cls_w, int n, int num_class, int out_rows,
+                                          int ld, float* out) {
+    ARG_CHECK(ctx && e1 && cls_w && out && n >= 1 && num_class >= 1 && out_rows >= n && ld >= num_class + 96);
+    CTX_ENTER(ctx);
+    float *d1, *d2, *dw, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgf.e1", e1, (size_t)n * 96, &d1));
+    REID_TRY(dbg_upload(ctx, "dbgf.e2", e2, (size_t)n * 96, &d2));
+    REID_TRY(dbg_upload(ctx, "dbgf.clsw", cls_w, (size_t)num_class * 96, &dw));
+    REID_TRY(dbg_output(ctx, "dbgf.desc", (size_t)out_rows * ld, &dout));
+    REID_TRY(launch_swin_descriptor(ctx, d1, d2, dw, n, num_class, ld, dout));
+    REID_TRY(dbg_download(ctx, out, dout, (size_t)out_rows * ld));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }

@@ -235,6 +235,13 @@ int launch_sfe_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const f
 int swin_crops_check(int out_h, int out_w, const float* mean_std6);   // sizes multiples of 224, mean finite, std > 0 (REID_ERR_ARG otherwise)
 int launch_swin_crop_front(reid_ctx* ctx, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
                            const float* mean_std6, const float* c1_w, const float* c1_b, float* c1);
+// swin.hip: what the Swin descriptor entries launch from libreid_hip_swin_eval.so (swin_eval.h) - the two stems of the mirrored view
+// (arguments as the plain stems above) and the descriptor kernel: e1 / e2 (or nullptr) [n][96], cls_w [num_class][96] -> out rows of
+// num_class + 96 floats, ld floats apart
+int launch_sfe_conv1_mirror(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* c1);
+int launch_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
+                                  const float* mean_std6, const float* c1_w, const float* c1_b, float* c1);
+int launch_swin_descriptor(reid_ctx* ctx, const float* e1, const float* e2, const float* cls_w, int n, int num_class, long long ld, float* out);
 int launch_split_pack(reid_ctx* ctx, const float* x, long long rows, int C, _Float16* out, const float* d_scale = nullptr);           // fp32 [rows][C] -> f16 [rows][2C] = [xh | xl']
 int launch_split_weights(reid_ctx* ctx, const float* w, int cout, int taps, int cin, int terms, _Float16* out, const float* d_scale = nullptr);  // fp32 [cout][taps][cin] -> f16 [cout][taps][terms * cin]
 // fp16 elementwise kernels (elementwise_f16.hip)

@@ -2,6 +2,7 @@
 // Every Linear / patch-merge / 8x8 conv / ConvTranspose is a launch of the f32 MFMA GEMM (gemm_f32.hip) with fused
 // bias / GELU / residual epilogues; this file holds the kernels that are not GEMMs (stem, LayerNorm, window attention,
 // LN + GeM_1D + BN tail) and the launch sequence.  The two kernels only v2 blocks launch are in swin_v2.hip (libreid_hip_swin_v2.so, opened when v2 weights are loaded).
+// What the descriptor entries (reid_swin_descriptor_*) launch beyond the forward is in swin_eval.hip (libreid_hip_swin_eval.so).
 //
 // Cyclic shift: LayerNorm and every Linear are per-token, so the roll(-3,-3) ... roll(+3,+3) pair of a shifted block
 // (swin_transformer.py:193-194,230-231) is folded into the attention kernel's indexing alone: window position (y', x')
@@ -9,6 +10,7 @@
 #include "reid_internal.h"
 #include "swin_v2.h"
 #include "swin_crops.h"
+#include "swin_eval.h"
 #include <mutex>
 #include <math.h>
 #include <string.h>
@@ -1246,6 +1248,32 @@ static int swin_crops_api(decltype(&swin_crops_front)* out) {
     return REID_OK;
 }
 
+// libreid_hip_swin_eval.so (swin_eval.h), opened the same way on the first descriptor call (reid_swin_descriptor_*, or a harness of its
+// kernels): a process that only embeds never opens it.  Missing library or symbol: REID_ERR_STATE naming the file - there is no other path
+// to a Swin descriptor.
+struct SwinEvalApi {
+    decltype(&swin_eval_conv1_mirror) conv1_mirror = nullptr;
+    decltype(&swin_eval_crop_front_mirror) crop_front_mirror = nullptr;
+    decltype(&swin_eval_descriptor) descriptor = nullptr;
+    decltype(&swin_eval_max_classes) max_classes = nullptr;
+};
+static int swin_eval_api(const SwinEvalApi** out) {
+    static std::mutex m;
+    static SwinEvalApi api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.descriptor) {
+        void* f[4];
+        REID_TRY(open_beside_self("libreid_hip_swin_eval.so", "Swin descriptors need",
+                                  {"swin_eval_conv1_mirror", "swin_eval_crop_front_mirror", "swin_eval_max_classes", "swin_eval_descriptor"}, f));
+        api.conv1_mirror = (decltype(api.conv1_mirror))f[0];
+        api.crop_front_mirror = (decltype(api.crop_front_mirror))f[1];
+        api.max_classes = (decltype(api.max_classes))f[2];
+        api.descriptor = (decltype(api.descriptor))f[3];
+    }
+    *out = &api;
+    return REID_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ weights
 struct SwinBlockW {
     // v2: no pos; bias_t = the block's position-bias table as [head][key 49][query 64] (made at load time from the blob's
@@ -1712,6 +1740,58 @@ int launch_swin_crop_front(reid_ctx* ctx, const uint8_t* d_src, const long long*
     return REID_OK;
 }
 
+// The stems of the MIRRORED view and the descriptor (libreid_hip_swin_eval.so, swin_eval.h), through the launchers the descriptor entries
+// and the harnesses (reid_debug_swin_conv1_mirror / _crop_front_mirror / _descriptor) share.  Same arguments and checks as the launchers
+// of the plain stems above; c1 then goes to swin_body with x == nullptr.
+int launch_sfe_conv1_mirror(reid_ctx* ctx, const float* x, int n, int h, int wd, const float* c1_w, const float* c1_b, float* c1) {
+    if (!x || !c1_w || !c1_b || !c1 || n < 1 || h < 2 || wd < 2 || (h & 1) || (wd & 1)) {
+        reid_set_error("launch_sfe_conv1_mirror: bad arguments (%d images of %d x %d)", n, h, wd);
+        return REID_ERR_ARG;
+    }
+    const SwinEvalApi* ev;
+    REID_TRY(swin_eval_api(&ev));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * wd * (12 + 12));
+    const hipError_t e = ev->conv1_mirror(ctx->stream, x, n, h, wd, c1_w, c1_b, c1);
+    prof_end(ctx);
+    HIP_TRY(e);
+    return REID_OK;
+}
+
+int launch_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int wd, int pitch,
+                                  const float* mean_std6, const float* c1_w, const float* c1_b, float* c1) {
+    if (!d_src || !d_off || !d_hw || !mean_std6 || !c1_w || !c1_b || !c1 || n < 1 || h < 224 || wd < 224 || h % 224 || wd % 224 || pitch < 0) {
+        reid_set_error("launch_swin_crop_front_mirror: bad arguments (%d windows to %d x %d, pitch %d)", n, h, wd, pitch);
+        return REID_ERR_ARG;
+    }
+    const SwinEvalApi* ev;
+    REID_TRY(swin_eval_api(&ev));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * wd * 12);
+    const hipError_t e = ev->crop_front_mirror(ctx->stream, d_src, d_off, d_hw, n, h, wd, pitch, mean_std6, c1_w, c1_b, c1);
+    prof_end(ctx);
+    HIP_TRY(e);
+    return REID_OK;
+}
+
+// e1 / e2 (or nullptr) [n][96], cls_w [num_class][96] -> out rows of num_class + 96 floats, ld floats apart; all on the device
+int launch_swin_descriptor(reid_ctx* ctx, const float* e1, const float* e2, const float* cls_w, int n, int num_class, long long ld, float* out) {
+    const SwinEvalApi* ev;
+    REID_TRY(swin_eval_api(&ev));
+    if (!e1 || !cls_w || !out || n < 1 || num_class < 1 || ld < (long long)num_class + 96 || (((uintptr_t)e1 | (uintptr_t)e2 | (uintptr_t)cls_w) & 15)) {
+        reid_set_error("launch_swin_descriptor: bad arguments (%d rows, %d classes, row pitch %lld; operands 16-byte aligned)", n, num_class, ld);
+        return REID_ERR_ARG;
+    }
+    if (num_class > ev->max_classes()) {
+        reid_set_error("Swin descriptor: %d classes, the descriptor kernel holds at most %d (both views' logits stay in LDS)", num_class,
+                       ev->max_classes());
+        return REID_ERR_ARG;
+    }
+    prof_begin(ctx, REID_K_ELEMENTWISE, 2.0 * n * num_class * 96 * (e2 ? 2 : 1), (double)n * ((double)num_class * 96 + num_class + 96 * 3) * 4);
+    const hipError_t e = ev->descriptor(ctx->stream, e1, e2, cls_w, n, num_class, ld, out);
+    prof_end(ctx);
+    HIP_TRY(e);
+    return REID_OK;
+}
+
 static int swin_body(reid_ctx* ctx, const SwinWeights& w, const float* x, float* c1, int n, int h, int wd, float* d_emb, float* d_logits);
 
 static int swin_c1(reid_ctx* ctx, int n, int h, int wd, float** c1) {
@@ -2114,4 +2194,194 @@ extern "C" int reid_swin_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame, int
     RaggedSrc src{};
     REID_TRY(src.frame(frame, fh, fw, boxes_xyxy, n));
     return swin_embed_windows(ctx, src, out_h, out_w, mean_std6, emb, logits);
+}
+
+// ------------------------------------------------------------------------------------------------ descriptors
+// The evaluation script's retrieval descriptor for a Swin (reid/image_reid_inference.py --backbone swin_v1 | swin_v2, :145-152, :202-208):
+// inference_efficient runs model(cat(img, flip(img))) (:112-123, with --sie the camera index of an image as the view_index of BOTH its
+// views, :117-120) and SwinTransformer.forward returns (logits, x_norm) in eval mode (swin_transformer.py:422-423), so a row is
+// [normalize(logits) | normalize(x_norm)], averaged over the views and renormalised (:252-253).  Per pass: the forward of the plain view,
+// the forward of the mirrored view from a stem that reads the source backwards (no mirrored copy), then swin_descriptor_kernel, which
+// runs the classifier itself - all three from libreid_hip_swin_eval.so.
+namespace {
+// whatever side indices are pending when a descriptor entry leaves, on any path, are dropped
+struct SidePendingClear {
+    reid_ctx* ctx;
+    ~SidePendingClear() {
+        ctx->side_idx.clear();
+        ctx->side_cursor = 0;
+    }
+};
+
+struct SwinDescPlan {
+    const SwinWeights* sw = nullptr;
+    std::vector<int32_t> side;   // the call's side indices, one per image (empty: none)
+    int nc = 0;
+};
+}  // namespace
+
+// Everything a descriptor call can be refused for, with nothing queued: weights with a classifier and the side libraries
+// (REID_ERR_STATE), the classifier's size and the side indices' count and range (REID_ERR_ARG).  Takes the pending side indices over.
+static int swin_descriptor_ready(reid_ctx* ctx, int n, bool crops, SwinDescPlan* p) {
+    p->sw = swin_find(ctx);
+    if (!p->sw || !p->sw->loaded) {
+        reid_set_error("reid_swin_descriptor_*: call reid_swin_load first");
+        return REID_ERR_STATE;
+    }
+    if (!p->sw->cls_w || p->sw->num_class <= 0) {
+        reid_set_error("reid_swin_descriptor_*: the loaded weights have no classifier (cls.w), the descriptor needs the logits");
+        return REID_ERR_STATE;
+    }
+    p->nc = p->sw->num_class;
+    const SwinEvalApi* ev;
+    REID_TRY(swin_eval_api(&ev));
+    if (crops) {
+        decltype(&swin_crops_front) front;
+        REID_TRY(swin_crops_api(&front));
+    }
+    if (p->nc > ev->max_classes()) {
+        reid_set_error("reid_swin_descriptor_*: %d classes, the descriptor kernel holds at most %d (both views' logits stay in LDS)", p->nc,
+                       ev->max_classes());
+        return REID_ERR_ARG;
+    }
+    if ((uintptr_t)p->sw->cls_w & 15) {
+        reid_set_error("reid_swin_descriptor_*: cls.w must lie 16-byte aligned in the blob (reid_amd.weights.pack_swin places it so)");
+        return REID_ERR_ARG;
+    }
+    if (ctx->side_idx.empty()) return REID_OK;
+    const size_t pending = ctx->side_idx.size() - ctx->side_cursor;
+    if (p->sw->views <= 0) {
+        reid_set_error("reid_swin_descriptor_*: side indices are pending (reid_ctx_set_side_index) but the loaded weights carry no table for them");
+        return REID_ERR_STATE;
+    }
+    if (pending != (size_t)n) {
+        reid_set_error("reid_swin_descriptor_*: %d images but %zu side indices are pending", n, pending);
+        return REID_ERR_ARG;
+    }
+    p->side.assign(ctx->side_idx.begin() + ctx->side_cursor, ctx->side_idx.end());
+    for (int i = 0; i < n; ++i)
+        if (p->side[i] >= p->sw->views) {
+            reid_set_error("reid_swin_descriptor_*: side index %d of image %d is outside the table of %d rows", p->side[i], i, p->sw->views);
+            return REID_ERR_ARG;
+        }
+    return REID_OK;
+}
+
+// One pass, images [i, i + m) of the call.  view(v, c1, e) queues the forward of view v (0 plain, 1 mirrored) into e [m][96], c1 being the
+// pass's first-convolution workspace.  Each view is handed the pass's side indices afresh: swin_body takes them (ctx_take_side) once per
+// forward, and the same index serves the plain and the mirrored view of an image.
+template <class View>
+static int swin_descriptor_pass(reid_ctx* ctx, const SwinDescPlan& p, int i, int m, int h, int wd, int flip_tta, float* e1, float* e2, View view,
+                                float* d_out) {
+    float* c1;
+    REID_TRY(swin_c1(ctx, m, h, wd, &c1));
+    for (int v = 0; v < (flip_tta ? 2 : 1); ++v) {
+        if (!p.side.empty()) {
+            ctx->side_idx.assign(p.side.begin() + i, p.side.begin() + i + m);
+            ctx->side_cursor = 0;
+        }
+        REID_TRY(view(v, c1, v ? e2 : e1));
+    }
+    return launch_swin_descriptor(ctx, e1, flip_tta ? e2 : nullptr, p.sw->cls_w, m, p.nc, p.nc + 96, d_out);
+}
+
+// the two x_norm buffers of a pass
+static int swin_descriptor_ws(reid_ctx* ctx, int pass, int flip_tta, float** e1, float** e2) {
+    *e2 = nullptr;
+    REID_TRY(ctx_ws(ctx, "swd.e1", (size_t)pass * 96 * 4, (void**)e1));
+    if (flip_tta) REID_TRY(ctx_ws(ctx, "swd.e2", (size_t)pass * 96 * 4, (void**)e2));
+    return REID_OK;
+}
+
+// a view of float images: the plain one through swin_body's own stem, the mirrored one through sfe_conv1_mirror_kernel into c1
+static int swin_view_f32(reid_ctx* ctx, const SwinWeights& w, int v, const float* d_x, float* c1, int m, int h, int wd, float* e) {
+    if (v == 0) return swin_body(ctx, w, d_x, c1, m, h, wd, e, nullptr);
+    REID_TRY(launch_sfe_conv1_mirror(ctx, d_x, m, h, wd, w.c1_w, w.c1_b, c1));
+    return swin_body(ctx, w, nullptr, c1, m, h, wd, e, nullptr);
+}
+
+extern "C" int reid_swin_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out) {
+    ARG_CHECK(ctx);
+    SidePendingClear drop{ctx};
+    ARG_CHECK(d_x && d_out && n >= 0 && h > 0 && w > 0 && h % 224 == 0 && w % 224 == 0);
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    SwinDescPlan p;
+    REID_TRY(swin_descriptor_ready(ctx, n, false, &p));
+    const int pass = swin_pass(ctx);
+    const size_t img = (size_t)3 * h * w, width = (size_t)p.nc + 96;
+    float *e1, *e2;
+    REID_TRY(swin_descriptor_ws(ctx, n < pass ? n : pass, flip_tta, &e1, &e2));
+    return embed_dev_passes(n, pass, [&](int i, int m) -> int {
+        const float* xi = d_x + (size_t)i * img;
+        return swin_descriptor_pass(
+            ctx, p, i, m, h, w, flip_tta, e1, e2, [&](int v, float* c1, float* e) -> int { return swin_view_f32(ctx, *p.sw, v, xi, c1, m, h, w, e); },
+            d_out + (size_t)i * width);
+    });
+}
+
+extern "C" int reid_swin_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, int h, int w, int flip_tta, float* out) {
+    ARG_CHECK(ctx);
+    SidePendingClear drop{ctx};
+    ARG_CHECK(x && out && n >= 0 && h > 0 && w > 0 && h % 224 == 0 && w % 224 == 0);
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    SwinDescPlan p;
+    REID_TRY(swin_descriptor_ready(ctx, n, false, &p));
+    const int pass = swin_pass(ctx);
+    const size_t img = (size_t)3 * h * w;
+    float *d_in, *e1, *e2;
+    EmbedOut o{out, nullptr, p.nc + 96, 0};
+    REID_TRY(ctx_ws(ctx, "io.in", (size_t)n * img * 4, (void**)&d_in));
+    REID_TRY(o.alloc(ctx, "swd", n, 0, false));
+    REID_TRY(swin_descriptor_ws(ctx, n < pass ? n : pass, flip_tta, &e1, &e2));
+    return embed_host(
+        ctx, n, pass,
+        [&](int i, int m, hipStream_t s) -> int {
+            HIP_TRY(hipMemcpyAsync(d_in + (size_t)i * img, x + (size_t)i * img, (size_t)m * img * 4, hipMemcpyHostToDevice, s));
+            return REID_OK;
+        },
+        [&](int i, int m, float* d_row, float*) -> int {
+            const float* xi = d_in + (size_t)i * img;
+            return swin_descriptor_pass(
+                ctx, p, i, m, h, w, flip_tta, e1, e2,
+                [&](int v, float* c1, float* e) -> int { return swin_view_f32(ctx, *p.sw, v, xi, c1, m, h, w, e); }, d_row);
+        },
+        o);
+}
+
+// uint8 crops in: the plain view through swin_crop_front_kernel, the mirrored one through swin_crop_front_mirror_kernel, which reverses
+// the RESIZED image's columns - Resize -> flip -> ToTensor -> Normalize, the order of the reference's transforms.  Bit-identical to
+// reid_swin_descriptor_f32_nchw on the same crops resized and normalised in fp32 on the host.
+extern "C" int reid_swin_descriptor_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                              int out_w, const float* mean_std6, int flip_tta, float* out) {
+    ARG_CHECK(ctx);
+    SidePendingClear drop{ctx};
+    ARG_CHECK(packed && offsets && hw && out && n >= 0);
+    REID_TRY(swin_crops_args(out_h, out_w, &mean_std6));
+    RaggedSrc src{packed, offsets, hw, n};
+    REID_TRY(src.check());
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    SwinDescPlan p;
+    REID_TRY(swin_descriptor_ready(ctx, n, true, &p));
+    const int pass = swin_pass(ctx);
+    float *e1, *e2;
+    EmbedOut o{out, nullptr, p.nc + 96, 0};
+    REID_TRY(src.alloc(ctx, "io"));
+    REID_TRY(o.alloc(ctx, "swd", n, 0, false));
+    REID_TRY(swin_descriptor_ws(ctx, n < pass ? n : pass, flip_tta, &e1, &e2));
+    return embed_host(
+        ctx, n, pass, [&](int i, int m, hipStream_t s) -> int { return src.up(i, m, s); },
+        [&](int i, int m, float* d_row, float*) -> int {
+            return swin_descriptor_pass(
+                ctx, p, i, m, out_h, out_w, flip_tta, e1, e2,
+                [&](int v, float* c1, float* e) -> int {
+                    REID_TRY((v ? launch_swin_crop_front_mirror : launch_swin_crop_front)(ctx, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, out_h,
+                                                                                         out_w, src.pitch, mean_std6, p.sw->c1_w, p.sw->c1_b, c1));
+                    return swin_body(ctx, *p.sw, nullptr, c1, m, out_h, out_w, e, nullptr);
+                },
+                d_row);
+        },
+        o);
 }

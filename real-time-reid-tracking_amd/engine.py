@@ -244,6 +244,45 @@ class Engine:
                                                 _ptr(lg)))
         return self._ret(emb, lg, logits)
 
+    # ---- Swin descriptors (the evaluation script's --backbone swin_v1 | swin_v2, reid/image_reid_inference.py:145-152)
+    def _swin_descriptor_width(self):
+        """num_class + 96 of the loaded Swin weights; ValueError when nothing with a classifier is loaded."""
+        nc = getattr(self, "swin_num_class", 0)
+        if nc <= 0:
+            raise ValueError("a Swin descriptor needs loaded Swin weights with a classifier (Engine.load_swin)")
+        return nc + self.swin_dim
+
+    def swin_descriptor_f32_nchw(self, x, flip_tta=True):
+        """float32 [n,3,h,w] (h, w multiples of 224, normalised by the caller) -> float32 [n, num_class + 96] retrieval descriptor,
+        [normalize(logits) | normalize(x_norm)] - the order of the reference's Swin (swin_transformer.py:422-423) - averaged with
+        the mirrored image's and renormalised when ``flip_tta``.  Pending side indices (set_side_index) serve both views."""
+        x = _f32(x)
+        if x.ndim != 4 or x.shape[1] != 3 or x.shape[2] <= 0 or x.shape[3] <= 0 or x.shape[2] % 224 or x.shape[3] % 224:
+            raise ValueError("swin_descriptor_f32_nchw expects float32[n,3,224k,224m], got %s" % (x.shape,))
+        out = np.empty((x.shape[0], self._swin_descriptor_width()), np.float32)
+        check(self.lib.reid_swin_descriptor_f32_nchw(self.h, _ptr(x), x.shape[0], x.shape[2], x.shape[3], int(bool(flip_tta)), _ptr(out)))
+        return out
+
+    def swin_descriptor_dev(self, d_x, n, h, w, flip_tta, d_out):
+        """The same on device pointers: d_x fp32 [n,3,h,w] -> d_out fp32 [n, num_class + 96] (reid_swin_descriptor_f32_nchw_dev)."""
+        n, h, w = int(n), int(h), int(w)
+        if n < 0 or h <= 0 or w <= 0 or h % 224 or w % 224:
+            raise ValueError("swin_descriptor_dev expects n >= 0 images of 224k x 224m, got n = %d, h = %d, w = %d" % (n, h, w))
+        if n and (not d_x or not d_out):
+            raise ValueError("swin_descriptor_dev: null device pointer")
+        check(self.lib.reid_swin_descriptor_f32_nchw_dev(self.h, C.c_void_p(d_x), n, h, w, int(bool(flip_tta)), C.c_void_p(d_out)))
+
+    def swin_descriptor_ragged_u8(self, crops, size=(448, 224), mean_std=None, flip_tta=True):
+        """list of uint8[h_i,w_i,3] -> float32 [n, num_class + 96]: crops resized to ``size`` = (H, W) and normalised as
+        swin_embed_ragged_u8; the mirrored view is the RESIZED crop mirrored (Resize -> flip -> ToTensor -> Normalize)."""
+        h, w, ms = self._swin_crop_args(size, mean_std)
+        crops = list(crops)
+        n = len(crops)
+        out = np.empty((n, self._swin_descriptor_width()), np.float32)
+        src, offs, hw, _keep = self._pack_ragged(crops)
+        check(self.lib.reid_swin_descriptor_ragged_u8(self.h, src, _ptr(offs), _ptr(hw), n, h, w, _ptr(ms), int(bool(flip_tta)), _ptr(out)))
+        return out
+
     # ---- embedding
     def _outs(self, n, want_logits, dim=None, num_class=None):
         """Host arrays an embed call fills: emb[n, dim] and logits[n, num_class] or None (default sizes: the ResNet18-SE family's)."""
@@ -701,9 +740,10 @@ class Engine:
                                                       C.c_float(-1.0 if gate is None else gate), _ptr(out)))
         return out
 
-    def debug_swin_crop_front(self, packed, offsets, hw, c1_w, c1_b, size=(224, 224), mean_std=None, pitch=0):
+    def debug_swin_crop_front(self, packed, offsets, hw, c1_w, c1_b, size=(224, 224), mean_std=None, pitch=0, mirror=False):
         """swin_crop_front_kernel alone through its launcher (reid_debug_swin_crop_front): windows as debug_resize_norm, ``size`` = (H, W),
-        mean_std = (mean[3], std[3]) (None: ImageNet), c1_w [12, 2, 2, 3] / c1_b [12] -> fp32 [n, H / 2, W / 2, 12]."""
+        mean_std = (mean[3], std[3]) (None: ImageNet), c1_w [12, 2, 2, 3] / c1_b [12] -> fp32 [n, H / 2, W / 2, 12].  ``mirror``:
+        swin_crop_front_mirror_kernel (reid_debug_swin_crop_front_mirror), the resized image's columns reversed."""
         h_out, w_out, ms = self._swin_crop_args(size, mean_std)
         if ms is None:
             ms = _f32([0.485, 0.456, 0.406, 0.229, 0.224, 0.225])
@@ -718,18 +758,38 @@ class Engine:
         if c1_w.size != 144 or c1_b.size != 12:
             raise ValueError("debug_swin_crop_front expects c1_w[12,2,2,3] and c1_b[12]")
         out = np.empty((n, h_out // 2, w_out // 2, 12), np.float32)
-        check(_ffi.debug_lib().reid_debug_swin_crop_front(self.h, _ptr(packed), _ptr(offsets), _ptr(hw), C.c_int(n), C.c_int(int(pitch)),
-                                                          C.c_int(h_out), C.c_int(w_out), _ptr(ms), _ptr(c1_w), _ptr(c1_b), _ptr(out)))
+        fn = _ffi.debug_lib().reid_debug_swin_crop_front_mirror if mirror else _ffi.debug_lib().reid_debug_swin_crop_front
+        check(fn(self.h, _ptr(packed), _ptr(offsets), _ptr(hw), C.c_int(n), C.c_int(int(pitch)), C.c_int(h_out), C.c_int(w_out), _ptr(ms), _ptr(c1_w),
+                 _ptr(c1_b), _ptr(out)))
         return out
 
-    def debug_swin_conv1(self, x, c1_w, c1_b):
-        """sfe_conv1_kernel alone through its launcher (reid_debug_swin_conv1): x fp32 [n, 3, h, w] -> fp32 [n, h / 2, w / 2, 12]."""
+    def debug_swin_conv1(self, x, c1_w, c1_b, mirror=False):
+        """sfe_conv1_kernel alone through its launcher (reid_debug_swin_conv1): x fp32 [n, 3, h, w] -> fp32 [n, h / 2, w / 2, 12].
+        ``mirror``: sfe_conv1_mirror_kernel (reid_debug_swin_conv1_mirror), the image read with reversed columns."""
         x, c1_w, c1_b = _f32(x), _f32(c1_w).reshape(-1), _f32(c1_b).reshape(-1)
         n, c, h, w = x.shape
         if c != 3 or h % 2 or w % 2 or c1_w.size != 144 or c1_b.size != 12:
             raise ValueError("debug_swin_conv1 expects x[n,3,2k,2m], c1_w[12,2,2,3] and c1_b[12]")
         out = np.empty((n, h // 2, w // 2, 12), np.float32)
-        check(_ffi.debug_lib().reid_debug_swin_conv1(self.h, _ptr(x), C.c_int(n), C.c_int(h), C.c_int(w), _ptr(c1_w), _ptr(c1_b), _ptr(out)))
+        fn = _ffi.debug_lib().reid_debug_swin_conv1_mirror if mirror else _ffi.debug_lib().reid_debug_swin_conv1
+        check(fn(self.h, _ptr(x), C.c_int(n), C.c_int(h), C.c_int(w), _ptr(c1_w), _ptr(c1_b), _ptr(out)))
+        return out
+
+    def debug_swin_descriptor(self, e1, e2, cls_w, out_rows=None, ld=None):
+        """swin_descriptor_kernel alone through its launcher (reid_debug_swin_descriptor): e1, e2 (None: one view) fp32 [n, 96], cls_w
+        [num_class, 96] -> fp32 [out_rows, ld] whose rows [0, n) x columns [0, num_class + 96) hold the descriptors; the rest is NaN."""
+        e1, cls_w = _f32(e1), _f32(cls_w)
+        e2 = None if e2 is None else _f32(e2)
+        if e1.ndim != 2 or e1.shape[1] != 96 or e1.shape[0] < 1 or cls_w.ndim != 2 or cls_w.shape[1] != 96 or cls_w.shape[0] < 1 or \
+                (e2 is not None and e2.shape != e1.shape):
+            raise ValueError("debug_swin_descriptor expects e1 (and e2) [n,96] and cls_w [num_class,96]")
+        n, nc = e1.shape[0], cls_w.shape[0]
+        out_rows, ld = n if out_rows is None else int(out_rows), nc + 96 if ld is None else int(ld)
+        if out_rows < n or ld < nc + 96:
+            raise ValueError("debug_swin_descriptor: out_rows >= n and ld >= num_class + 96")
+        out = np.empty((out_rows, ld), np.float32)
+        check(_ffi.debug_lib().reid_debug_swin_descriptor(self.h, _ptr(e1), _ptr(e2), _ptr(cls_w), C.c_int(n), C.c_int(nc), C.c_int(out_rows),
+                                                          C.c_int(ld), _ptr(out)))
         return out
 
     def debug_maxpool(self, x):

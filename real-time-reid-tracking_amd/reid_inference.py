@@ -1,5 +1,6 @@
 """The evaluation script's chain on the device - counterpart of reid/image_reid_inference.py (SURVEY.md section 8c,
-"Python harness row"), for the seres18 / cares18 / emares18 `.pt` path without side information.
+"Python harness row"), for the seres18 / cares18 / emares18 `.pt` path without side information (``arch="seres18"``, the default) and
+for the script's ``--backbone swin_v1 | swin_v2`` (:145-152, :202-208; ``arch="swin"``), with ``--sie`` as ``use_side``.
 
 Reference flow (reid/image_reid_inference.py):
   :78-135   inference_efficient   model(cat(img, flipped img)) -> cat(normalize(emb), normalize(logits)), the two halves apart
@@ -18,6 +19,11 @@ host there (`dists.cpu().numpy()`, :297) and stays a host call here - clustering
 so the Jaccard matrix is downloaded once for it; ``cluster_fn`` replaces it.  Images enter as float32 [n,3,256,128] after the
 caller's transform (the script's torchvision transforms are data loading, not this path).
 
+With ``arch="swin"`` the descriptor link is ``reid_swin_descriptor_f32_nchw_dev``: images are float32 [n,3,h,w] with h, w multiples of
+224 (the script resizes to 448x224, data_transforms.py:78-84), a row is [normalize(logits) | normalize(x_norm)] - the Swin returns
+(logits, x_norm), swin_transformer.py:422-423 - and is num_class + 96 wide (``reid_swin_dims``); every later link takes that width as it
+is.  ``use_side`` hands the cameras over as the view indices of both views (inference_efficient :117-120, model(img, cam.repeat(2))).
+
 The Market-1501 attribute distance (:278-283, needs the dataset's .mat file) is not part of this harness.
 """
 import numpy as np
@@ -32,21 +38,62 @@ def dbscan_pseudo_labels(dists, eps=0.5, min_samples=5):
     return DBSCAN(eps=eps, min_samples=min_samples, metric="precomputed", n_jobs=-1).fit_predict(dists)
 
 
-def inference_efficient(engine, images, d_out, flip=True, bs=1024):
+ARCHS = ("seres18", "swin")
+
+
+def _descriptor_width(engine, arch):
+    """Width of a descriptor row of ``arch`` on this engine; ValueError for an unknown arch or weights without a classifier."""
+    if arch not in ARCHS:
+        raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
+    if arch == "swin":
+        nc, dim = getattr(engine, "swin_num_class", 0), getattr(engine, "swin_dim", 0)
+        if nc <= 0 or dim <= 0:
+            raise ValueError("arch='swin' needs Swin weights with a classifier on the engine (Engine.load_swin)")
+        return dim + nc
+    return engine.embed_dim + engine.num_class
+
+
+def _check_images(images, arch):
+    images = np.asarray(images)
+    if arch == "swin":
+        if images.ndim != 4 or images.shape[1] != 3 or images.shape[2] <= 0 or images.shape[3] <= 0 or images.shape[2] % 224 or \
+                images.shape[3] % 224:
+            raise ValueError("images must be float32 [n,3,h,w] with h, w multiples of 224, got %s" % (images.shape,))
+    elif images.ndim != 4 or images.shape[1:] != (3, IMG_H, IMG_W):
+        raise ValueError("images must be float32 [n,3,%d,%d], got %s" % (IMG_H, IMG_W, images.shape))
+    return images
+
+
+def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None):
     """Descriptors of ``images`` (float32 [n,3,256,128], host) into the device rows ``d_out`` (pointer to [n, 512 + num_class]
     fp32): upload in batches of ``bs`` images, one ``reid_descriptor_f32_nchw_dev`` per batch.  Unlike the reference function
-    (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253)."""
-    images = np.asarray(images)
-    if images.ndim != 4 or images.shape[1:] != (3, IMG_H, IMG_W):
-        raise ValueError("images must be float32 [n,3,%d,%d], got %s" % (IMG_H, IMG_W, images.shape))
+    (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253).
+
+    ``arch="swin"``: images float32 [n,3,h,w], h, w multiples of 224, rows [n, num_class + 96] through
+    ``reid_swin_descriptor_f32_nchw_dev``; ``view_index`` (one per image; ``arch="swin"`` only) is the side index of both views."""
+    width = _descriptor_width(engine, arch)
+    images = _check_images(images, arch)
     n = images.shape[0]
-    width = engine.embed_dim + engine.num_class
-    stage = DevArray(engine, (min(bs, max(n, 1)), 3, IMG_H, IMG_W), np.float32)
+    if int(bs) < 1:
+        raise ValueError("bs must be at least 1, got %r" % (bs,))
+    if view_index is not None:
+        if arch != "swin":
+            raise ValueError("view_index is the Swin's side information; arch=%r takes none here" % (arch,))
+        view_index = np.asarray(view_index).reshape(-1)
+        if view_index.shape[0] != n or (n and (view_index.min() < 0 or view_index.max() >= 2 ** 31)):
+            raise ValueError("view_index must hold one non-negative index per image (%d), got %d" % (n, view_index.shape[0]))
+        view_index = view_index.astype(np.int32)
+    stage = DevArray(engine, (min(bs, max(n, 1)),) + images.shape[1:], np.float32)
     try:
         for i in range(0, n, bs):
             part = np.ascontiguousarray(images[i:i + bs], np.float32)
             engine.h2d(stage.ptr, part)
-            engine.descriptor_dev(stage.ptr, part.shape[0], flip, d_out + i * width * 4)
+            if arch == "swin":
+                if view_index is not None:
+                    engine.set_side_index(view_index[i:i + bs])
+                engine.swin_descriptor_dev(stage.ptr, part.shape[0], part.shape[2], part.shape[3], flip, d_out + i * width * 4)
+            else:
+                engine.descriptor_dev(stage.ptr, part.shape[0], flip, d_out + i * width * 4)
         engine.sync()
     finally:
         stage.free()
@@ -55,23 +102,30 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024):
 
 def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, query_images, query_labels, query_cams,
                   query_seqs, num_gallery_cams=None, eps=0.5, la=0.05, k1=20, k2=6, flip=True, cluster_fn=None, taps=None,
-                  verbose=True, device=0, engine=None):
+                  verbose=True, device=0, engine=None, arch="seres18", use_side=False):
     """(CMC float32 [ng], mAP float) of the script's chain for one gallery / query pair; weights must be loaded on the engine
     (``Engine.load_seres18`` / ``build_model``).  ``taps`` (a dict) receives host copies of the intermediates the
     reference-generated fixture holds: "desc", "debiased", "jaccard", "pseudo_labels", "smoothed".
-    ``cluster_fn(dists float32 [N,N]) -> int labels [N]`` (-1 = noise) replaces the DBSCAN call."""
+    ``cluster_fn(dists float32 [N,N]) -> int labels [N]`` (-1 = noise) replaces the DBSCAN call.
+    ``arch="swin"``: the chain on the loaded Swin weights (``Engine.load_swin``), images float32 [n,3,h,w] with h, w multiples of 224;
+    ``use_side`` (the script's --sie, ``arch="swin"`` only) passes each image's camera as the view index of both its views."""
+    if arch not in ARCHS:
+        raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
+    if use_side and arch != "swin":
+        raise ValueError("use_side is the Swin's side information (--sie); arch=%r takes none here" % (arch,))
     eng = engine or get_engine(device)
     gl, gc, gs = (np.ascontiguousarray(a, np.int64).reshape(-1) for a in (gallery_labels, gallery_cams, gallery_seqs))
     ql, qc, qs = (np.ascontiguousarray(a, np.int64).reshape(-1) for a in (query_labels, query_cams, query_seqs))
     ng, nq = len(gl), len(ql)
     if len(gallery_images) != ng or len(query_images) != nq or ng < 1 or nq < 1:
         raise ValueError("images and labels disagree: %d/%d gallery, %d/%d query" % (len(gallery_images), ng, len(query_images), nq))
-    n, width = ng + nq, eng.embed_dim + eng.num_class
+    gallery_images, query_images = _check_images(gallery_images, arch), _check_images(query_images, arch)
+    n, width = ng + nq, _descriptor_width(eng, arch)
     merged = DevArray(eng, (n, width), np.float32)
     dists = DevArray(eng, (n, n), np.float32)
     try:
-        inference_efficient(eng, gallery_images, merged.ptr, flip)
-        inference_efficient(eng, query_images, merged.row_ptr(ng), flip)
+        inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None)
+        inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None)
         if taps is not None:
             taps["desc"] = merged.numpy()
         merged_cams = np.concatenate([gc, qc]).astype(np.int32)
