@@ -245,6 +245,33 @@ int reid_diou_cost(reid_ctx* ctx, const double* tracks_t4, int t, const double* 
  * normalised by the caller's transform; out: fp32 [n][512 + num_class] (reid_seres18_dims). */
 int reid_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, int flip_tta, float* out);
 int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, float* d_out);
+/* The same descriptors from uint8 images as the dataset stores them: the evaluation script's own transform runs on the device.
+ * reid/data_transforms.py:56-127 is transforms.Resize((H, W)) on an RGB PIL image - Pillow's 8-bit Image.resize((W, H), BILINEAR): two
+ * passes of 22-bit fixed-point arithmetic with the support widened by the scale when an axis shrinks, the horizontal pass first into a
+ * uint8 image, the vertical pass on that rounded image - then ToTensor and Normalize(mean, std); the mirrored view flips the resized
+ * image (:130-209).  Integer arithmetic has one answer, so the resized image equals Pillow's byte for byte, and the normalised float is a
+ * lookup in a [3][256] table (v / 255 - mean) / std built on the host in fp32 with two true divisions, the bits of torch's.
+ * packed / offsets / hw: n RGB HWC images as reid_embed_ragged_u8 takes crops (image i is hw[2i] x hw[2i + 1] pixels at byte offsets[i] of
+ * packed; images may share bytes and lie in any order); mean_std6 = mean[3] | std[3], NULL = ImageNet.  Host in, host out, passes
+ * pipelined as the other host entries.
+ *   reid_descriptor_images_u8       seres18 / cares18 / emares18: Resize((256, 128)); out fp32 [n][512 + num_class], in every precision
+ *                                   bit-identical to reid_descriptor_f32_nchw on the same images preprocessed on the host (flip_tta: the
+ *                                   resized image mirrored).  n pending side indices (the camera of each image) serve both views of
+ *                                   an image, as the script's model(img, cam.repeat(2)): what that entry computes when it is given the
+ *                                   indices twice; another count is REID_ERR_ARG.
+ *   reid_swin_descriptor_images_u8  Swin v1 / v2: out_h, out_w multiples of 224 (the script: 448x224, or 224x224 for VeRi); out fp32
+ *                                   [n][num_class + 96], bit-identical to reid_swin_descriptor_f32_nchw likewise; n pending side indices
+ *                                   serve both views of an image.  Refusals as reid_swin_descriptor_ragged_u8.
+ * Limits: 1 <= h, w <= 4096 per source image (pil_resize_max_side() of the side library; the int32 accumulator and the coefficient
+ * tables are sized for it).  Workspace beyond the float entry's: per pass of p images the uint8 intermediates, sum of h_i * out_w * 3
+ * bytes (at most p * 4096 * out_w * 3), the pass's fp32 images, p * 3 * out_h * out_w * 4 bytes, and the call's coefficient tables, at
+ * most (2 * in + 5 * out) * 4 bytes per distinct (in, out) pair of an axis.  A larger source is REID_ERR_ARG naming the limit, an image
+ * without pixels REID_ERR_ARG, both before anything is queued; n == 0 returns REID_OK; nothing pending stays pending.
+ * The kernels are libreid_hip_pil_resize.so, which must lie beside this library (REID_ERR_STATE naming it otherwise). */
+int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, const float* mean_std6,
+                              int flip_tta, float* out);
+int reid_swin_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,
+                                   const float* mean_std6, int flip_tta, float* out);
 /* diminish_camera_bias, reid/inference_utils.py:5-15, in place on x fp32 [n][d]: per camera id c (cams is a host int32[n],
  * ids >= 0) rows X_c <- normalize_rows((X_c - mean X_c) inverse(X_c^T X_c + n_c*la*I)^T).  The inverse is a Newton-Schulz
  * iteration of fp32 GEMMs that stops when the residual reaches the fp32 noise floor (iters = upper bound, <= 0: 40). */

@@ -134,6 +134,12 @@ int reid_debug_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* packed, cons
                                       int out_w, const float* mean_std6, const float* c1_w, const float* c1_b, float* out);
 int reid_debug_swin_descriptor(reid_ctx* ctx, const float* e1, const float* e2, const float* cls_w, int n, int num_class, int out_rows, int ld,
                                float* out);
+/* The two kernels of libreid_hip_pil_resize.so (csrc/pil_resize.hip; tests/test_gpu_pil_resize.py) through the launcher the *_images_u8
+ * entry points call, one launch of all n images: packed / offsets / hw as reid_descriptor_images_u8, out_h and out_w from 1 to 1024,
+ * mean_std6 NULL = ImageNet -> u8_out [n][out_h][out_w][3], Pillow's Image.resize((out_w, out_h), BILINEAR) (may be NULL), and f32_out
+ * [n][3][out_h][out_w], ToTensor + Normalize of it.  A float the launch leaves alone reads NaN.  Returns the fault status. */
+int reid_debug_pil_resize(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int out_h, int out_w,
+                          const float* mean_std6, uint8_t* u8_out, float* f32_out);
 /* maxpool: MaxPool(3, 2, 1) of x NHWC [n][h][w][c] -> out [n][(h - 1) / 2 + 1][(w - 1) / 2 + 1][c], fp32 (f16 = 0) or raw f16 bits. */
 int reid_debug_maxpool(reid_ctx* ctx, int f16, const void* x, int n, int h, int w, int c, void* out);
 /* The two kernels of the Swin "v2" blocks alone (csrc/swin_v2.hip; correctness harnesses, tests/test_gpu_swin_v2.py), each through the

@@ -409,6 +409,35 @@ class SwinT:
             if idx is not None:
                 get_engine(self._device).set_side_index(None)
 
+    def descriptor_images(self, images, size=(448, 224), view_index=None, flip_tta=True):
+        """descriptor() from uint8 HxWx3 images of any sizes as the dataset stores them: the evaluation script's transform - PIL's
+        antialiased Resize to ``size`` = (H, W) (multiples of 224), ToTensor, ImageNet Normalize (reid/data_transforms.py:56-127) -
+        runs on the device, and the rows are bit-identical to descriptor() on the images preprocessed with PIL on the host."""
+        images = list(images)
+        Engine._swin_crop_args(size, None)                  # a bad size raises here, before anything is bound or launched
+        for i, im in enumerate(images):
+            if getattr(im, "dtype", None) != np.uint8 or np.ndim(im) != 3 or np.shape(im)[2] != 3 or min(np.shape(im)[:2]) < 1:
+                raise ValueError("image %d must be uint8 [h,w,3], got %s %s" % (i, getattr(im, "dtype", type(im)), np.shape(im)))
+        if view_index is not None and not (self.side_info and self.views > 0):
+            if self.side_info:
+                raise AttributeError("SwinTransformer was built without camera / sequence: no side_info_embedding")
+            view_index = None
+        idx = None
+        if view_index is not None:
+            idx = _index_array(view_index, len(images))
+            if idx.size and (idx.min() < 0 or idx.max() >= self.views):
+                raise ValueError("view_index must lie in [0, %d), got %d .. %d" % (self.views, idx.min(), idx.max()))
+
+        def run(eng):
+            if idx is not None:
+                eng.set_side_index(idx)
+            return eng.swin_descriptor_images_u8(images, size=size, flip_tta=flip_tta)
+        try:
+            return self._run(run)
+        finally:
+            if idx is not None:
+                get_engine(self._device).set_side_index(None)
+
     def embed_crops(self, crops, size=(224, 224)):
         """uint8 HxWx3 crops of any size -> float32[N,96]: bilinear resize to ``size`` = (H, W) (multiples of 224), ImageNet
         normalisation (reid/data_transforms.py:64) and the stem's first convolution in one kernel on the device."""

@@ -1,6 +1,7 @@
 // Kernel experiments and correctness harnesses (include/reid_hip_debug.h).  Built into libreid_hip_debug.so, which links
 // against libreid_hip.so: nothing here is part of the product library or of the drop-in C ABI.
 #include "reid_internal.h"
+#include "pil_launch.h"
 #include <string.h>
 #include <stdlib.h>
 #include <vector>
@@ -1089,6 +1090,38 @@ extern "C" int reid_debug_resize_norm(reid_ctx* ctx, const uint8_t* packed, cons
     REID_TRY(dbg_output(ctx, "dbgf.xf32", (size_t)n * 256 * 128 * 3, &dout));
     REID_TRY(launch_resize_norm(ctx, dpk, doff, dhw, n, 256, 128, pitch, dout));
     REID_TRY(dbg_download(ctx, out, dout, (size_t)n * 256 * 128 * 3));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// The two kernels of libreid_hip_pil_resize.so through PilPlan, the launcher the *_images_u8 entry points call, on host operands: n packed
+// uint8 RGB images -> Pillow's Image.resize((out_w, out_h), BILINEAR) as u8_out [n][out_h][out_w][3] (may be NULL) and
+// ToTensor + Normalize(mean_std6; NULL = ImageNet) of it as f32_out [n][3][out_h][out_w].  One launch of all n images.
+extern "C" int reid_debug_pil_resize(reid_ctx* ctx, const uint8_t* packed, const long long* offsets, const int* hw, int n, int out_h, int out_w,
+                                     const float* mean_std6, uint8_t* u8_out, float* f32_out) {
+    ARG_CHECK(ctx && packed && offsets && hw && n >= 1 && f32_out);
+    REID_TRY(pil_mean_std(&mean_std6));
+    RaggedSrc src{packed, (const int64_t*)offsets, hw, n};
+    REID_TRY(src.check());
+    CTX_ENTER(ctx);
+    PilPlan plan;
+    REID_TRY(plan.build(src, out_h, out_w, mean_std6, n));
+    const size_t px = (size_t)n * out_h * out_w;
+    uint8_t* du8 = nullptr;
+    float* df32;
+    REID_TRY(src.alloc(ctx, "dbgp"));
+    REID_TRY(plan.alloc(ctx, "dbgp"));
+    if (u8_out) REID_TRY(dbg_output(ctx, "dbgp.u8", px * 3, &du8));
+    REID_TRY(dbg_output(ctx, "dbgp.f32", px * 3, &df32));
+    int rc = src.up(0, n, ctx->stream);
+    if (rc == REID_OK) rc = plan.up(ctx->stream);
+    if (rc == REID_OK) rc = plan.launch(ctx, src, 0, n, du8, df32);
+    if (rc != REID_OK) {
+        (void)hipStreamSynchronize(ctx->stream);   // the uploads read the caller's buffers and this call's plan
+        return rc;
+    }
+    REID_TRY(dbg_download(ctx, u8_out, (const uint8_t*)du8, px * 3));
+    REID_TRY(dbg_download(ctx, f32_out, (const float*)df32, px * 3));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }

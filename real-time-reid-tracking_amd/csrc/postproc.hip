@@ -8,6 +8,7 @@
 //     positive definite with eigenvalues in [n la, ||A||_inf], so the iteration converges quadratically from the first step
 //     and every iterate is a polynomial in A, i.e. symmetric: no transposes), then the projection GEMM.
 #include "reid_internal.h"
+#include "pil_launch.h"
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -181,7 +182,10 @@ int gemm_nt_dev(reid_ctx* ctx, const float* a, int m, const float* b, int n, int
 
 // x: [n][3][256][128] fp32 already normalised by the caller's transform (the evaluation script uses ImageNet mean/std,
 // data_transforms.py:56-130); out: [n][512 + num_class].  flip_tta != 0 averages the descriptor of the mirrored image.
-extern "C" int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, float* d_out) {
+// before_view(v, i, m) runs before the forward of images [i, i + m) of view v (0 plain, 1 mirrored): nothing for the float entries,
+// the side indices of the pass for reid_descriptor_images_u8.
+template <class BeforeView>
+static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, float* d_out, BeforeView before_view) {
     ARG_CHECK(ctx && d_x && d_out && n >= 0);
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
@@ -195,6 +199,7 @@ extern "C" int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int
     float *e1, *l1, *e2 = nullptr, *l2 = nullptr, *xf = nullptr;
     REID_TRY(ctx_ws(ctx, "pp.e1", (size_t)n * de * 4, (void**)&e1));
     REID_TRY(ctx_ws(ctx, "pp.l1", (size_t)n * nc * 4 + 16, (void**)&l1));
+    REID_TRY(before_view(0, 0, n));
     REID_TRY(reid_embed_f32_nchw_dev(ctx, d_x, n, e1, l1));
     if (flip_tta) {
         REID_TRY(ctx_ws(ctx, "pp.e2", (size_t)n * de * 4, (void**)&e2));
@@ -207,6 +212,7 @@ extern "C" int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int
             hipLaunchKernelGGL(flip_w_nchw_kernel, dim3(grid_for(rows * 128)), dim3(256), 0, ctx->stream, d_x + (size_t)i * img, rows,
                                128, xf);
             LAUNCH_CHECK();
+            REID_TRY(before_view(1, i, m));
             REID_TRY(reid_embed_f32_nchw_dev(ctx, xf, m, e2 + (size_t)i * de, l2 + (size_t)i * nc));
         }
     }
@@ -215,6 +221,10 @@ extern "C" int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int
     prof_end(ctx);
     LAUNCH_CHECK();
     return REID_OK;
+}
+
+extern "C" int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, float* d_out) {
+    return descriptor_dev(ctx, d_x, n, flip_tta, d_out, [](int, int, int) -> int { return REID_OK; });
 }
 
 extern "C" int reid_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, int flip_tta, float* out) {
@@ -232,6 +242,68 @@ extern "C" int reid_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, in
     HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * (de + nc) * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
+}
+
+// uint8 images of any sizes in: transforms.Resize((256, 128)) as PIL computes it -> ToTensor -> Normalize on the device (PilPlan,
+// libreid_hip_pil_resize.so), then per pass of `chunk` images what reid_descriptor_f32_nchw_dev runs on that pass - the same passes, the
+// same kernels, so the same bits as reid_descriptor_f32_nchw on the images preprocessed on the host.  n pending side indices serve the
+// plain and the mirrored view of an image, as the script's model(img, cam.repeat(2)) and as reid_swin_descriptor_*; the float entry
+// computes the same when it is given the indices twice (its plain passes take the first n, its mirrored passes the next n).  None stays
+// pending.
+extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
+                                         const float* mean_std6, int flip_tta, float* out) {
+    ARG_CHECK(ctx);
+    struct SideDrop {
+        reid_ctx* ctx;
+        ~SideDrop() {
+            ctx->side_idx.clear();
+            ctx->side_cursor = 0;
+        }
+    } drop{ctx};
+    ARG_CHECK(packed && offsets && hw && out && n >= 0);
+    REID_TRY(pil_mean_std(&mean_std6));
+    RaggedSrc src{packed, offsets, hw, n};
+    REID_TRY(src.check());
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    int de = 0, nc = 0;
+    REID_TRY(reid_seres18_dims(ctx, &de, &nc));
+    if (nc <= 0) {
+        reid_set_error("reid_descriptor_*: the loaded weights have no classifier (cls.w), the descriptor needs the logits");
+        return REID_ERR_STATE;
+    }
+    const int pass = ctx->chunk;
+    PilPlan plan;
+    REID_TRY(plan.build(src, 256, 128, mean_std6, pass));
+    std::vector<int32_t> side;
+    if (!ctx->side_idx.empty()) {
+        side.assign(ctx->side_idx.begin() + ctx->side_cursor, ctx->side_idx.end());
+        if (side.size() != (size_t)n) {
+            reid_set_error("reid_descriptor_images_u8: %d images but %zu side indices are pending", n, side.size());
+            return REID_ERR_ARG;
+        }
+    }
+    EmbedOut o{out, nullptr, de + nc, 0};
+    REID_TRY(src.alloc(ctx, "io"));
+    REID_TRY(o.alloc(ctx, "ppd", n, 0, false));
+    REID_TRY(plan.alloc(ctx, "io"));
+    return embed_host(
+        ctx, n, pass,
+        [&](int i, int m, hipStream_t s) -> int {
+            REID_TRY(src.up(i, m, s));
+            return i == 0 ? plan.up(s) : REID_OK;
+        },
+        [&](int i, int m, float* d_row, float*) -> int {
+            REID_TRY(plan.launch(ctx, src, i, m, nullptr, plan.d_f32));
+            return descriptor_dev(ctx, plan.d_f32, m, flip_tta, d_row, [&](int, int, int) -> int {
+                if (!side.empty()) {
+                    ctx->side_idx.assign(side.begin() + i, side.begin() + i + m);
+                    ctx->side_cursor = 0;
+                }
+                return REID_OK;
+            });
+        },
+        o);
 }
 
 // d_x [n][d] is updated in place; cams is a HOST array of camera ids >= 0 (ids without rows are skipped: the reference's

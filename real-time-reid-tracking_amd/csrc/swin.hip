@@ -11,6 +11,7 @@
 #include "swin_v2.h"
 #include "swin_crops.h"
 #include "swin_eval.h"
+#include "pil_launch.h"
 #include <mutex>
 #include <math.h>
 #include <string.h>
@@ -2382,6 +2383,45 @@ extern "C" int reid_swin_descriptor_ragged_u8(reid_ctx* ctx, const uint8_t* pack
                     return swin_body(ctx, *p.sw, nullptr, c1, m, out_h, out_w, e, nullptr);
                 },
                 d_row);
+        },
+        o);
+}
+
+// uint8 images of any sizes in: transforms.Resize((out_h, out_w)) as PIL computes it -> ToTensor -> Normalize on the device (PilPlan,
+// libreid_hip_pil_resize.so) into the pass's fp32 NCHW workspace, then the two views of reid_swin_descriptor_f32_nchw on it - the same
+// kernels on the same values, so the same bits as that entry on the images preprocessed on the host.
+extern "C" int reid_swin_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                              int out_w, const float* mean_std6, int flip_tta, float* out) {
+    ARG_CHECK(ctx);
+    SidePendingClear drop{ctx};
+    ARG_CHECK(packed && offsets && hw && out && n >= 0);
+    REID_TRY(swin_crops_args(out_h, out_w, &mean_std6));
+    RaggedSrc src{packed, offsets, hw, n};
+    REID_TRY(src.check());
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    SwinDescPlan p;
+    REID_TRY(swin_descriptor_ready(ctx, n, false, &p));
+    const int pass = swin_pass(ctx);
+    PilPlan plan;
+    REID_TRY(plan.build(src, out_h, out_w, mean_std6, pass));
+    float *e1, *e2;
+    EmbedOut o{out, nullptr, p.nc + 96, 0};
+    REID_TRY(src.alloc(ctx, "io"));
+    REID_TRY(o.alloc(ctx, "swd", n, 0, false));
+    REID_TRY(plan.alloc(ctx, "io"));
+    REID_TRY(swin_descriptor_ws(ctx, n < pass ? n : pass, flip_tta, &e1, &e2));
+    return embed_host(
+        ctx, n, pass,
+        [&](int i, int m, hipStream_t s) -> int {
+            REID_TRY(src.up(i, m, s));
+            return i == 0 ? plan.up(s) : REID_OK;
+        },
+        [&](int i, int m, float* d_row, float*) -> int {
+            REID_TRY(plan.launch(ctx, src, i, m, nullptr, plan.d_f32));
+            return swin_descriptor_pass(
+                ctx, p, i, m, out_h, out_w, flip_tta, e1, e2,
+                [&](int v, float* c1, float* e) -> int { return swin_view_f32(ctx, *p.sw, v, plan.d_f32, c1, m, out_h, out_w, e); }, d_row);
         },
         o);
 }

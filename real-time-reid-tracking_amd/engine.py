@@ -283,6 +283,45 @@ class Engine:
         check(self.lib.reid_swin_descriptor_ragged_u8(self.h, src, _ptr(offs), _ptr(hw), n, h, w, _ptr(ms), int(bool(flip_tta)), _ptr(out)))
         return out
 
+    def swin_descriptor_images_u8(self, images, size=(448, 224), mean_std=None, flip_tta=True):
+        """list of uint8[h_i,w_i,3] images of any sizes -> float32 [n, num_class + 96]: the evaluation script's own transform on the
+        device - transforms.Resize(size) as PIL computes it (8-bit antialiased bilinear, bit for bit), ToTensor, Normalize(mean_std;
+        None: ImageNet) - then the descriptor of swin_descriptor_f32_nchw, to whose result on host-preprocessed images this is
+        bit-identical (reid_swin_descriptor_images_u8).  ``size`` as swin_descriptor_ragged_u8; pending side indices serve both views."""
+        h, w, ms = self._swin_crop_args(size, mean_std)
+        images = list(images)
+        n = len(images)
+        src, offs, hw, _keep = self._pack_images(images)
+        out = np.empty((n, self._swin_descriptor_width()), np.float32)
+        check(self.lib.reid_swin_descriptor_images_u8(self.h, src, _ptr(offs), _ptr(hw), n, h, w, _ptr(ms), int(bool(flip_tta)), _ptr(out)))
+        return out
+
+    PIL_MAX_SIDE = 4096     # pil_resize_max_side() of libreid_hip_pil_resize.so: the largest source side of the *_images_u8 entries
+
+    @classmethod
+    def _pack_images(cls, images):
+        """_pack_ragged for the *_images_u8 entries, with their source limit checked before any device call."""
+        for i, im in enumerate(images):
+            shp = np.shape(im)
+            if len(shp) == 3 and max(shp[0], shp[1]) > cls.PIL_MAX_SIDE:
+                raise ValueError("image %d is %d x %d, a source side may be %d at most" % (i, shp[0], shp[1], cls.PIL_MAX_SIDE))
+        return cls._pack_ragged(images)
+
+    def descriptor_images_u8(self, images, flip_tta=True, mean_std=None):
+        """list of uint8[h_i,w_i,3] images of any sizes -> float32 [n, 512 + num_class]: transforms.Resize((256, 128)) as PIL computes
+        it, ToTensor and Normalize(mean_std; None: ImageNet) on the device, then the descriptor of descriptor_f32_nchw, to whose result
+        on host-preprocessed images this is bit-identical (reid_descriptor_images_u8)."""
+        _, _, ms = self._swin_crop_args((224, 224), mean_std)
+        images = list(images)
+        n = len(images)
+        src, offs, hw, _keep = self._pack_images(images)
+        nc = getattr(self, "num_class", 0)
+        if nc <= 0:
+            raise ValueError("a descriptor needs loaded weights with a classifier (Engine.load_seres18)")
+        out = np.empty((n, self.embed_dim + nc), np.float32)
+        check(self.lib.reid_descriptor_images_u8(self.h, src, _ptr(offs), _ptr(hw), n, _ptr(ms), int(bool(flip_tta)), _ptr(out)))
+        return out
+
     # ---- embedding
     def _outs(self, n, want_logits, dim=None, num_class=None):
         """Host arrays an embed call fills: emb[n, dim] and logits[n, num_class] or None (default sizes: the ResNet18-SE family's)."""
@@ -729,6 +768,37 @@ class Engine:
         out = np.empty((n, IMG_H, IMG_W, 3), np.float32)
         check(_ffi.debug_lib().reid_debug_resize_norm(self.h, _ptr(packed), _ptr(offsets), _ptr(hw), C.c_int(n), C.c_int(int(pitch)), _ptr(out)))
         return out
+
+    def debug_pil_resize(self, images, size, mean_std=None, want_u8=True, packed=None, offsets=None, hw=None):
+        """The two kernels of libreid_hip_pil_resize.so through the launcher the *_images_u8 entries call (reid_debug_pil_resize):
+        list of uint8[h_i,w_i,3] -> (uint8 [n, H, W, 3] = PIL's Image.resize((W, H), BILINEAR), float32 [n, 3, H, W] = ToTensor +
+        Normalize of it); ``size`` = (H, W), each from 1 to 1024.  ``packed`` / ``offsets`` / ``hw`` instead of ``images``: the raw
+        arguments (items may share source bytes, offsets in any order).  Floats the launch leaves alone read NaN."""
+        try:
+            h, w = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise ValueError("size must be (H, W), got %r" % (size,))
+        if not (1 <= h <= 1024 and 1 <= w <= 1024):
+            raise ValueError("debug_pil_resize: output sides from 1 to 1024, got %r" % (size,))
+        _, _, ms = self._swin_crop_args((224, 224), mean_std)
+        if packed is None:
+            src, offs, hws, _keep = self._pack_images(list(images))
+        else:
+            packed = np.ascontiguousarray(packed, np.uint8).reshape(-1)
+            offs = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+            hws = np.ascontiguousarray(hw, np.int32).reshape(-1, 2)
+            if len(hws) != len(offs) or len(offs) < 1 or int(offs.min()) < 0 or int(hws.min()) < 1 or int(hws.max()) > self.PIL_MAX_SIDE or \
+                    max(int(o) + int(a) * int(b) * 3 for o, (a, b) in zip(offs, hws)) > packed.size:
+                raise ValueError("debug_pil_resize: an image leaves the buffer or the limits")
+            src = _ptr(packed)
+        n = len(offs)
+        if n < 1:
+            raise ValueError("debug_pil_resize: at least one image")
+        u8 = np.empty((n, h, w, 3), np.uint8) if want_u8 else None
+        f32 = np.empty((n, 3, h, w), np.float32)
+        check(_ffi.debug_lib().reid_debug_pil_resize(self.h, src, _ptr(offs), _ptr(hws), C.c_int(n), C.c_int(h), C.c_int(w), _ptr(ms), _ptr(u8),
+                                                     _ptr(f32)))
+        return u8, f32
 
     def debug_bank_cost96(self, bank, slots, dets, metric=_ffi.METRIC_COS, gate=None):
         """reid_debug_bank_cost96: the frame pipeline's cost launch for a 96-wide bank handle on host operands -> cost[t, m] float32

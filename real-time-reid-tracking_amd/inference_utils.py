@@ -40,4 +40,8 @@ def smooth_tracklets(embeddings, seqs, indices_valid, device=0):
 
 
 def extract_descriptors(images, flip=True, device=0):
+    """float [n,3,256,128] after the caller's transform, or a list of uint8 [h,w,3] images of any sizes, which the device resizes as PIL
+    does and normalises with the ImageNet values (Engine.descriptor_images_u8)."""
+    if isinstance(images, (list, tuple)) and len(images) and all(getattr(im, "dtype", None) == np.uint8 for im in images):
+        return get_engine(device).descriptor_images_u8(images, flip_tta=flip)
     return get_engine(device).descriptor_f32_nchw(_np(images), flip)

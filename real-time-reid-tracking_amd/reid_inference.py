@@ -17,7 +17,9 @@ in place (``reid_cam_debias_dev`` -> ``reid_rerank_jaccard_dev`` -> ``reid_smoot
 without a host round trip between links.  The one exception is the reference's own: DBSCAN is scikit-learn (or cuML) on the
 host there (`dists.cpu().numpy()`, :297) and stays a host call here - clustering is outside the hot path -
 so the Jaccard matrix is downloaded once for it; ``cluster_fn`` replaces it.  Images enter as float32 [n,3,256,128] after the
-caller's transform (the script's torchvision transforms are data loading, not this path).
+caller's transform, or as uint8 [h,w,3] arrays of any sizes as the dataset stores them: then the script's transform itself (PIL's
+antialiased ``Resize``, ``ToTensor``, ``Normalize``, data_transforms.py:56-127) runs on the device, bit for bit
+(``reid_descriptor_images_u8`` / ``reid_swin_descriptor_images_u8``).
 
 With ``arch="swin"`` the descriptor link is ``reid_swin_descriptor_f32_nchw_dev``: images are float32 [n,3,h,w] with h, w multiples of
 224 (the script resizes to 448x224, data_transforms.py:78-84), a row is [normalize(logits) | normalize(x_norm)] - the Swin returns
@@ -64,16 +66,75 @@ def _check_images(images, arch):
     return images
 
 
-def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None):
+def is_u8_images(images):
+    """True for images handed over as the dataset stores them: a list / tuple of uint8 [h,w,3] arrays of any sizes, or one uint8
+    [n,h,w,3] array.  Everything else is the float path's business."""
+    if isinstance(images, np.ndarray):
+        return images.dtype == np.uint8
+    if isinstance(images, (list, tuple)):
+        return len(images) > 0 and all(getattr(im, "dtype", None) == np.uint8 for im in images)
+    return False
+
+
+def _check_u8_images(images, arch, size):
+    """uint8 HWC images of any sizes and the (H, W) they are resized to -> (list of arrays, (H, W)); ValueError before any device call."""
+    from .engine import Engine
+    if arch == "swin":
+        h, w, _ = Engine._swin_crop_args((448, 224) if size is None else size, None)
+    else:
+        if size is not None and tuple(int(v) for v in size) != (IMG_H, IMG_W):
+            raise ValueError("arch=%r resizes to (%d, %d) only, got size %r" % (arch, IMG_H, IMG_W, size))
+        h, w = IMG_H, IMG_W
+    out = []
+    for i, im in enumerate(images):
+        im = np.asarray(im)
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError("image %d must be uint8 [h,w,3], got %s %s" % (i, im.dtype, im.shape))
+        if max(im.shape[:2]) > Engine.PIL_MAX_SIDE:
+            raise ValueError("image %d is %d x %d, a source side may be %d at most" % (i, im.shape[0], im.shape[1], Engine.PIL_MAX_SIDE))
+        out.append(im)
+    return out, (h, w)
+
+
+def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width):
+    """The uint8 path of inference_efficient: batches of ``bs`` images through the *_images_u8 entries, whose rows (about 5 KB per
+    image) are copied into the device matrix."""
+    n = len(images)
+    for i in range(0, n, bs):
+        part = images[i:i + bs]
+        if arch == "swin":
+            if view_index is not None:
+                engine.set_side_index(view_index[i:i + bs])
+            rows = engine.swin_descriptor_images_u8(part, size=size, flip_tta=flip)
+        else:
+            rows = engine.descriptor_images_u8(part, flip_tta=flip)
+        engine.h2d(d_out + i * width * 4, rows)
+    engine.sync()
+    return n
+
+
+def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None):
     """Descriptors of ``images`` (float32 [n,3,256,128], host) into the device rows ``d_out`` (pointer to [n, 512 + num_class]
     fp32): upload in batches of ``bs`` images, one ``reid_descriptor_f32_nchw_dev`` per batch.  Unlike the reference function
     (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253).
 
     ``arch="swin"``: images float32 [n,3,h,w], h, w multiples of 224, rows [n, num_class + 96] through
-    ``reid_swin_descriptor_f32_nchw_dev``; ``view_index`` (one per image; ``arch="swin"`` only) is the side index of both views."""
+    ``reid_swin_descriptor_f32_nchw_dev``; ``view_index`` (one per image; ``arch="swin"`` only) is the side index of both views.
+
+    ``images`` may instead be a sequence of uint8 [h,w,3] arrays of any sizes (or one uint8 [n,h,w,3] array): the script's transform -
+    PIL's antialiased Resize, ToTensor, Normalize with the ImageNet values - then runs on the device (``reid_descriptor_images_u8``,
+    to 256x128; ``reid_swin_descriptor_images_u8`` to ``size`` = (H, W), default (448, 224)), with rows bit-identical to the float path
+    on the same images preprocessed with PIL on the host.  ``size`` is for uint8 images only."""
     width = _descriptor_width(engine, arch)
-    images = _check_images(images, arch)
-    n = images.shape[0]
+    u8 = is_u8_images(images)
+    if u8:
+        images, size = _check_u8_images(images, arch, size)
+        n = len(images)
+    else:
+        if size is not None:
+            raise ValueError("size is the resize target of uint8 images; float images carry their own")
+        images = _check_images(images, arch)
+        n = images.shape[0]
     if int(bs) < 1:
         raise ValueError("bs must be at least 1, got %r" % (bs,))
     if view_index is not None:
@@ -83,6 +144,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
         if view_index.shape[0] != n or (n and (view_index.min() < 0 or view_index.max() >= 2 ** 31)):
             raise ValueError("view_index must hold one non-negative index per image (%d), got %d" % (n, view_index.shape[0]))
         view_index = view_index.astype(np.int32)
+    if u8:
+        return _inference_u8(engine, images, d_out, flip, int(bs), arch, view_index, size, width)
     stage = DevArray(engine, (min(bs, max(n, 1)),) + images.shape[1:], np.float32)
     try:
         for i in range(0, n, bs):
@@ -102,13 +165,15 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
 
 def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, query_images, query_labels, query_cams,
                   query_seqs, num_gallery_cams=None, eps=0.5, la=0.05, k1=20, k2=6, flip=True, cluster_fn=None, taps=None,
-                  verbose=True, device=0, engine=None, arch="seres18", use_side=False):
+                  verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None):
     """(CMC float32 [ng], mAP float) of the script's chain for one gallery / query pair; weights must be loaded on the engine
     (``Engine.load_seres18`` / ``build_model``).  ``taps`` (a dict) receives host copies of the intermediates the
     reference-generated fixture holds: "desc", "debiased", "jaccard", "pseudo_labels", "smoothed".
     ``cluster_fn(dists float32 [N,N]) -> int labels [N]`` (-1 = noise) replaces the DBSCAN call.
     ``arch="swin"``: the chain on the loaded Swin weights (``Engine.load_swin``), images float32 [n,3,h,w] with h, w multiples of 224;
-    ``use_side`` (the script's --sie, ``arch="swin"`` only) passes each image's camera as the view index of both its views."""
+    ``use_side`` (the script's --sie, ``arch="swin"`` only) passes each image's camera as the view index of both its views.
+    Gallery and query images may each be a sequence of uint8 [h,w,3] arrays of any sizes instead (see ``inference_efficient``); ``size``
+    = (H, W) is what a Swin resizes them to (default (448, 224); the ResNet family is fixed at 256x128)."""
     if arch not in ARCHS:
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
     if use_side and arch != "swin":
@@ -119,13 +184,18 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     ng, nq = len(gl), len(ql)
     if len(gallery_images) != ng or len(query_images) != nq or ng < 1 or nq < 1:
         raise ValueError("images and labels disagree: %d/%d gallery, %d/%d query" % (len(gallery_images), ng, len(query_images), nq))
-    gallery_images, query_images = _check_images(gallery_images, arch), _check_images(query_images, arch)
+    u8 = [is_u8_images(gallery_images), is_u8_images(query_images)]
+    if size is not None and not any(u8):
+        raise ValueError("size is the resize target of uint8 images; float images carry their own")
+    gallery_images, query_images = (_check_u8_images(im, arch, size)[0] if is_u8 else _check_images(im, arch)
+                                    for im, is_u8 in zip((gallery_images, query_images), u8))
     n, width = ng + nq, _descriptor_width(eng, arch)
     merged = DevArray(eng, (n, width), np.float32)
     dists = DevArray(eng, (n, n), np.float32)
     try:
-        inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None)
-        inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None)
+        inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None, size=size if u8[0] else None)
+        inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None,
+                            size=size if u8[1] else None)
         if taps is not None:
             taps["desc"] = merged.numpy()
         merged_cams = np.concatenate([gc, qc]).astype(np.int32)
