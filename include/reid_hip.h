@@ -272,6 +272,34 @@ int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_
                               int flip_tta, float* out);
 int reid_swin_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,
                                    const float* mean_std6, int flip_tta, float* out);
+/* ---- ResNet18-IBN-SE at any input size ---------------------------------------------------- */
+/* The network is fully convolutional with a GeM neck, and the evaluation script runs the ResNet family on VeRi at
+ * Resize((224, int(ratio * 224))), ratio = the mean width / height of the dataset's images (reid/data_transforms.py:121,
+ * reid/image_reid_inference.py:169-180) - a width such as 251 or 268; the tracker plug-in carries DeepSORT's (64, 128) beside (128, 256)
+ * (modification_deepsort/feature_extractor.py:23-24).  The entries below are the entries of the same name without _hw with the input
+ * size h x w (out_h x out_w: the size the uint8 sources are resized to) as arguments, each 32 .. 512, odd values allowed.
+ *   (256, 128)   is handed to the existing entry: the same code path, the same bits, every architecture and precision mode.
+ *   other sizes  a second forward, generic in H and W, for seres18_ibn weights in precision mode 0 (exact fp32): the convolutions on the
+ *                generic implicit-GEMM kernel, InstanceNorm / SE / GeM for any number of pixels from libreid_hip_anysize.so, which must
+ *                lie beside this library (REID_ERR_STATE naming it otherwise).  Another architecture or precision mode is REID_ERR_ARG
+ *                naming both - nothing falls back.  A pass is chunk * 256 * 128 / (h * w) images, clamped to 1 .. 4096, so it needs no
+ *                more workspace than a pass of the 256 x 128 forward; results do not depend on the pass size.  Pending side indices
+ *                (camera bias) apply as in the entries without _hw; reid_debug_stage reads the taps of the last pass, each
+ *                [n][Ho][Wo][C] of its own map size.
+ * reid_embed_ragged_u8_hw: the cv2-style bilinear resize of reid_embed_ragged_u8 to out_h x out_w, then (v - mean[c]) / std[c];
+ * mean_std6 = mean[3] | std[3], NULL = 0.5 / 0.5 (the tracker's Normalize; at (256, 128) the only one).
+ * reid_descriptor_images_u8_hw: Pillow's Resize((out_h, out_w)) as reid_descriptor_images_u8, bit-identical to
+ * reid_descriptor_f32_nchw_hw on the same images preprocessed on the host; the mirrored view is read with reversed columns by the
+ * layout kernel in front of the stem, no flipped copy of the batch is made.
+ * Refused before anything is queued: a side outside 32 .. 512 (REID_ERR_ARG). */
+int reid_embed_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits);
+int reid_embed_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits);
+int reid_embed_ragged_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,
+                            const float* mean_std6, float* emb, float* logits);
+int reid_descriptor_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, int flip_tta, float* out);
+int reid_descriptor_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out);
+int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                 int out_w, const float* mean_std6, int flip_tta, float* out);
 /* diminish_camera_bias, reid/inference_utils.py:5-15, in place on x fp32 [n][d]: per camera id c (cams is a host int32[n],
  * ids >= 0) rows X_c <- normalize_rows((X_c - mean X_c) inverse(X_c^T X_c + n_c*la*I)^T).  The inverse is a Newton-Schulz
  * iteration of fp32 GEMMs that stops when the residual reaches the fp32 noise floor (iters = upper bound, <= 0: 40). */

@@ -97,6 +97,20 @@ int reid_debug_sibling_tail(reid_ctx* ctx, int arch, int n, int h, int w, int c,
 /* gem_neck: GeM (exponent p) + BNNeck, emb = gem * scale + shift, on fp32 x (f16 = 0) or f16 x (f16 = 1); gem_out may be null. */
 int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c, float p, const void* x, const float* scale, const float* shift,
                         float* gem_out, float* emb);
+/* The kernels of libreid_hip_anysize.so (csrc/anysize.h: the block tails of ResNet18-IBN-SE for any number of pixels hw) through the
+ * launchers the any-size forward calls, on host operands; NHWC fp32, c = 64 .. 512 a power of two.  Every output has ONE guard pixel
+ * (c floats) behind its last row, set to 0xff bytes before the launch as the outputs are: out [n hw c + c], gate / gem_out / emb [n c + c].
+ *   any_norm     x -> out in place: channels < half InstanceNorm2d(affine) over the image's hw pixels + ReLU; channels >= half
+ *                relu(x * bn_scale + bn_shift), or left as they are when bn_scale is NULL (half % 32 == 0).
+ *   any_se_tail  out = relu(sigmoid(w2t^T relu(w1 mean_hw(y))) y + shortcut), w1 / w2t [mid][c]; gate may be null.
+ *   any_gem      GeM (exponent p, clamp 1e-6) + BNNeck, emb = gem * scale + shift; gem_out may be null.
+ * The switch "anysize_force" (reid_debug_set_switch) sends 256 x 128 through the any-size forward in the reid_*_hw entries. */
+int reid_debug_any_norm(reid_ctx* ctx, int n, int hw, int c, int half, const float* x, const float* in_gamma, const float* in_beta,
+                        const float* bn_scale, const float* bn_shift, float* out);
+int reid_debug_any_se_tail(reid_ctx* ctx, int n, int hw, int c, int mid, const float* w1, const float* w2t, const float* y,
+                           const float* shortcut, float* out, float* gate);
+int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, const float* x, const float* scale, const float* shift, float* gem_out,
+                       float* emb);
 /* gem_neck of the last block's tail in one launch (launch_gem_neck_tail; tests/test_gpu_tail_stream.py): GeM + BNNeck of
  * relu(gate y + shortcut) with se_tail's gate, fp32 operands as in se_tail; equals se_tail form 4 followed by gem_neck bit for bit. */
 int reid_debug_gem_neck_fused(reid_ctx* ctx, int n, int hw, int c, int mid, int tiles, float p, const float* stats, const float* w1,

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import precision as _precision
 from . import synth, weights
-from .engine import IMG_H, IMG_W, Engine, get_engine
+from .engine import IMG_H, IMG_W, Engine, check_hw, get_engine
 
 
 def _device_index(device):
@@ -194,8 +194,14 @@ class SERes18IBN:
         is_torch = hasattr(x, "detach")
         if not is_torch:
             x = np.asarray(x, np.float32)
-        if x.ndim != 4 or tuple(x.shape[1:]) != (3, IMG_H, IMG_W):
-            raise ValueError("expected [N,3,%d,%d] input, got %s" % (IMG_H, IMG_W, tuple(x.shape)))
+        if x.ndim != 4 or x.shape[1] != 3:
+            raise ValueError("expected [N,3,H,W] input, got %s" % (tuple(x.shape),))
+        size = check_hw(tuple(x.shape[2:]))
+        any_size = size != (IMG_H, IMG_W)
+        if any_size and self.arch != "seres18_ibn":
+            raise ValueError("%s runs at [N,3,%d,%d] only (other sizes: seres18_ibn), got %s" % (self.arch, IMG_H, IMG_W, tuple(x.shape)))
+        # another size runs the any-size forward, which is exact fp32: this CALL runs in mode 0, the model keeps its own mode
+        run = (lambda fn: _precision.run(_ExactCall(self), get_engine(self._device), self.arch, fn)) if any_size else self._run
         if is_torch and x.is_cuda:
             if x.device.index != self._device:
                 self.to(x.device.index)
@@ -205,9 +211,10 @@ class SERes18IBN:
                 if cam is not None:
                     eng.set_side_index(_index_array(cam, x.shape[0]))
                 return _torch_cuda_forward(
-                    x, lambda xf, o: eng.embed_f32_nchw_dev(xf.data_ptr(), xf.shape[0], o[0].data_ptr(), o[1].data_ptr()), eng,
+                    x, lambda xf, o: eng.embed_f32_nchw_dev(xf.data_ptr(), xf.shape[0], o[0].data_ptr(), o[1].data_ptr(),
+                                                            size=size if any_size else None), eng,
                     (self.embed_dim, self.num_classes))
-            emb, logits = self._run(on_device)
+            emb, logits = run(on_device)
         else:
             x_np = x.detach().float().cpu().numpy() if is_torch else np.asarray(x, np.float32)
 
@@ -215,7 +222,7 @@ class SERes18IBN:
                 if cam is not None:
                     eng.set_side_index(_index_array(cam, x_np.shape[0]))
                 return eng.embed_f32_nchw(x_np, logits=True)
-            emb, logits = self._run(on_host)
+            emb, logits = run(on_host)
             if is_torch:
                 import torch
                 emb, logits = torch.from_numpy(emb), torch.from_numpy(logits)
@@ -229,6 +236,20 @@ class SERes18IBN:
         """uint8 HxWx3 crops of any size -> float32[N,512]; resize + normalise on the device."""
         crops = list(crops)
         return self._run(lambda eng: eng.embed_ragged_u8(crops))
+
+
+class _ExactCall(object):
+    """precision.run owner for ONE call in exact fp32 with another object's weights (an input size other than 256 x 128)."""
+    _mode = _precision.EXACT
+
+    def __init__(self, owner):
+        self._owner = owner
+
+    def _needs_bind(self, eng):
+        return self._owner._needs_bind(eng)
+
+    def _do_bind(self, eng):
+        self._owner._do_bind(eng)
 
 
 def seres18_ibn(num_classes=751, loss="triplet", pretrained=False, use_gpu=True, **kwargs):

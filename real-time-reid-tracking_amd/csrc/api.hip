@@ -2,6 +2,8 @@
 // distance / selection entry points.  No torch types, no CPU compute fallback: every result comes from a HIP kernel.
 #include "reid_internal.h"
 #include "siblings_f16.h"
+#include "anysize.h"
+#include <cmath>
 #include <dlfcn.h>
 #include <mutex>
 #include <stdarg.h>
@@ -993,7 +995,7 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
     }
     ctx->last_n = n;
     ctx->last_f16 = false;
-    for (int s = 0; s < 11; ++s) ctx->stage_ptr[s] = b.stage[s];
+    for (int s = 0; s < 11; ++s) { ctx->stage_ptr[s] = b.stage[s]; ctx->stage_elems[s] = 0; }
     return REID_OK;
 }
 
@@ -1244,7 +1246,7 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
     }
     ctx->last_n = n;
     ctx->last_f16 = true;
-    for (int s2 = 0; s2 < 11; ++s2) ctx->stage_ptr[s2] = stage[s2];
+    for (int s2 = 0; s2 < 11; ++s2) { ctx->stage_ptr[s2] = stage[s2]; ctx->stage_elems[s2] = 0; }
     return REID_OK;
 }
 
@@ -1263,7 +1265,7 @@ extern "C" int reid_debug_stage(reid_ctx* ctx, int stage, float* out, size_t max
         reid_set_error("reid_debug_stage: enable reid_ctx_set_debug_keep before the embed call");
         return REID_ERR_STATE;
     }
-    const size_t total = kStageElems[stage] * (size_t)ctx->last_n;
+    const size_t total = (ctx->stage_elems[stage] ? ctx->stage_elems[stage] : kStageElems[stage]) * (size_t)ctx->last_n;
     if (count) *count = total;
     const size_t ncopy = total < max_floats ? total : max_floats;
     if (ctx->last_f16 && stage < 10) {   // fp16 path: activations are stored as f16, widen on the host
@@ -1446,6 +1448,308 @@ extern "C" int reid_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, float* 
             return REID_OK;
         },
         [&](int i, int m, float* d_emb, float* d_log) -> int { return se_run_nchw(ctx, d_in + (size_t)i * kCropElems, m, d_emb, d_log); }, out);
+}
+
+// ------------------------------------------------------------------------------------------------ any input size (seres18_ibn, exact fp32)
+// The network is fully convolutional with a GeM neck, and the evaluation script runs it at Resize((224, int(ratio * 224))) for VeRi
+// (reid/data_transforms.py:121, image_reid_inference.py:169-180).  A second forward, generic in H and W: every convolution through
+// launch_gemm_f32 - the one launcher of the product library that takes n Ho Wo off the tile height, odd Wo, Cin = 3, the BN epilogue
+// and an identity residual at once (conv_f32.hip wants hw % 128 == 0 and Wo | 32, its general form has no BN epilogue or ReLU) - and
+// the tails between them from libreid_hip_anysize.so (anysize.h).  A GEMM row is one output pixel summed in k order whatever tile it
+// falls into and no launch splits K, so the bits of an image do not depend on the pass it ran in.
+struct AnysizeApi {
+    decltype(&anysize_norm) norm = nullptr;
+    decltype(&anysize_se_tail) se_tail = nullptr;
+    decltype(&anysize_gem) gem = nullptr;
+    decltype(&anysize_nchw_to_nhwc3) to_nhwc = nullptr;
+    decltype(&anysize_resize_norm) resize = nullptr;
+};
+static int anysize_api(const AnysizeApi** out) {
+    static std::mutex m;
+    static AnysizeApi api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.norm) {
+        void* f[5];
+        REID_TRY(open_beside_self("libreid_hip_anysize.so", "ResNet18-IBN-SE at an input size other than 256 x 128 needs",
+                                  {"anysize_norm", "anysize_se_tail", "anysize_gem", "anysize_nchw_to_nhwc3", "anysize_resize_norm"}, f));
+        api.se_tail = (decltype(api.se_tail))f[1];
+        api.gem = (decltype(api.gem))f[2];
+        api.to_nhwc = (decltype(api.to_nhwc))f[3];
+        api.resize = (decltype(api.resize))f[4];
+        api.norm = (decltype(api.norm))f[0];
+    }
+    *out = &api;
+    return REID_OK;
+}
+
+bool se_any_routes(const reid_ctx* ctx, int h, int w) { return h != IMG_H || w != IMG_W || ctx->anysize_force != 0; }
+
+int se_any_pass(const reid_ctx* ctx, int h, int w) {
+    const long long p = (long long)ctx->chunk * IMG_H * IMG_W / ((long long)h * w);
+    return (int)(p < 1 ? 1 : (p > 4096 ? 4096 : p));
+}
+
+int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
+    if (h < 32 || h > 512 || w < 32 || w > 512) {
+        reid_set_error("%s: input size %d x %d, height and width must each be in [32, 512]", who, h, w);
+        return REID_ERR_ARG;
+    }
+    if (!se_any_routes(ctx, h, w)) return REID_OK;
+    const Se18Weights& wt = ctx->se18;
+    if (!wt.loaded) {
+        reid_set_error("%s: call reid_seres18_load first", who);
+        return REID_ERR_STATE;
+    }
+    if (wt.arch != 0 || ctx->precision != 0) {
+        static const char* const kArch[3] = {"seres18_ibn", "cares18_ibn", "emares18_ibn"};
+        reid_set_error("%s: input size %d x %d runs seres18_ibn in precision mode 0 (exact fp32) only; loaded architecture %s, precision "
+                       "mode %d (256 x 128 runs every architecture and mode)", who, h, w, kArch[wt.arch], ctx->precision);
+        return REID_ERR_ARG;
+    }
+    const AnysizeApi* api;
+    return anysize_api(&api);
+}
+
+static int any_launched(hipError_t e, const char* what) {
+    if (e != hipSuccess) {
+        reid_set_error("libreid_hip_anysize.so %s -> %s", what, hipGetErrorString(e));
+        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+    }
+    return REID_OK;
+}
+
+int launch_any_norm(reid_ctx* ctx, float* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta, const float* bn_scale,
+                    const float* bn_shift) {
+    const AnysizeApi* api;
+    REID_TRY(anysize_api(&api));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * (bn_scale ? c : half) * 12.0);
+    const hipError_t e = api->norm(ctx->stream, x, n, hw, c, half, in_gamma, in_beta, bn_scale, bn_shift);
+    prof_end(ctx);
+    return any_launched(e, "anysize_norm");
+}
+
+int launch_any_se_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int hw, int c, int mid, const float* w1, const float* w2t,
+                       float* out, float* gate_out) {
+    const AnysizeApi* api;
+    REID_TRY(anysize_api(&api));
+    float* pooled;
+    REID_TRY(ctx_ws(ctx, "any.pooled", (size_t)n * c * 4, (void**)&pooled));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 16.0);
+    const hipError_t e = api->se_tail(ctx->stream, y, sc, n, hw, c, mid, w1, w2t, pooled, out, gate_out);
+    prof_end(ctx);
+    return any_launched(e, "anysize_se_tail");
+}
+
+int launch_any_gem(reid_ctx* ctx, const float* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out,
+                   float* emb) {
+    const AnysizeApi* api;
+    REID_TRY(anysize_api(&api));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 4.0);
+    const hipError_t e = api->gem(ctx->stream, x, n, hw, c, p, scale, shift, gem_out, emb);
+    prof_end(ctx);
+    return any_launched(e, "anysize_gem");
+}
+
+// one convolution of the any-size forward: NHWC fp32 in / out, folded BN (+ identity residual) (+ ReLU from column relu_from on)
+static int any_conv(reid_ctx* ctx, int amode, const float* x, int n, int H, int W, int Cin, const float* wgt, int Cout, int R, int stride, int pad,
+                    const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out) {
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    const int K = amode == A_IM2COL ? R * R * Cin : 192;   // the stem's rows are padded to 8 x 24 (stem_pack)
+    p.A = x;
+    p.H = H; p.W = W; p.Cin = Cin; p.R = R; p.S = R; p.stride = stride; p.pad_y = pad; p.pad_x = pad;
+    p.Ho = (H + 2 * pad - R) / stride + 1;
+    p.Wo = (W + 2 * pad - R) / stride + 1;
+    p.B = wgt; p.ldb = K;
+    p.M = n * p.Ho * p.Wo; p.N = Cout; p.K = K;
+    p.C = out; p.ldc = Cout;
+    p.col_scale = scale; p.col_shift = shift; p.residual = residual; p.relu = relu; p.relu_from = relu_from;
+    const double ktrue = (double)R * R * Cin;
+    return launch_gemm_f32(ctx, amode, E_CONV, p, REID_K_CONV_GEMM, 2.0 * p.M * Cout * ktrue,
+                           ((double)n * H * W * Cin + (double)p.M * Cout * (residual ? 2.0 : 1.0) + (double)Cout * ktrue) * 4.0);
+}
+
+// x: fp32 NHWC [n][h][w][3] on the device
+static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
+    Se18Weights& wt = ctx->se18;
+    const bool keep = ctx->debug_keep != 0;
+    const int H1 = (h + 6 - 7) / 2 + 1, W1 = (w + 6 - 7) / 2 + 1;        // conv 7x7 s2 p3
+    const int H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;      // MaxPool2d(3, 2, 1)
+    ARG_CHECK((long long)n * H1 * W1 < (1ll << 31));                     // the GEMM's row index is an int (element offsets are 64-bit)
+    size_t elems[11];
+    elems[0] = (size_t)H1 * W1 * 64;
+    elems[1] = (size_t)H2 * W2 * 64;
+    size_t per = elems[1];
+    {
+        int H = H2, W = W2;
+        for (int i = 0; i < 8; ++i) {
+            const Se18Block& k = wt.blk[i];
+            H = (H + 2 - 3) / k.stride + 1;
+            W = (W + 2 - 3) / k.stride + 1;
+            elems[2 + i] = (size_t)H * W * k.c;
+            if (elems[2 + i] > per) per = elems[2 + i];
+        }
+    }
+    elems[10] = 512;
+    float *stem, *pool, *tbase, *gem;
+    REID_TRY(ctx_ws(ctx, "se18.stem", (size_t)n * elems[0] * 4, (void**)&stem));
+    REID_TRY(ctx_ws(ctx, "se18.pool", (size_t)n * per * 4, (void**)&pool));
+    REID_TRY(ctx_ws(ctx, "se18.t", (size_t)n * per * 4 * (keep ? 4 * 8 : 4), (void**)&tbase));
+    REID_TRY(ctx_ws(ctx, "se18.gem", (size_t)n * 512 * 4, (void**)&gem));
+    float* stage[11];
+    // stem: conv7x7 s2 p3 + BN, no ReLU (SERes18_IBN.py:251-253), then MaxPool2d(3, 2, 1) with -inf padding (:254; maxpool3s2_kernel skips
+    // the taps outside the map, at odd sizes too)
+    REID_TRY(any_conv(ctx, A_STEM_F32, x, n, h, w, 3, wt.stem_w, 64, 7, 2, 3, wt.stem_scale, wt.stem_shift, nullptr, 0, 0, stem));
+    REID_TRY(launch_maxpool3s2(ctx, stem, n, H1, W1, 64, pool));
+    stage[0] = stem;
+    stage[1] = pool;
+    const float* cur = pool;
+    int H = H2, W = W2;
+    for (int i = 0; i < 8; ++i) {
+        const Se18Block& k = wt.blk[i];
+        float* free_[3];
+        int nf = 0;
+        for (int j = 0; j < 4 && nf < 3; ++j) {
+            float* t = tbase + ((size_t)(keep ? i * 4 : 0) + j) * n * per;
+            if (t != cur) free_[nf++] = t;
+        }
+        float *c1 = free_[0], *y = free_[1], *sc = free_[2];
+        const int Ho = (H + 2 - 3) / k.stride + 1, Wo = (W + 2 - 3) / k.stride + 1, hw = Ho * Wo;
+        if (k.ibn) {   // BatchNorm half + ReLU in conv1's epilogue, InstanceNorm half (statistics of the whole image) by one pass in place
+            REID_TRY(any_conv(ctx, A_IM2COL, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, wt.ep + (size_t)i * 1024,
+                              wt.ep + (size_t)i * 1024 + 512, nullptr, 1, k.c / 2, c1));
+            REID_TRY(launch_any_norm(ctx, c1, n, hw, k.c, k.c / 2, k.in_gamma, k.in_beta, nullptr, nullptr));
+        } else {
+            REID_TRY(any_conv(ctx, A_IM2COL, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, k.bn1_scale, k.bn1_shift, nullptr, 1, 0, c1));
+        }
+        // a block without a downsample is the whole BasicBlock_IBN: residual + ReLU before the SE scale, the input added again after
+        REID_TRY(any_conv(ctx, A_IM2COL, c1, n, Ho, Wo, k.c, k.conv2_w, k.c, 3, 1, 1, k.bn2_scale, k.bn2_shift, k.ds ? nullptr : cur,
+                          k.ds ? 0 : 1, 0, y));
+        const float* shortcut = cur;
+        if (k.ds) {
+            REID_TRY(any_conv(ctx, A_IM2COL, cur, n, H, W, k.cin, k.ds_w, k.c, 1, k.stride, 0, k.ds_scale, k.ds_shift, nullptr, 0, 0, sc));
+            shortcut = sc;
+        }
+        float* out = c1;   // conv1's output is dead after conv2
+        REID_TRY(launch_any_se_tail(ctx, y, shortcut, n, hw, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr));
+        stage[2 + i] = out;
+        cur = out;
+        H = Ho;
+        W = Wo;
+    }
+    REID_TRY(launch_any_gem(ctx, cur, n, H * W, 512, wt.gem_p, wt.neck_scale, wt.neck_shift, gem, d_emb));
+    {   // SERse18_IBN.forward(x, cam): + cam_factor * cam_bias[cam] on the BNNeck output, before the classifier (:269-271)
+        const int32_t* d_cam;
+        REID_TRY(ctx_take_side(ctx, n, wt.num_cams, "reid_embed (camera bias)", &d_cam));
+        if (d_cam) REID_TRY(launch_add_indexed_rows(ctx, d_emb, n, 1, 512, wt.cam_bias, d_cam, wt.cam_factor));
+    }
+    stage[10] = gem;
+    if (d_logits) {
+        if (!wt.cls_w) {
+            reid_set_error("logits requested but the weight blob has no classifier (cls.w)");
+            return REID_ERR_STATE;
+        }
+        GemmParams p;
+        memset(&p, 0, sizeof(p));
+        p.A = d_emb; p.lda = 512;
+        p.B = wt.cls_w; p.ldb = 512;
+        p.M = n; p.N = wt.num_class; p.K = 512;
+        p.C = d_logits; p.ldc = wt.num_class;
+        REID_TRY(launch_gemm_f32(ctx, A_DENSE, E_BIAS, p, REID_K_CONV_GEMM, 2.0 * n * wt.num_class * 512,
+                                 ((double)n * 512 + (double)wt.num_class * 512 + (double)n * wt.num_class) * 4.0));
+    }
+    ctx->last_n = n;
+    ctx->last_f16 = false;
+    for (int s = 0; s < 11; ++s) {
+        ctx->stage_ptr[s] = stage[s];
+        ctx->stage_elems[s] = elems[s];
+    }
+    return REID_OK;
+}
+
+int se_any_run_nchw(reid_ctx* ctx, const float* d_x, int m, int h, int w, int mirror, float* d_emb, float* d_log) {
+    const AnysizeApi* api;
+    REID_TRY(anysize_api(&api));
+    float* nhwc;
+    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * h * w * 3 * 4, (void**)&nhwc));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)m * h * w * 24.0);
+    const hipError_t e = api->to_nhwc(ctx->stream, d_x, m, h, w, mirror, nhwc);
+    prof_end(ctx);
+    REID_TRY(any_launched(e, "anysize_nchw_to_nhwc3"));
+    return seres18_forward_any(ctx, nhwc, m, h, w, d_emb, d_log);
+}
+
+static int se_any_run_windows(reid_ctx* ctx, const RaggedSrc& src, int i, int m, int h, int w, const float* mean_std6, float* d_emb, float* d_log) {
+    const AnysizeApi* api;
+    REID_TRY(anysize_api(&api));
+    float* nhwc;
+    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * h * w * 3 * 4, (void**)&nhwc));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)m * h * w * 15.0);
+    const hipError_t e = api->resize(ctx->stream, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, h, w, src.pitch, mean_std6, nhwc);
+    prof_end(ctx);
+    REID_TRY(any_launched(e, "anysize_resize_norm"));
+    return seres18_forward_any(ctx, nhwc, m, h, w, d_emb, d_log);
+}
+
+extern "C" int reid_embed_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits) {
+    ARG_CHECK(ctx && d_x && d_emb && n >= 0);
+    REID_TRY(se_any_ready(ctx, h, w, "reid_embed_f32_nchw_hw"));
+    if (!se_any_routes(ctx, h, w)) return reid_embed_f32_nchw_dev(ctx, d_x, n, d_emb, d_logits);
+    CTX_ENTER(ctx);
+    const int nc = ctx->se18.num_class;
+    const size_t img = (size_t)3 * h * w;
+    return embed_dev_passes(n, se_any_pass(ctx, h, w), [&](int i, int m) -> int {
+        return se_any_run_nchw(ctx, d_x + (size_t)i * img, m, h, w, 0, d_emb + (size_t)i * 512, d_logits ? d_logits + (size_t)i * nc : nullptr);
+    });
+}
+
+extern "C" int reid_embed_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits) {
+    ARG_CHECK(ctx && x && emb && n >= 0);
+    REID_TRY(se_any_ready(ctx, h, w, "reid_embed_f32_nchw_hw"));
+    if (!se_any_routes(ctx, h, w)) return reid_embed_f32_nchw(ctx, x, n, emb, logits);
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    const size_t img = (size_t)3 * h * w;
+    float* d_in;
+    EmbedOut out{emb, logits, 512, ctx->se18.num_class};
+    REID_TRY(ctx_ws(ctx, "io.in", (size_t)n * img * 4, (void**)&d_in));
+    REID_TRY(out.alloc(ctx, "io", n, 0, logits != nullptr));
+    return embed_host(
+        ctx, n, se_any_pass(ctx, h, w),
+        [&](int i, int m, hipStream_t s) -> int {
+            HIP_TRY(hipMemcpyAsync(d_in + (size_t)i * img, x + (size_t)i * img, (size_t)m * img * 4, hipMemcpyHostToDevice, s));
+            return REID_OK;
+        },
+        [&](int i, int m, float* d_emb, float* d_log) -> int { return se_any_run_nchw(ctx, d_in + (size_t)i * img, m, h, w, 0, d_emb, d_log); }, out);
+}
+
+// Extractor._preprocess to out_h x out_w: the cv2-style bilinear resize, then (v - mean[c]) / std[c]; mean_std6 NULL = 0.5 / 0.5, the
+// tracker's Normalize (feature_extractor.py:41-46) and the only one the 256 x 128 entry knows
+extern "C" int reid_embed_ragged_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                       int out_w, const float* mean_std6, float* emb, float* logits) {
+    ARG_CHECK(ctx && packed && offsets && hw && emb && n >= 0);
+    static const float kHalf[6] = {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f};
+    if (!mean_std6) mean_std6 = kHalf;
+    for (int i = 0; i < 6; ++i) ARG_CHECK(std::isfinite(mean_std6[i]) && (i < 3 || mean_std6[i] > 0.f));
+    REID_TRY(se_any_ready(ctx, out_h, out_w, "reid_embed_ragged_u8_hw"));
+    if (!se_any_routes(ctx, out_h, out_w)) {
+        if (memcmp(mean_std6, kHalf, sizeof(kHalf)) != 0) {
+            reid_set_error("reid_embed_ragged_u8_hw: at 256 x 128 the existing forward normalises with mean = std = 0.5 only");
+            return REID_ERR_ARG;
+        }
+        return reid_embed_ragged_u8(ctx, packed, offsets, hw, n, emb, logits);
+    }
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    RaggedSrc src{packed, offsets, hw, n};
+    REID_TRY(src.check());
+    EmbedOut out{emb, logits, 512, ctx->se18.num_class};
+    REID_TRY(src.alloc(ctx, "io"));
+    REID_TRY(out.alloc(ctx, "io", n, 0, logits != nullptr));
+    return embed_host(
+        ctx, n, se_any_pass(ctx, out_h, out_w), [&](int i, int m, hipStream_t s) -> int { return src.up(i, m, s); },
+        [&](int i, int m, float* d_emb, float* d_log) -> int { return se_any_run_windows(ctx, src, i, m, out_h, out_w, mean_std6, d_emb, d_log); },
+        out);
 }
 
 int ragged_enqueue_begin(reid_ctx* ctx, const char* tag, RaggedSrc& src, EmbedOut& out, bool want_logits, bool side_copy) {

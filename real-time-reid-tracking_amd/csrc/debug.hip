@@ -25,7 +25,7 @@ const Switch kSwitches[] = {
     {"f16_se_tail", &reid_ctx::f16_se_tail}, {"f16_c64", &reid_ctx::f16_c64}, {"swin_chunk_cap", &reid_ctx::swin_chunk_cap},
     {"split_x3", &reid_ctx::split_x3}, {"x3_ablate", &reid_ctx::x3_ablate}, {"x3_unroll", &reid_ctx::x3_unroll}, {"x3_narrow", &reid_ctx::x3_narrow}, {"conv_x3s", &reid_ctx::conv_x3s}, {"x3s_sk_cap", &reid_ctx::x3s_sk_cap}, {"x3_l4_narrow_nmt", &reid_ctx::x3_l4_narrow_nmt}, {"split_x3_small", &reid_ctx::split_x3_small}, {"split_x3_min_blocks", &reid_ctx::split_x3_min_blocks}, {"f32_dist_bk16", &reid_ctx::f32_dist_bk16}, {"lin_x3", &reid_ctx::lin_x3},
     {"host_pipeline", &reid_ctx::host_pipeline}, {"x3_sk_cap", &reid_ctx::x3_sk_cap}, {"chain", &reid_ctx::chain}, {"split_gemm_min_tiles", &reid_ctx::split_gemm_min_tiles},
-    {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc}, {"gem_tail_min", &reid_ctx::gem_tail_min},
+    {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc}, {"gem_tail_min", &reid_ctx::gem_tail_min}, {"anysize_force", &reid_ctx::anysize_force},
 };
 }  // namespace
 
@@ -667,6 +667,67 @@ extern "C" int reid_debug_gem_neck(reid_ctx* ctx, int f16, int n, int hw, int c,
         REID_TRY(dbg_upload(ctx, "dbgt.x", (const float*)x, nx, &dx));
         REID_TRY(launch_gem_neck(ctx, dx, n, hw, c, dp, dsc, dsh, dg, de));
     }
+    if (dg) REID_TRY(dbg_download(ctx, gem_out, dg, ne));
+    REID_TRY(dbg_download(ctx, emb, de, ne));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// ---- the kernels of libreid_hip_anysize.so (anysize.h; tests/test_gpu_anysize.py) through the launchers the any-size forward calls.  Every
+// output buffer carries one guard pixel (c floats) behind the last image, set to 0xff bytes with the rest and returned with it.
+extern "C" int reid_debug_any_norm(reid_ctx* ctx, int n, int hw, int c, int half, const float* x, const float* in_gamma, const float* in_beta,
+                                   const float* bn_scale, const float* bn_shift, float* out) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && half >= 32 && half <= c && x && in_gamma && in_beta && out &&
+              (bn_scale == nullptr) == (bn_shift == nullptr));
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)n * hw * c;
+    float *dx, *dg, *db, *dbs = nullptr, *dbh = nullptr;
+    REID_TRY(dbg_output(ctx, "dbgt.x", nx + c, &dx));
+    HIP_TRY(hipMemcpyAsync(dx, x, nx * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(dbg_upload(ctx, "dbgt.gamma", in_gamma, (size_t)half, &dg));
+    REID_TRY(dbg_upload(ctx, "dbgt.beta", in_beta, (size_t)half, &db));
+    if (bn_scale && c > half) {
+        REID_TRY(dbg_upload(ctx, "dbgt.bns", bn_scale, (size_t)(c - half), &dbs));
+        REID_TRY(dbg_upload(ctx, "dbgt.bnh", bn_shift, (size_t)(c - half), &dbh));
+    }
+    REID_TRY(launch_any_norm(ctx, dx, n, hw, c, half, dg, db, dbs, dbh));
+    REID_TRY(dbg_download(ctx, out, dx, nx + c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_any_se_tail(reid_ctx* ctx, int n, int hw, int c, int mid, const float* w1, const float* w2t, const float* y,
+                                      const float* shortcut, float* out, float* gate) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && mid >= 1 && w1 && w2t && y && shortcut && out);
+    CTX_ENTER(ctx);
+    const size_t ny = (size_t)n * hw * c;
+    float *dw1, *dw2, *dy, *dsc, *dout, *dgate = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", w1, (size_t)mid * c, &dw1));
+    REID_TRY(dbg_upload(ctx, "dbgt.w2", w2t, (size_t)mid * c, &dw2));
+    REID_TRY(dbg_upload(ctx, "dbgt.x", y, ny, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgt.sc", shortcut, ny, &dsc));
+    REID_TRY(dbg_output(ctx, "dbgt.out", ny + c, &dout));
+    if (gate) REID_TRY(dbg_output(ctx, "dbgt.a", (size_t)n * c + c, &dgate));
+    REID_TRY(launch_any_se_tail(ctx, dy, dsc, n, hw, c, mid, dw1, dw2, dout, dgate));
+    REID_TRY(dbg_download(ctx, out, dout, ny + c));
+    if (dgate) REID_TRY(dbg_download(ctx, gate, dgate, (size_t)n * c + c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, const float* x, const float* scale, const float* shift,
+                                  float* gem_out, float* emb) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && x && scale && shift && emb);
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)n * hw * c, ne = (size_t)n * c + c;
+    float *dx, *dp, *dsc, *dsh, *dg = nullptr, *de;
+    REID_TRY(dbg_upload(ctx, "dbgt.p", &p, 1, &dp));
+    REID_TRY(dbg_upload(ctx, "dbgt.bns", scale, (size_t)c, &dsc));
+    REID_TRY(dbg_upload(ctx, "dbgt.bnh", shift, (size_t)c, &dsh));
+    REID_TRY(dbg_upload(ctx, "dbgt.x", x, nx, &dx));
+    if (gem_out) REID_TRY(dbg_output(ctx, "dbgt.a", ne, &dg));
+    REID_TRY(dbg_output(ctx, "dbgt.b", ne, &de));
+    REID_TRY(launch_any_gem(ctx, dx, n, hw, c, dp, dsc, dsh, dg, de));
     if (dg) REID_TRY(dbg_download(ctx, gem_out, dg, ne));
     REID_TRY(dbg_download(ctx, emb, de, ne));
     HIP_TRY(hipStreamSynchronize(ctx->stream));

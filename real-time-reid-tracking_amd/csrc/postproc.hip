@@ -184,9 +184,12 @@ int gemm_nt_dev(reid_ctx* ctx, const float* a, int m, const float* b, int n, int
 // data_transforms.py:56-130); out: [n][512 + num_class].  flip_tta != 0 averages the descriptor of the mirrored image.
 // before_view(v, i, m) runs before the forward of images [i, i + m) of view v (0 plain, 1 mirrored): nothing for the float entries,
 // the side indices of the pass for reid_descriptor_images_u8.
+// h x w other than 256 x 128 (or the debug switch anysize_force): the any-size forward of api.hip in passes of se_any_pass images, the
+// mirrored view read with reversed columns by its layout kernel (no flipped copy of the batch).
 template <class BeforeView>
-static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, float* d_out, BeforeView before_view) {
+static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out, BeforeView before_view) {
     ARG_CHECK(ctx && d_x && d_out && n >= 0);
+    REID_TRY(se_any_ready(ctx, h, w, "reid_descriptor_*_hw"));
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
     int de = 0, nc = 0;
@@ -195,11 +198,29 @@ static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, 
         reid_set_error("reid_descriptor_*: the loaded weights have no classifier (cls.w), the descriptor needs the logits");
         return REID_ERR_STATE;
     }
-    const size_t img = (size_t)3 * 256 * 128;
+    const size_t img = (size_t)3 * h * w;
     float *e1, *l1, *e2 = nullptr, *l2 = nullptr, *xf = nullptr;
     REID_TRY(ctx_ws(ctx, "pp.e1", (size_t)n * de * 4, (void**)&e1));
     REID_TRY(ctx_ws(ctx, "pp.l1", (size_t)n * nc * 4 + 16, (void**)&l1));
     REID_TRY(before_view(0, 0, n));
+    if (se_any_routes(ctx, h, w)) {
+        REID_TRY(reid_embed_f32_nchw_hw_dev(ctx, d_x, n, h, w, e1, l1));
+        if (flip_tta) {
+            REID_TRY(ctx_ws(ctx, "pp.e2", (size_t)n * de * 4, (void**)&e2));
+            REID_TRY(ctx_ws(ctx, "pp.l2", (size_t)n * nc * 4 + 16, (void**)&l2));
+            const int pass = se_any_pass(ctx, h, w);
+            for (int i = 0; i < n; i += pass) {
+                const int m = n - i < pass ? n - i : pass;
+                REID_TRY(before_view(1, i, m));
+                REID_TRY(se_any_run_nchw(ctx, d_x + (size_t)i * img, m, h, w, 1, e2 + (size_t)i * de, l2 + (size_t)i * nc));
+            }
+        }
+        prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * (de + nc) * 4.0 * (flip_tta ? 3 : 2));
+        hipLaunchKernelGGL(descriptor_kernel, dim3(n), dim3(256), 0, ctx->stream, e1, l1, e2, l2, de, nc, d_out);
+        prof_end(ctx);
+        LAUNCH_CHECK();
+        return REID_OK;
+    }
     REID_TRY(reid_embed_f32_nchw_dev(ctx, d_x, n, e1, l1));
     if (flip_tta) {
         REID_TRY(ctx_ws(ctx, "pp.e2", (size_t)n * de * 4, (void**)&e2));
@@ -223,25 +244,48 @@ static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, 
     return REID_OK;
 }
 
-extern "C" int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, float* d_out) {
-    return descriptor_dev(ctx, d_x, n, flip_tta, d_out, [](int, int, int) -> int { return REID_OK; });
+// the debug switch anysize_force belongs to the reid_*_hw entries: the entries without a size keep the 256 x 128 forward whatever it says
+struct ForceOff {
+    reid_ctx* ctx;
+    int saved;
+    explicit ForceOff(reid_ctx* c) : ctx(c), saved(c ? c->anysize_force : 0) {
+        if (ctx) ctx->anysize_force = 0;
+    }
+    ~ForceOff() {
+        if (ctx) ctx->anysize_force = saved;
+    }
+};
+
+extern "C" int reid_descriptor_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out) {
+    return descriptor_dev(ctx, d_x, n, h, w, flip_tta, d_out, [](int, int, int) -> int { return REID_OK; });
 }
 
-extern "C" int reid_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, int flip_tta, float* out) {
+extern "C" int reid_descriptor_f32_nchw_dev(reid_ctx* ctx, const float* d_x, int n, int flip_tta, float* d_out) {
+    ForceOff off(ctx);
+    return descriptor_dev(ctx, d_x, n, 256, 128, flip_tta, d_out, [](int, int, int) -> int { return REID_OK; });
+}
+
+extern "C" int reid_descriptor_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, int flip_tta, float* out) {
     ARG_CHECK(ctx && x && out && n >= 0);
+    REID_TRY(se_any_ready(ctx, h, w, "reid_descriptor_f32_nchw_hw"));
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
     int de = 0, nc = 0;
     REID_TRY(reid_seres18_dims(ctx, &de, &nc));
-    const size_t img = (size_t)3 * 256 * 128;
+    const size_t img = (size_t)3 * h * w;
     float *dx, *dout;
     REID_TRY(ctx_ws(ctx, "pp.x", (size_t)n * img * 4, (void**)&dx));
     REID_TRY(ctx_ws(ctx, "pp.out", (size_t)n * (de + (nc > 0 ? nc : 0)) * 4 + 16, (void**)&dout));
     HIP_TRY(hipMemcpyAsync(dx, x, (size_t)n * img * 4, hipMemcpyHostToDevice, ctx->stream));
-    REID_TRY(reid_descriptor_f32_nchw_dev(ctx, dx, n, flip_tta, dout));
+    REID_TRY(reid_descriptor_f32_nchw_hw_dev(ctx, dx, n, h, w, flip_tta, dout));
     HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * (de + nc) * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, int flip_tta, float* out) {
+    ForceOff off(ctx);
+    return reid_descriptor_f32_nchw_hw(ctx, x, n, 256, 128, flip_tta, out);
 }
 
 // uint8 images of any sizes in: transforms.Resize((256, 128)) as PIL computes it -> ToTensor -> Normalize on the device (PilPlan,
@@ -250,8 +294,8 @@ extern "C" int reid_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, in
 // plain and the mirrored view of an image, as the script's model(img, cam.repeat(2)) and as reid_swin_descriptor_*; the float entry
 // computes the same when it is given the indices twice (its plain passes take the first n, its mirrored passes the next n).  None stays
 // pending.
-extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
-                                         const float* mean_std6, int flip_tta, float* out) {
+extern "C" int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                            int out_w, const float* mean_std6, int flip_tta, float* out) {
     ARG_CHECK(ctx);
     struct SideDrop {
         reid_ctx* ctx;
@@ -264,6 +308,7 @@ extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, c
     REID_TRY(pil_mean_std(&mean_std6));
     RaggedSrc src{packed, offsets, hw, n};
     REID_TRY(src.check());
+    REID_TRY(se_any_ready(ctx, out_h, out_w, "reid_descriptor_images_u8_hw"));
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
     int de = 0, nc = 0;
@@ -272,9 +317,9 @@ extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, c
         reid_set_error("reid_descriptor_*: the loaded weights have no classifier (cls.w), the descriptor needs the logits");
         return REID_ERR_STATE;
     }
-    const int pass = ctx->chunk;
+    const int pass = se_any_routes(ctx, out_h, out_w) ? se_any_pass(ctx, out_h, out_w) : ctx->chunk;
     PilPlan plan;
-    REID_TRY(plan.build(src, 256, 128, mean_std6, pass));
+    REID_TRY(plan.build(src, out_h, out_w, mean_std6, pass));
     std::vector<int32_t> side;
     if (!ctx->side_idx.empty()) {
         side.assign(ctx->side_idx.begin() + ctx->side_cursor, ctx->side_idx.end());
@@ -295,7 +340,7 @@ extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, c
         },
         [&](int i, int m, float* d_row, float*) -> int {
             REID_TRY(plan.launch(ctx, src, i, m, nullptr, plan.d_f32));
-            return descriptor_dev(ctx, plan.d_f32, m, flip_tta, d_row, [&](int, int, int) -> int {
+            return descriptor_dev(ctx, plan.d_f32, m, out_h, out_w, flip_tta, d_row, [&](int, int, int) -> int {
                 if (!side.empty()) {
                     ctx->side_idx.assign(side.begin() + i, side.begin() + i + m);
                     ctx->side_cursor = 0;
@@ -304,6 +349,12 @@ extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, c
             });
         },
         o);
+}
+
+extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
+                                         const float* mean_std6, int flip_tta, float* out) {
+    ForceOff off(ctx);
+    return reid_descriptor_images_u8_hw(ctx, packed, offsets, hw, n, 256, 128, mean_std6, flip_tta, out);
 }
 
 // d_x [n][d] is updated in place; cams is a HOST array of camera ids >= 0 (ids without rows are skipped: the reference's

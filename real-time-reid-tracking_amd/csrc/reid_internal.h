@@ -489,6 +489,8 @@ struct reid_ctx {
     size_t side_cursor = 0;              // how many of them the passes so far have consumed
     const char* frame_out[2] = {nullptr, nullptr};
     float* stage_ptr[11] = {nullptr};
+    size_t stage_elems[11] = {0};   // floats per image of each stage tap of the last pass, when that pass ran the any-size forward (else 0)
+    int anysize_force = 0;   // libreid_hip_debug.so switch: 256 x 128 through the any-size forward too (reid_*_hw entries; A/B and tests)
     unsigned long long* conv_diag = nullptr;   // experiments (debug.hip): stamps of the loader-wave conv kernel
     // Which launch the last f16 convolution launcher made, written on the host only (harnesses read it, include/reid_hip_debug.h:
     // reid_debug_conv_layer_f16).  launch_gemm_f16: the tile configuration BN*1000 + BK*10 + NST; launch_conv3x3_f16: BN*10 + split K;
@@ -746,6 +748,24 @@ int bank_geometry(const reid_bank* b, int* max_tracks, int* budget, int* d);
 // The library `file` in the directory this library lies in: opened (RTLD_NOW | RTLD_LOCAL), fns[k] = its symbol names[k].  A missing file
 // ("<what> <path> beside libreid_hip.so: <dlerror>") or symbol ("<path> lacks a / b", the handle closed again) is REID_ERR_STATE.
 int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns);
+// ---- ResNet18-IBN-SE at input sizes other than 256 x 128 (api.hip; kernels: anysize.h).  The reid_*_hw entries hand 256 x 128 to the
+// existing entries unless the debug switch anysize_force is set (se_any_routes).  se_any_ready: everything such a call would refuse, with
+// nothing queued - a side outside 32 .. 512 (REID_ERR_ARG), weights not loaded (REID_ERR_STATE), an architecture other than seres18_ibn or
+// a precision mode other than 0 (REID_ERR_ARG naming both), libreid_hip_anysize.so (REID_ERR_STATE).  se_any_pass: images per pass, the
+// context's chunk scaled by 256 * 128 / (h * w) and clamped to 1 .. 4096.  se_any_run_nchw: one pass from fp32 NCHW [m][3][h][w] on the
+// device (mirror: the horizontally flipped view); se_any_run_windows: from uploaded uint8 windows through the cv2-style resize.
+struct RaggedSrc;
+bool se_any_routes(const reid_ctx* ctx, int h, int w);
+int se_any_ready(reid_ctx* ctx, int h, int w, const char* who);
+int se_any_pass(const reid_ctx* ctx, int h, int w);
+int se_any_run_nchw(reid_ctx* ctx, const float* d_x, int m, int h, int w, int mirror, float* d_emb, float* d_log);
+// debug.hip harnesses: the three kernel families of libreid_hip_anysize.so on device operands, with the context's profiling slot
+int launch_any_norm(reid_ctx* ctx, float* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta, const float* bn_scale,
+                    const float* bn_shift);
+int launch_any_se_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int hw, int c, int mid, const float* w1, const float* w2t,
+                       float* out, float* gate_out);
+int launch_any_gem(reid_ctx* ctx, const float* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out,
+                   float* emb);
 void prof_begin(reid_ctx* ctx, int kind, double flops, double bytes);
 void prof_end(reid_ctx* ctx);
 

@@ -13,6 +13,37 @@ from ._ffi import check
 _ENGINES = {}
 
 IMG_H, IMG_W = 256, 128   # Extractor.size = (128, 256) as (W, H), feature_extractor.py:24
+SIZE_MIN, SIZE_MAX = 32, 512   # input sides of the any-size forward (reid_*_hw, include/reid_hip.h)
+
+
+def check_hw(size):
+    """(H, W) of a ResNet18-IBN-SE input, each side an integer in [32, 512]; ValueError otherwise, before any device call."""
+    try:
+        h, w = size
+        if int(h) != h or int(w) != w:
+            raise TypeError
+        h, w = int(h), int(w)
+    except (TypeError, ValueError):
+        raise ValueError("size must be (H, W) integers, got %r" % (size,))
+    if not (SIZE_MIN <= h <= SIZE_MAX and SIZE_MIN <= w <= SIZE_MAX):
+        raise ValueError("input size (H, W) = (%d, %d): each side must be in [%d, %d]" % (h, w, SIZE_MIN, SIZE_MAX))
+    return h, w
+
+
+def any_pass_size(chunk, h, w):
+    """Images per pass of the any-size forward: the context's chunk scaled by 256 * 128 / (h * w), clamped to 1 .. 4096 (se_any_pass)."""
+    return max(1, min(4096, int(chunk) * IMG_H * IMG_W // (int(h) * int(w))))
+
+
+def stage_shapes(h, w):
+    """[(Ho, Wo, C)] of the ten activation taps of reid_debug_stage for an h x w input (stem, pool, eight blocks)."""
+    h1, w1 = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    hh, ww = (h1 - 1) // 2 + 1, (w1 - 1) // 2 + 1
+    out = [(h1, w1, 64), (hh, ww, 64)]
+    for c, stride in ((64, 1), (64, 1), (128, 2), (128, 1), (256, 2), (256, 1), (512, 1), (512, 1)):
+        hh, ww = (hh - 1) // stride + 1, (ww - 1) // stride + 1
+        out.append((hh, ww, c))
+    return out
 
 
 def _f32(a):
@@ -307,11 +338,14 @@ class Engine:
                 raise ValueError("image %d is %d x %d, a source side may be %d at most" % (i, shp[0], shp[1], cls.PIL_MAX_SIDE))
         return cls._pack_ragged(images)
 
-    def descriptor_images_u8(self, images, flip_tta=True, mean_std=None):
+    def descriptor_images_u8(self, images, flip_tta=True, mean_std=None, size=None):
         """list of uint8[h_i,w_i,3] images of any sizes -> float32 [n, 512 + num_class]: transforms.Resize((256, 128)) as PIL computes
         it, ToTensor and Normalize(mean_std; None: ImageNet) on the device, then the descriptor of descriptor_f32_nchw, to whose result
-        on host-preprocessed images this is bit-identical (reid_descriptor_images_u8)."""
+        on host-preprocessed images this is bit-identical (reid_descriptor_images_u8).  ``size`` = (H, W), sides 32 .. 512: Resize(size)
+        and the any-size forward (reid_descriptor_images_u8_hw; seres18_ibn weights, exact fp32) - the script's VeRi geometry is
+        (224, int(ratio * 224))."""
         _, _, ms = self._swin_crop_args((224, 224), mean_std)
+        hw_out = None if size is None else check_hw(size)
         images = list(images)
         n = len(images)
         src, offs, hw, _keep = self._pack_images(images)
@@ -319,6 +353,10 @@ class Engine:
         if nc <= 0:
             raise ValueError("a descriptor needs loaded weights with a classifier (Engine.load_seres18)")
         out = np.empty((n, self.embed_dim + nc), np.float32)
+        if hw_out is not None:
+            check(self.lib.reid_descriptor_images_u8_hw(self.h, src, _ptr(offs), _ptr(hw), n, hw_out[0], hw_out[1], _ptr(ms), int(bool(flip_tta)),
+                                                        _ptr(out)))
+            return out
         check(self.lib.reid_descriptor_images_u8(self.h, src, _ptr(offs), _ptr(hw), n, _ptr(ms), int(bool(flip_tta)), _ptr(out)))
         return out
 
@@ -370,13 +408,22 @@ class Engine:
         packed = np.concatenate([c.reshape(-1) for c in flat]) if flat else np.empty(0, np.uint8)
         return _ptr(packed), offs, hw, packed
 
-    def embed_ragged_u8(self, crops, logits=False):
+    def embed_ragged_u8(self, crops, logits=False, size=None, mean_std=None):
         """list of uint8[h_i,w_i,3] -> float32[n,512]; resize + normalise run on the device.  Crops that already lie one after
         the other in ONE host buffer (views of a stacked array, slices of a pinned slab) are handed over in place - no packing copy;
-        more crops than a pass holds go up pass by pass under the kernels (csrc/api.hip reid_embed_ragged_u8)."""
+        more crops than a pass holds go up pass by pass under the kernels (csrc/api.hip reid_embed_ragged_u8).  ``size`` = (H, W), sides
+        32 .. 512, resizes to that instead of (256, 128) and ``mean_std`` = (mean[3], std[3]) replaces the 0.5 / 0.5 of the tracker's
+        Normalize (reid_embed_ragged_u8_hw; other sizes: seres18_ibn weights, exact fp32)."""
+        hw_out = None if size is None else check_hw(size)
+        if mean_std is not None and hw_out is None:
+            hw_out = (IMG_H, IMG_W)
+        _, _, ms = self._swin_crop_args((224, 224), mean_std)
         n = len(crops)
         src, offs, hw, _keep = self._pack_ragged(crops)
         emb, lg = self._outs(n, logits)
+        if hw_out is not None:
+            check(self.lib.reid_embed_ragged_u8_hw(self.h, src, _ptr(offs), _ptr(hw), n, hw_out[0], hw_out[1], _ptr(ms), _ptr(emb), _ptr(lg)))
+            return self._ret(emb, lg, logits)
         check(self.lib.reid_embed_ragged_u8(self.h, src, _ptr(offs), _ptr(hw), n, _ptr(emb), _ptr(lg)))
         return self._ret(emb, lg, logits)
 
@@ -543,14 +590,25 @@ class Engine:
         return self._ret(emb, lg, logits)
 
     def embed_f32_nchw(self, x, logits=False):
+        """float32 [n,3,H,W] -> float32 [n,512] (and logits).  (256, 128) runs the loaded architecture in the context's precision;
+        any other H, W in 32 .. 512 the any-size forward (reid_embed_f32_nchw_hw: seres18_ibn weights, exact fp32)."""
         x = _f32(x)
-        if x.ndim != 4 or x.shape[1:] != (3, IMG_H, IMG_W):
-            raise ValueError("embed_f32_nchw expects float32[n,3,%d,%d], got %s" % (IMG_H, IMG_W, x.shape))
+        if x.ndim != 4 or x.shape[1] != 3:
+            raise ValueError("embed_f32_nchw expects float32[n,3,H,W] (%d x %d, or sides in [%d, %d]), got %s"
+                             % (IMG_H, IMG_W, SIZE_MIN, SIZE_MAX, x.shape))
+        h, w = check_hw(x.shape[2:])
         emb, lg = self._outs(x.shape[0], logits)
+        if (h, w) != (IMG_H, IMG_W):
+            check(self.lib.reid_embed_f32_nchw_hw(self.h, _ptr(x), x.shape[0], h, w, _ptr(emb), _ptr(lg)))
+            return self._ret(emb, lg, logits)
         check(self.lib.reid_embed_f32_nchw(self.h, _ptr(x), x.shape[0], _ptr(emb), _ptr(lg)))
         return self._ret(emb, lg, logits)
 
-    def embed_f32_nchw_dev(self, d_x, n, d_emb, d_logits=None):
+    def embed_f32_nchw_dev(self, d_x, n, d_emb, d_logits=None, size=None):
+        if size is not None:
+            h, w = check_hw(size)
+            check(self.lib.reid_embed_f32_nchw_hw_dev(self.h, C.c_void_p(d_x), int(n), h, w, C.c_void_p(d_emb), C.c_void_p(d_logits or 0)))
+            return
         check(self.lib.reid_embed_f32_nchw_dev(self.h, C.c_void_p(d_x), int(n), C.c_void_p(d_emb), C.c_void_p(d_logits or 0)))
 
     def embed_u8_dev(self, d_crops, n, d_emb, d_logits=None):
@@ -586,8 +644,11 @@ class Engine:
     def debug_keep(self, on):
         check(self.lib.reid_ctx_set_debug_keep(self.h, int(on)))
 
-    def debug_stage(self, stage, n):
+    def debug_stage(self, stage, n, size=None):
+        """Tap ``stage`` of the last pass (n images) as a flat array; ``size`` = (H, W) of that pass's input when it was not 256 x 128."""
         sizes = [524288, 131072, 131072, 131072, 65536, 65536, 32768, 32768, 65536, 65536, 512]
+        if size is not None:
+            sizes = [a * b * c for a, b, c in stage_shapes(*check_hw(size))] + [512]
         out = np.empty(sizes[stage] * n, np.float32)
         cnt = C.c_size_t()
         check(self.lib.reid_debug_stage(self.h, int(stage), _ptr(out), out.size, C.byref(cnt)))
@@ -1056,17 +1117,54 @@ class Engine:
                                     C.c_void_p(d_D), C.c_void_p(d_I)))
 
     def descriptor_f32_nchw(self, x, flip_tta=True):
-        """float32 [n,3,256,128] (normalised by the caller) -> float32 [n, 512 + num_class] retrieval descriptor."""
+        """float32 [n,3,H,W] (normalised by the caller) -> float32 [n, 512 + num_class] retrieval descriptor; sizes as embed_f32_nchw."""
         x = _f32(x)
-        if x.ndim != 4 or x.shape[1:] != (3, IMG_H, IMG_W):
-            raise ValueError("descriptor_f32_nchw expects [n,3,%d,%d], got %s" % (IMG_H, IMG_W, x.shape))
+        if x.ndim != 4 or x.shape[1] != 3:
+            raise ValueError("descriptor_f32_nchw expects [n,3,H,W] (%d x %d, or sides in [%d, %d]), got %s"
+                             % (IMG_H, IMG_W, SIZE_MIN, SIZE_MAX, x.shape))
+        h, w = check_hw(x.shape[2:])
         de, nc = self.embed_dim, self.num_class
         out = np.empty((x.shape[0], de + nc), np.float32)
+        if (h, w) != (IMG_H, IMG_W):
+            check(self.lib.reid_descriptor_f32_nchw_hw(self.h, _ptr(x), x.shape[0], h, w, int(bool(flip_tta)), _ptr(out)))
+            return out
         check(self.lib.reid_descriptor_f32_nchw(self.h, _ptr(x), x.shape[0], int(bool(flip_tta)), _ptr(out)))
         return out
 
-    def descriptor_dev(self, d_x, n, flip_tta, d_out):
+    def descriptor_dev(self, d_x, n, flip_tta, d_out, size=None):
+        if size is not None:
+            h, w = check_hw(size)
+            check(self.lib.reid_descriptor_f32_nchw_hw_dev(self.h, C.c_void_p(d_x), int(n), h, w, int(bool(flip_tta)), C.c_void_p(d_out)))
+            return
         check(self.lib.reid_descriptor_f32_nchw_dev(self.h, C.c_void_p(d_x), int(n), int(bool(flip_tta)), C.c_void_p(d_out)))
+
+    # ---- the kernels of libreid_hip_anysize.so on host operands (libreid_hip_debug.so; tests/test_gpu_anysize.py).  Each returns its
+    # outputs WITH the guard pixel the harness keeps behind them (c more floats, NaN unless a kernel wrote out of bounds).
+    def debug_any_norm(self, x, half, in_gamma, in_beta, bn_scale=None, bn_shift=None):
+        x = _f32(x)
+        n, hw, c = x.shape
+        out = np.empty(x.size + c, np.float32)
+        g, b = _f32(in_gamma), _f32(in_beta)
+        bs, bh = (None, None) if bn_scale is None else (_f32(bn_scale), _f32(bn_shift))
+        check(_ffi.debug_lib().reid_debug_any_norm(self.h, n, hw, c, int(half), _ptr(x), _ptr(g), _ptr(b), _ptr(bs), _ptr(bh), _ptr(out)))
+        return out
+
+    def debug_any_se_tail(self, y, shortcut, w1, w2t):
+        y, shortcut, w1, w2t = _f32(y), _f32(shortcut), _f32(w1), _f32(w2t)
+        n, hw, c = y.shape
+        out = np.empty(y.size + c, np.float32)
+        gate = np.empty(n * c + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_se_tail(self.h, n, hw, c, w1.shape[0], _ptr(w1), _ptr(w2t), _ptr(y), _ptr(shortcut), _ptr(out),
+                                                      _ptr(gate)))
+        return out, gate
+
+    def debug_any_gem(self, x, p, scale, shift):
+        x, scale, shift = _f32(x), _f32(scale), _f32(shift)
+        n, hw, c = x.shape
+        gem = np.empty(n * c + c, np.float32)
+        emb = np.empty(n * c + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_gem(self.h, n, hw, c, C.c_float(p), _ptr(x), _ptr(scale), _ptr(shift), _ptr(gem), _ptr(emb)))
+        return gem, emb
 
     def cam_debias_dev(self, d_x, cams, n, d, la=0.05, iters=0):
         cams = np.ascontiguousarray(cams, dtype=np.int32).reshape(-1)

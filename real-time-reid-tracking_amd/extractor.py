@@ -38,7 +38,10 @@ class Extractor(object):
         """``Extractor(model_path, use_cuda=True)`` as feature_extractor.py:15-29.  ``precision`` (keyword, not in the reference):
         "f16x3" (default; $REID_PRECISION overrides the default) / "f32" / "f16" - see precision.py; a checkpoint the fp32-class
         arithmetic cannot represent runs in exact fp32, with one log line.  ``size`` (keyword, (W, H) like ``self.size``): the size
-        crops are resized to - a Swin checkpoint takes multiples of 224 (default (224, 224)), the ResNet family (128, 256) only."""
+        crops are resized to - a Swin checkpoint takes multiples of 224 (default (224, 224)); the ResNet family (128, 256), and a
+        seres18_ibn checkpoint any (W, H) with sides in 32 .. 512 (DeepSORT's own (64, 128), feature_extractor.py:23) when exact fp32
+        is asked for: that forward has no other arithmetic, so ``precision="f32"`` must be given - nothing is demoted behind the
+        caller's back - and the object's log line names size and arithmetic."""
         if not use_cuda:
             raise RuntimeError("Extractor: the MI355X engine has no CPU path (use_cuda=False is not supported)")
         self.device = "cuda"
@@ -52,21 +55,30 @@ class Extractor(object):
             import torch
             state_dict = torch.load(model_path, map_location="cpu")   # {"state_dict": ...} / "module." prefixes: weights.pack_seres18
         from .engine import Engine, get_engine
-        self.net = get_engine(device)
         self._arch, blob, manifest, self.info = pack_checkpoint(state_dict)
         if self._arch == "swin":
             self.size = tuple(int(v) for v in (size or (224, 224)))           # (W, H)
             Engine._swin_crop_args(self.size[::-1], None)
-            self.net._swin_owner = None
         else:
             self.size = (128, 256)             # (W, H), feature_extractor.py:24
             if size is not None and tuple(size) != self.size:
-                raise ValueError("Extractor: the ResNet18-IBN family runs at size (W, H) = (128, 256) only, got %r" % (size,))
-            self.net._owner = None
+                from .engine import check_hw
+                h, w = check_hw(tuple(size)[::-1])
+                if self.info.get("arch") != "seres18_ibn" or self._mode != _precision.EXACT:
+                    raise ValueError("Extractor: at a size other than (W, H) = (128, 256) the ResNet18-IBN family runs seres18_ibn "
+                                     "checkpoints in exact fp32 only (precision=\"f32\"); got size %r, %s, precision %s"
+                                     % (size, self.info.get("arch"), _precision.LABEL[self._mode]))
+                self.size = (w, h)
+        self.net = get_engine(device)          # a bad size was refused above, before any device call
+        setattr(self.net, "_swin_owner" if self._arch == "swin" else "_owner", None)
         self._packed = (blob, manifest)
         _precision.run(self, self.net, "Extractor", lambda eng: None)      # load now; a checkpoint mode 2 refuses falls back here
         logger = logging.getLogger("root.tracker")
-        logger.info("Loading weights from {}... Done!".format(model_path if not isinstance(model_path, dict) else "<state_dict>"))
+        where = model_path if not isinstance(model_path, dict) else "<state_dict>"
+        if self._arch != "swin" and self.size != (128, 256):
+            logger.info("Loading weights from {}... Done! (size (W, H) = {}: exact fp32)".format(where, self.size))
+        else:
+            logger.info("Loading weights from {}... Done!".format(where))
 
     @property
     def precision(self):
@@ -105,10 +117,15 @@ class Extractor(object):
             if self._arch == "swin":
                 stacked = np.ascontiguousarray(im_crops)
                 return self._run(lambda eng: eng.swin_embed_ragged_u8(list(stacked), size=size_hw))
+            if size_hw != (256, 128):
+                stacked = np.ascontiguousarray(im_crops)
+                return self._run(lambda eng: eng.embed_ragged_u8(list(stacked), size=size_hw))
             return self._run(lambda eng: eng.embed_u8(im_crops))
         crops = self._preprocess(im_crops)
         if self._arch == "swin":
             return self._run(lambda eng: eng.swin_embed_ragged_u8(crops, size=size_hw))
+        if size_hw != (256, 128):
+            return self._run(lambda eng: eng.embed_ragged_u8(crops, size=size_hw))
         return self._run(lambda eng: eng.embed_ragged_u8(crops))
 
     def from_frame(self, bbox_xywh, ori_img):
@@ -126,4 +143,7 @@ class Extractor(object):
             xyxy[i] = (max(int(x - w / 2), 0), max(int(y - h / 2), 0), min(int(x + w / 2), width - 1), min(int(y + h / 2), height - 1))
         if self._arch == "swin":
             return self._run(lambda eng: eng.swin_embed_frame_u8(ori_img, xyxy, size=(self.size[1], self.size[0])))
+        if self.size != (128, 256):      # the frame entry is 256 x 128; the same windows, cut on the host, through the ragged entry
+            crops = [ori_img[y1:y2, x1:x2] for x1, y1, x2, y2 in xyxy]
+            return self._run(lambda eng: eng.embed_ragged_u8(crops, size=(self.size[1], self.size[0])))
         return self._run(lambda eng: eng.embed_frame_u8(ori_img, xyxy))

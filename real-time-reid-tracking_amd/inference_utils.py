@@ -4,12 +4,12 @@
 * ``smooth_tracklets(embeddings, seqs, indices_valid)``   reid/inference_utils.py:18-27
 * ``extract_descriptors(model_or_engine, images, flip=True)``: what ``inference_efficient`` + the averaging at
   reid/image_reid_inference.py:112-123,252-253 produce for one set of images - ``normalize((d(x) + d(hflip x)) / 2)`` with
-  ``d = cat(normalize(emb), normalize(logits))``.  ``images`` is float32 [N,3,256,128] after the caller's transform
+  ``d = cat(normalize(emb), normalize(logits))``.  ``images`` is float32 [N,3,H,W] after the caller's transform
   (the script uses ImageNet mean/std, data_transforms.py:56-130).
 """
 import numpy as np
 
-from .engine import get_engine
+from .engine import check_hw, get_engine
 
 
 def _np(a):
@@ -39,9 +39,15 @@ def smooth_tracklets(embeddings, seqs, indices_valid, device=0):
     return out
 
 
-def extract_descriptors(images, flip=True, device=0):
-    """float [n,3,256,128] after the caller's transform, or a list of uint8 [h,w,3] images of any sizes, which the device resizes as PIL
-    does and normalises with the ImageNet values (Engine.descriptor_images_u8)."""
+def extract_descriptors(images, flip=True, device=0, size=None):
+    """float [n,3,H,W] after the caller's transform ((256, 128), or sides in 32 .. 512 for seres18_ibn weights in exact fp32), or a list
+    of uint8 [h,w,3] images of any sizes, which the device resizes as PIL does - to ``size`` = (H, W), default (256, 128); the script's
+    VeRi geometry is (224, int(ratio * 224)) - and normalises with the ImageNet values (Engine.descriptor_images_u8)."""
+    if size is not None:
+        size = check_hw(size)
     if isinstance(images, (list, tuple)) and len(images) and all(getattr(im, "dtype", None) == np.uint8 for im in images):
-        return get_engine(device).descriptor_images_u8(images, flip_tta=flip)
-    return get_engine(device).descriptor_f32_nchw(_np(images), flip)
+        return get_engine(device).descriptor_images_u8(images, flip_tta=flip, size=size)
+    images = _np(images)
+    if size is not None and tuple(images.shape[2:]) != size:
+        raise ValueError("size %r is the resize target of uint8 images; these float images are %s" % (size, tuple(images.shape[2:])))
+    return get_engine(device).descriptor_f32_nchw(images, flip)

@@ -30,7 +30,7 @@ The Market-1501 attribute distance (:278-283, needs the dataset's .mat file) is 
 """
 import numpy as np
 
-from .engine import IMG_H, IMG_W, get_engine
+from .engine import IMG_H, IMG_W, check_hw, get_engine
 from .parallel import DevArray
 
 
@@ -40,7 +40,11 @@ def dbscan_pseudo_labels(dists, eps=0.5, min_samples=5):
     return DBSCAN(eps=eps, min_samples=min_samples, metric="precomputed", n_jobs=-1).fit_predict(dists)
 
 
-ARCHS = ("seres18", "swin")
+ARCHS = ("seres18", "swin", "seres18_hw")
+# "seres18_hw": the ResNet path at the images' own size - the script's --dataset veri runs the ResNet family at
+# Resize((224, int(ratio * 224))), ratio the mean width / height of the dataset (data_transforms.py:121, image_reid_inference.py:169-180).
+# Float images carry the size, uint8 images are resized to ``size`` (required); seres18_ibn weights, exact fp32 (reid_*_hw).  The default
+# "seres18" stays fixed at 256 x 128, every architecture of the family and every precision mode.
 
 
 def _descriptor_width(engine, arch):
@@ -61,6 +65,10 @@ def _check_images(images, arch):
         if images.ndim != 4 or images.shape[1] != 3 or images.shape[2] <= 0 or images.shape[3] <= 0 or images.shape[2] % 224 or \
                 images.shape[3] % 224:
             raise ValueError("images must be float32 [n,3,h,w] with h, w multiples of 224, got %s" % (images.shape,))
+    elif arch == "seres18_hw":
+        if images.ndim != 4 or images.shape[1] != 3:
+            raise ValueError("images must be float32 [n,3,h,w], got %s" % (images.shape,))
+        check_hw(images.shape[2:])
     elif images.ndim != 4 or images.shape[1:] != (3, IMG_H, IMG_W):
         raise ValueError("images must be float32 [n,3,%d,%d], got %s" % (IMG_H, IMG_W, images.shape))
     return images
@@ -81,6 +89,10 @@ def _check_u8_images(images, arch, size):
     from .engine import Engine
     if arch == "swin":
         h, w, _ = Engine._swin_crop_args((448, 224) if size is None else size, None)
+    elif arch == "seres18_hw":
+        if size is None:
+            raise ValueError("arch='seres18_hw' resizes uint8 images to size=(H, W), which must be given")
+        h, w = check_hw(size)
     else:
         if size is not None and tuple(int(v) for v in size) != (IMG_H, IMG_W):
             raise ValueError("arch=%r resizes to (%d, %d) only, got size %r" % (arch, IMG_H, IMG_W, size))
@@ -106,6 +118,8 @@ def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width
             if view_index is not None:
                 engine.set_side_index(view_index[i:i + bs])
             rows = engine.swin_descriptor_images_u8(part, size=size, flip_tta=flip)
+        elif arch == "seres18_hw":
+            rows = engine.descriptor_images_u8(part, flip_tta=flip, size=size)
         else:
             rows = engine.descriptor_images_u8(part, flip_tta=flip)
         engine.h2d(d_out + i * width * 4, rows)
@@ -124,7 +138,11 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     ``images`` may instead be a sequence of uint8 [h,w,3] arrays of any sizes (or one uint8 [n,h,w,3] array): the script's transform -
     PIL's antialiased Resize, ToTensor, Normalize with the ImageNet values - then runs on the device (``reid_descriptor_images_u8``,
     to 256x128; ``reid_swin_descriptor_images_u8`` to ``size`` = (H, W), default (448, 224)), with rows bit-identical to the float path
-    on the same images preprocessed with PIL on the host.  ``size`` is for uint8 images only."""
+    on the same images preprocessed with PIL on the host.  ``size`` is for uint8 images only.
+
+    ``arch="seres18_hw"``: the ResNet path at another input size - float32 [n,3,h,w] with sides in 32 .. 512, or uint8 images resized to
+    ``size`` = (H, W) (required), e.g. the script's VeRi geometry ``size=(224, int(ratio * 224))``; seres18_ibn weights with the context in
+    exact fp32 (``reid_descriptor_f32_nchw_hw_dev`` / ``reid_descriptor_images_u8_hw``)."""
     width = _descriptor_width(engine, arch)
     u8 = is_u8_images(images)
     if u8:
@@ -155,6 +173,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
                 if view_index is not None:
                     engine.set_side_index(view_index[i:i + bs])
                 engine.swin_descriptor_dev(stage.ptr, part.shape[0], part.shape[2], part.shape[3], flip, d_out + i * width * 4)
+            elif arch == "seres18_hw":
+                engine.descriptor_dev(stage.ptr, part.shape[0], flip, d_out + i * width * 4, size=part.shape[2:])
             else:
                 engine.descriptor_dev(stage.ptr, part.shape[0], flip, d_out + i * width * 4)
         engine.sync()
@@ -173,7 +193,8 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     ``arch="swin"``: the chain on the loaded Swin weights (``Engine.load_swin``), images float32 [n,3,h,w] with h, w multiples of 224;
     ``use_side`` (the script's --sie, ``arch="swin"`` only) passes each image's camera as the view index of both its views.
     Gallery and query images may each be a sequence of uint8 [h,w,3] arrays of any sizes instead (see ``inference_efficient``); ``size``
-    = (H, W) is what a Swin resizes them to (default (448, 224); the ResNet family is fixed at 256x128)."""
+    = (H, W) is what a Swin resizes them to (default (448, 224); the ResNet family is fixed at 256x128 unless ``arch="seres18_hw"``, which
+    runs seres18_ibn weights in exact fp32 at the float images' own size or at ``size``: VeRi is ``size=(224, int(ratio * 224))``)."""
     if arch not in ARCHS:
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
     if use_side and arch != "swin":
