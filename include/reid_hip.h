@@ -291,7 +291,20 @@ int reid_swin_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const i
  * reid_descriptor_images_u8_hw: Pillow's Resize((out_h, out_w)) as reid_descriptor_images_u8, bit-identical to
  * reid_descriptor_f32_nchw_hw on the same images preprocessed on the host; the mirrored view is read with reversed columns by the
  * layout kernel in front of the stem, no flipped copy of the batch is made.
- * Refused before anything is queued: a side outside 32 .. 512 (REID_ERR_ARG). */
+ * Refused before anything is queued: a side outside 32 .. 512 (REID_ERR_ARG).
+ *
+ * reid_ctx_set_hw_precision(ctx, v): the arithmetic of that second forward, a setting of its own because the forward has kernels of its own.
+ *   -1 (default)  the rule above: another size needs the context in mode 0.
+ *    0            other sizes run exact fp32 whatever the context's mode.
+ *    2            other sizes run fp32-class (the arithmetic of mode 2: hi/lo-split f16 operands on the matrix pipe, one fp32 accumulator,
+ *                 fp32 storage) whatever the context's mode: the 3x3 and 1x1 convolutions of the trunk on any_conv_x3_kernel from
+ *                 libreid_hip_anysize_x3.so, which must lie beside this library (REID_ERR_STATE naming it otherwise, on the first call at
+ *                 another size); the 7x7 stem, the classifier, the max-pool and the tails stay exact fp32.  The activations are split in the
+ *                 kernel's loader and a value outside f16's range raises REID_FAULT bit 0 as in mode 2.  A loaded ResNet checkpoint outside
+ *                 the split range (|w| 2^11 >= 65504) makes the call fail with REID_ERR_ARG naming the tensor, as reid_ctx_set_precision(2)
+ *                 does, and so does loading one while v == 2.
+ *   Any other value is REID_ERR_ARG.  (256, 128) is not affected by v, and cares18_ibn / emares18_ibn stay refused at other sizes. */
+int reid_ctx_set_hw_precision(reid_ctx* ctx, int v);
 int reid_embed_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits);
 int reid_embed_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits);
 int reid_embed_ragged_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,

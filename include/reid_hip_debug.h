@@ -111,6 +111,17 @@ int reid_debug_any_se_tail(reid_ctx* ctx, int n, int hw, int c, int mid, const f
                            const float* shortcut, float* out, float* gate);
 int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, const float* x, const float* scale, const float* shift, float* gem_out,
                        float* emb);
+/* One trunk convolution of the any-size forward (tests/test_gpu_anysize_x3.py) through the launcher the forward calls, on host operands:
+ * x [n][h][w][cin], wgt [cout][r][r][cin], out [n ho wo cout + cout] with ONE guard row (cout floats) behind the last pixel, preset to 0xff
+ * bytes with the rest.  r = 3 with pad 1 or r = 1 with pad 0, stride 1 or 2, cin % 32 == 0, cout % 64 == 0.  out = acc * scale + shift (both
+ * or neither NULL), + residual [n ho wo cout] (may be NULL), ReLU from column relu_from on when relu != 0.
+ *   hw_precision 2   any_conv_x3_kernel of libreid_hip_anysize_x3.so (fp32-class: activations split in the loader, the cached split of wgt
+ *                    dropped first); form_out (may be NULL) = the tile form launched, 1 = 128 x 64, 2 = 128 x 128.
+ *   hw_precision 0   the exact-fp32 GEMM the forward uses at reid_ctx_set_hw_precision 0 / -1, for A/B; form_out = 0.
+ * Returns the context's fault status (REID_ERR_STATE when the loader met a value outside f16's range). */
+int reid_debug_any_conv(reid_ctx* ctx, int hw_precision, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int r,
+                        int stride, int pad, const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out,
+                        int* form_out);
 /* gem_neck of the last block's tail in one launch (launch_gem_neck_tail; tests/test_gpu_tail_stream.py): GeM + BNNeck of
  * relu(gate y + shortcut) with se_tail's gate, fp32 operands as in se_tail; equals se_tail form 4 followed by gem_neck bit for bit. */
 int reid_debug_gem_neck_fused(reid_ctx* ctx, int n, int hw, int c, int mid, int tiles, float p, const float* stats, const float* w1,

@@ -87,10 +87,13 @@ class SERes18IBN:
     arch = "seres18_ibn"
 
     def __init__(self, num_classes=751, loss="triplet", pretrained=False, use_gpu=True, seed=0, num_cams=6, cam_factor=-1.0,
-                 precision=None, **_):
+                 precision=None, hw_precision=None, **_):
         if loss not in ("triplet", "softmax"):
             raise NotImplementedError                      # seres18_ibn(), SERes18_IBN.py:279-285
         self._mode = _precision.resolve(precision)         # "f16x3" unless the argument or $REID_PRECISION says otherwise (precision.py)
+        # inputs of another size (seres18_ibn only): None = exact fp32 for that call, "f16x3" = the fp32-class arithmetic for that call
+        hw = Engine.hw_precision_value(hw_precision)
+        self._hw_call = _HwClassCall(self) if hw == 2 else None
         self.num_classes = num_classes
         self.num_cams, self.cam_factor = num_cams, float(cam_factor)   # SERes18_IBN.py:193,198: cam_bias [num_cams,512] and its factor
         self.is_reid = loss == "softmax"
@@ -200,8 +203,12 @@ class SERes18IBN:
         any_size = size != (IMG_H, IMG_W)
         if any_size and self.arch != "seres18_ibn":
             raise ValueError("%s runs at [N,3,%d,%d] only (other sizes: seres18_ibn), got %s" % (self.arch, IMG_H, IMG_W, tuple(x.shape)))
-        # another size runs the any-size forward, which is exact fp32: this CALL runs in mode 0, the model keeps its own mode
-        run = (lambda fn: _precision.run(_ExactCall(self), get_engine(self._device), self.arch, fn)) if any_size else self._run
+        # another size runs the any-size forward: this CALL runs in exact fp32 (mode 0) or, with hw_precision="f16x3", in the fp32-class
+        # arithmetic (reid_ctx_set_hw_precision 2 around the call); the model keeps its own mode and the engine gets its settings back
+        if any_size and self._hw_call is not None:
+            run = self._hw_call.run
+        else:
+            run = (lambda fn: _precision.run(_ExactCall(self), get_engine(self._device), self.arch, fn)) if any_size else self._run
         if is_torch and x.is_cuda:
             if x.device.index != self._device:
                 self.to(x.device.index)
@@ -250,6 +257,25 @@ class _ExactCall(object):
 
     def _do_bind(self, eng):
         self._owner._do_bind(eng)
+
+
+class _HwClassCall(_ExactCall):
+    """precision.run owner for the calls of a model at another input size in the fp32-class arithmetic (hw_precision="f16x3"): the context
+    in mode 2 and reid_ctx_set_hw_precision 2 around the call, both restored after it.  A checkpoint outside the split range (refused at
+    the switch, or through the fault word while running) makes THIS owner exact fp32 for the rest of the model's life, with the one log
+    line of precision.fallback_to_exact - the model's own mode at 256 x 128 is not touched."""
+
+    def __init__(self, owner):
+        _ExactCall.__init__(self, owner)
+        self._mode = _precision.F32_CLASS
+
+    def run(self, fn):
+        eng = get_engine(self._owner._device)
+
+        def scoped(e):
+            with e.hw_precision_scope(2 if self._mode == _precision.F32_CLASS else None):
+                return fn(e)
+        return _precision.run(self, eng, self._owner.arch, scoped)
 
 
 def seres18_ibn(num_classes=751, loss="triplet", pretrained=False, use_gpu=True, **kwargs):

@@ -3,6 +3,7 @@
 #include "reid_internal.h"
 #include "siblings_f16.h"
 #include "anysize.h"
+#include "anysize_x3.h"
 #include <cmath>
 #include <dlfcn.h>
 #include <mutex>
@@ -185,6 +186,23 @@ extern "C" int reid_ctx_set_precision(reid_ctx* ctx, int mode) {
         }
     }
     ctx->precision = mode;
+    return REID_OK;
+}
+
+extern "C" int reid_ctx_set_hw_precision(reid_ctx* ctx, int v) {
+    ARG_CHECK(ctx);
+    CTX_GUARD(ctx);
+    if (v != -1 && v != 0 && v != 2) {
+        reid_set_error("reid_ctx_set_hw_precision: the value must be -1 (other input sizes need the context in mode 0), 0 (they run exact "
+                       "fp32 whatever the mode) or 2 (they run fp32-class whatever the mode)");
+        return REID_ERR_ARG;
+    }
+    if (v == 2 && !ctx->split_bad_se18.empty()) {   // the guard of reid_ctx_set_precision(ctx, 2): the same split form of the same weights
+        reid_set_error("reid_ctx_set_hw_precision(2): weight tensor %s of the loaded checkpoint is outside the range the fp32-class "
+                       "arithmetic can split (|w| 2^11 < 65504); use 0", ctx->split_bad_se18.c_str());
+        return REID_ERR_ARG;
+    }
+    ctx->hw_precision = v;
     return REID_OK;
 }
 
@@ -467,6 +485,11 @@ extern "C" int reid_seres18_load(reid_ctx* ctx, const float* blob, size_t n_floa
     if (!bad.empty() && ctx->precision == 2) {
         reid_set_error("reid_seres18_load: weight tensor %s cannot be split for the fp32-class arithmetic selected on this context "
                        "(reid_ctx_set_precision 2 needs |w| 2^11 < 65504); load it in mode 0", bad.c_str());
+        return REID_ERR_ARG;
+    }
+    if (!bad.empty() && ctx->hw_precision == 2) {
+        reid_set_error("reid_seres18_load: weight tensor %s cannot be split for the fp32-class arithmetic selected for other input sizes "
+                       "on this context (reid_ctx_set_hw_precision 2 needs |w| 2^11 < 65504); load it at 0 or -1", bad.c_str());
         return REID_ERR_ARG;
     }
     ctx->split_bad_se18 = bad;
@@ -1482,6 +1505,24 @@ static int anysize_api(const AnysizeApi** out) {
     return REID_OK;
 }
 
+// ... and the trunk convolutions of that forward in the fp32-class arithmetic (reid_ctx_set_hw_precision 2): anysize_x3.h
+struct AnysizeX3Api {
+    decltype(&anysize_x3_conv) conv = nullptr;
+};
+static int anysize_x3_api(const AnysizeX3Api** out) {
+    static std::mutex m;
+    static AnysizeX3Api api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.conv) {
+        void* f[1];
+        REID_TRY(open_beside_self("libreid_hip_anysize_x3.so", "ResNet18-IBN-SE at another input size in the fp32-class arithmetic needs",
+                                  {"anysize_x3_conv"}, f));
+        api.conv = (decltype(api.conv))f[0];
+    }
+    *out = &api;
+    return REID_OK;
+}
+
 bool se_any_routes(const reid_ctx* ctx, int h, int w) { return h != IMG_H || w != IMG_W || ctx->anysize_force != 0; }
 
 int se_any_pass(const reid_ctx* ctx, int h, int w) {
@@ -1500,14 +1541,19 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
         reid_set_error("%s: call reid_seres18_load first", who);
         return REID_ERR_STATE;
     }
-    if (wt.arch != 0 || ctx->precision != 0) {
+    if (wt.arch != 0 || (ctx->hw_precision < 0 && ctx->precision != 0)) {   // reid_ctx_set_hw_precision 0 / 2 names the arithmetic itself
         static const char* const kArch[3] = {"seres18_ibn", "cares18_ibn", "emares18_ibn"};
         reid_set_error("%s: input size %d x %d runs seres18_ibn in precision mode 0 (exact fp32) only; loaded architecture %s, precision "
                        "mode %d (256 x 128 runs every architecture and mode)", who, h, w, kArch[wt.arch], ctx->precision);
         return REID_ERR_ARG;
     }
     const AnysizeApi* api;
-    return anysize_api(&api);
+    REID_TRY(anysize_api(&api));
+    if (ctx->hw_precision == 2) {
+        const AnysizeX3Api* x3;
+        REID_TRY(anysize_x3_api(&x3));
+    }
+    return REID_OK;
 }
 
 static int any_launched(hipError_t e, const char* what) {
@@ -1569,10 +1615,36 @@ static int any_conv(reid_ctx* ctx, int amode, const float* x, int n, int H, int 
                            ((double)n * H * W * Cin + (double)p.M * Cout * (residual ? 2.0 : 1.0) + (double)Cout * ktrue) * 4.0);
 }
 
+// ... and in the arithmetic the forward runs in: exact fp32 as above, or fp32-class (any_conv_x3_kernel, anysize_x3.h) on the split form of the
+// weights the 256 x 128 forward of mode 2 caches too ([wh 2^11 | wh | wl'] per tap, ctx->split_w: made once per weight buffer, dropped by
+// reid_seres18_load, freed with the context)
+int launch_any_conv(reid_ctx* ctx, int arith, const float* x, int n, int H, int W, int Cin, const float* wgt, int Cout, int R, int stride, int pad,
+                    const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out) {
+    if (arith == 0) return any_conv(ctx, A_IM2COL, x, n, H, W, Cin, wgt, Cout, R, stride, pad, scale, shift, residual, relu, relu_from, out);
+    ARG_CHECK(arith == 2);
+    const AnysizeX3Api* api;
+    REID_TRY(anysize_x3_api(&api));
+    const _Float16* w16;
+    REID_TRY(split_weights_of(ctx, wgt, Cout, R * R, Cin, &w16));
+    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - R) / stride + 1;
+    const double m = (double)n * Ho * Wo, ktrue = (double)R * R * Cin;
+    prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * Cout * ktrue,
+               ((double)n * H * W * Cin + m * Cout * (residual ? 2.0 : 1.0)) * 4.0 + (double)Cout * ktrue * 6.0);
+    const hipError_t e = api->conv(ctx->stream, x, n, H, W, Cin, w16, ctx->split_terms, Cout, R, stride, pad, scale, shift, residual, relu,
+                                   relu_from, out, ctx->fault, &ctx->any_conv_form);
+    prof_end(ctx);
+    if (e != hipSuccess) {
+        reid_set_error("libreid_hip_anysize_x3.so anysize_x3_conv -> %s", hipGetErrorString(e));
+        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+    }
+    return REID_OK;
+}
+
 // x: fp32 NHWC [n][h][w][3] on the device
 static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
     Se18Weights& wt = ctx->se18;
     const bool keep = ctx->debug_keep != 0;
+    const int arith = ctx->hw_precision == 2 ? 2 : 0;   // the setting and nothing else picks the trunk's convolution launcher
     const int H1 = (h + 6 - 7) / 2 + 1, W1 = (w + 6 - 7) / 2 + 1;        // conv 7x7 s2 p3
     const int H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;      // MaxPool2d(3, 2, 1)
     ARG_CHECK((long long)n * H1 * W1 < (1ll << 31));                     // the GEMM's row index is an int (element offsets are 64-bit)
@@ -1616,18 +1688,18 @@ static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int 
         float *c1 = free_[0], *y = free_[1], *sc = free_[2];
         const int Ho = (H + 2 - 3) / k.stride + 1, Wo = (W + 2 - 3) / k.stride + 1, hw = Ho * Wo;
         if (k.ibn) {   // BatchNorm half + ReLU in conv1's epilogue, InstanceNorm half (statistics of the whole image) by one pass in place
-            REID_TRY(any_conv(ctx, A_IM2COL, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, wt.ep + (size_t)i * 1024,
+            REID_TRY(launch_any_conv(ctx, arith, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, wt.ep + (size_t)i * 1024,
                               wt.ep + (size_t)i * 1024 + 512, nullptr, 1, k.c / 2, c1));
             REID_TRY(launch_any_norm(ctx, c1, n, hw, k.c, k.c / 2, k.in_gamma, k.in_beta, nullptr, nullptr));
         } else {
-            REID_TRY(any_conv(ctx, A_IM2COL, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, k.bn1_scale, k.bn1_shift, nullptr, 1, 0, c1));
+            REID_TRY(launch_any_conv(ctx, arith, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, k.bn1_scale, k.bn1_shift, nullptr, 1, 0, c1));
         }
         // a block without a downsample is the whole BasicBlock_IBN: residual + ReLU before the SE scale, the input added again after
-        REID_TRY(any_conv(ctx, A_IM2COL, c1, n, Ho, Wo, k.c, k.conv2_w, k.c, 3, 1, 1, k.bn2_scale, k.bn2_shift, k.ds ? nullptr : cur,
+        REID_TRY(launch_any_conv(ctx, arith, c1, n, Ho, Wo, k.c, k.conv2_w, k.c, 3, 1, 1, k.bn2_scale, k.bn2_shift, k.ds ? nullptr : cur,
                           k.ds ? 0 : 1, 0, y));
         const float* shortcut = cur;
         if (k.ds) {
-            REID_TRY(any_conv(ctx, A_IM2COL, cur, n, H, W, k.cin, k.ds_w, k.c, 1, k.stride, 0, k.ds_scale, k.ds_shift, nullptr, 0, 0, sc));
+            REID_TRY(launch_any_conv(ctx, arith, cur, n, H, W, k.cin, k.ds_w, k.c, 1, k.stride, 0, k.ds_scale, k.ds_shift, nullptr, 0, 0, sc));
             shortcut = sc;
         }
         float* out = c1;   // conv1's output is dead after conv2

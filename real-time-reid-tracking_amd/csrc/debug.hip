@@ -734,6 +734,41 @@ extern "C" int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, 
     return ctx_fault_status(ctx);
 }
 
+// One trunk convolution of the any-size forward through launch_any_conv, the function the forward calls: hw_precision 2 =
+// any_conv_x3_kernel (libreid_hip_anysize_x3.so), 0 = the exact-fp32 GEMM.  The weights land in a reused workspace, so the split form cached
+// under that address goes first.  form_out: the tile form an fp32-class launch took (anysize_x3.h), 0 for exact fp32.
+extern "C" int reid_debug_any_conv(reid_ctx* ctx, int hw_precision, const float* x, int n, int h, int w, int cin, const float* wgt, int cout,
+                                   int r, int stride, int pad, const float* scale, const float* shift, const float* residual, int relu,
+                                   int relu_from, float* out, int* form_out) {
+    ARG_CHECK(ctx && (hw_precision == 0 || hw_precision == 2) && x && wgt && out && n >= 1 && h >= 1 && w >= 1 && cin >= 32 && cin % 32 == 0 &&
+              cout >= 64 && cout % 64 == 0 && ((r == 3 && pad == 1) || (r == 1 && pad == 0)) && (stride == 1 || stride == 2) &&
+              (scale == nullptr) == (shift == nullptr) && relu_from >= 0 && relu_from <= cout);
+    CTX_ENTER(ctx);
+    const int ho = (h + 2 * pad - r) / stride + 1, wo = (w + 2 * pad - r) / stride + 1;
+    const size_t nx = (size_t)n * h * w * cin, nw = (size_t)cout * r * r * cin, ny = (size_t)n * ho * wo * cout;
+    if (hw_precision == 2)
+        for (size_t i = 0; i < nw; ++i)
+            if (!(fabsf(wgt[i]) * 2048.0f < 65504.0f)) {
+                reid_set_error("reid_debug_any_conv: weight %zu (%g) is outside the range the fp32-class arithmetic can split (|w| 2^11 < 65504)",
+                               i, (double)wgt[i]);
+                return REID_ERR_ARG;
+            }
+    float *dx, *dw, *ds, *dh, *dr, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgc.x", x, nx, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgc.w", wgt, nw, &dw));
+    REID_TRY(conv_weights_fresh(ctx, dw));
+    REID_TRY(dbg_upload(ctx, "dbgc.scale", scale, (size_t)cout, &ds));
+    REID_TRY(dbg_upload(ctx, "dbgc.shift", shift, (size_t)cout, &dh));
+    REID_TRY(dbg_upload(ctx, "dbgc.res", residual, ny, &dr));
+    REID_TRY(dbg_output(ctx, "dbgc.out", ny + cout, &dout));
+    ctx->any_conv_form = 0;
+    REID_TRY(launch_any_conv(ctx, hw_precision, dx, n, h, w, cin, dw, cout, r, stride, pad, ds, dh, dr, relu, relu_from, dout));
+    if (form_out) *form_out = ctx->any_conv_form;
+    REID_TRY(dbg_download(ctx, out, dout, ny + cout));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 // GeM + BNNeck of the last block's tail in one launch (launch_gem_neck_tail): what reid_debug_se_tail form 4 followed by
 // reid_debug_gem_neck computes, without the tensor between them.
 extern "C" int reid_debug_gem_neck_fused(reid_ctx* ctx, int n, int hw, int c, int mid, int tiles, float p, const float* stats, const float* w1,

@@ -491,6 +491,9 @@ struct reid_ctx {
     float* stage_ptr[11] = {nullptr};
     size_t stage_elems[11] = {0};   // floats per image of each stage tap of the last pass, when that pass ran the any-size forward (else 0)
     int anysize_force = 0;   // libreid_hip_debug.so switch: 256 x 128 through the any-size forward too (reid_*_hw entries; A/B and tests)
+    int hw_precision = -1;   // reid_ctx_set_hw_precision: the arithmetic of the any-size forward: -1 = it needs the context in mode 0 (default),
+                             // 0 = exact fp32 whatever the mode, 2 = fp32-class whatever the mode (libreid_hip_anysize_x3.so)
+    int any_conv_form = 0;   // the tile form the last fp32-class any-size convolution launched (anysize_x3.h), written on the host only
     unsigned long long* conv_diag = nullptr;   // experiments (debug.hip): stamps of the loader-wave conv kernel
     // Which launch the last f16 convolution launcher made, written on the host only (harnesses read it, include/reid_hip_debug.h:
     // reid_debug_conv_layer_f16).  launch_gemm_f16: the tile configuration BN*1000 + BK*10 + NST; launch_conv3x3_f16: BN*10 + split K;
@@ -751,7 +754,8 @@ int open_beside_self(const char* file, const char* what, std::initializer_list<c
 // ---- ResNet18-IBN-SE at input sizes other than 256 x 128 (api.hip; kernels: anysize.h).  The reid_*_hw entries hand 256 x 128 to the
 // existing entries unless the debug switch anysize_force is set (se_any_routes).  se_any_ready: everything such a call would refuse, with
 // nothing queued - a side outside 32 .. 512 (REID_ERR_ARG), weights not loaded (REID_ERR_STATE), an architecture other than seres18_ibn or
-// a precision mode other than 0 (REID_ERR_ARG naming both), libreid_hip_anysize.so (REID_ERR_STATE).  se_any_pass: images per pass, the
+// a precision mode other than 0 while reid_ctx_set_hw_precision is -1 (REID_ERR_ARG naming both), libreid_hip_anysize.so and, at
+// hw_precision 2, libreid_hip_anysize_x3.so (REID_ERR_STATE).  se_any_pass: images per pass, the
 // context's chunk scaled by 256 * 128 / (h * w) and clamped to 1 .. 4096.  se_any_run_nchw: one pass from fp32 NCHW [m][3][h][w] on the
 // device (mirror: the horizontally flipped view); se_any_run_windows: from uploaded uint8 windows through the cv2-style resize.
 struct RaggedSrc;
@@ -766,6 +770,11 @@ int launch_any_se_tail(reid_ctx* ctx, const float* y, const float* sc, int n, in
                        float* out, float* gate_out);
 int launch_any_gem(reid_ctx* ctx, const float* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out,
                    float* emb);
+// one trunk convolution of the any-size forward (NHWC fp32 in / out, folded BN, identity residual, ReLU from column relu_from on) in the
+// arithmetic `arith`: 0 = launch_gemm_f32 (exact fp32), 2 = any_conv_x3_kernel of libreid_hip_anysize_x3.so (fp32-class; R = 3 pad 1 or
+// R = 1 pad 0) on the cached split form of wgt.  The forward and reid_debug_any_conv call this one function.
+int launch_any_conv(reid_ctx* ctx, int arith, const float* x, int n, int H, int W, int Cin, const float* wgt, int Cout, int R, int stride, int pad,
+                    const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out);
 void prof_begin(reid_ctx* ctx, int kind, double flops, double bytes);
 void prof_end(reid_ctx* ctx);
 

@@ -14,6 +14,7 @@ _ENGINES = {}
 
 IMG_H, IMG_W = 256, 128   # Extractor.size = (128, 256) as (W, H), feature_extractor.py:24
 SIZE_MIN, SIZE_MAX = 32, 512   # input sides of the any-size forward (reid_*_hw, include/reid_hip.h)
+HW_PRECISION_NAMES = {"f32": 0, "fp32": 0, "exact": 0, "f16x3": 2, "fp32-class": 2}   # Engine.set_hw_precision
 
 
 def check_hw(size):
@@ -160,6 +161,54 @@ class Engine:
     def precision(self):
         """The arithmetic mode this context is in (the library's default is 0)."""
         return getattr(self, "_precision", 0)
+
+    @staticmethod
+    def hw_precision_value(v):
+        """None / -1 -> -1, "f32" / 0 -> 0, "f16x3" / 2 -> 2 (the values of reid_ctx_set_hw_precision); ValueError otherwise, before any
+        device call - the fp16-storage mode and every other value have no any-size forward."""
+        if v is None:
+            return -1
+        if isinstance(v, str):
+            key = v.strip().lower()
+            if key in HW_PRECISION_NAMES:
+                return HW_PRECISION_NAMES[key]
+        elif not isinstance(v, bool) and isinstance(v, (int, np.integer)) and int(v) in (-1, 0, 2):
+            return int(v)
+        raise ValueError("hw_precision must be None / -1 (other input sizes need mode 0), \"f32\" / 0 or \"f16x3\" / 2, got %r" % (v,))
+
+    def set_hw_precision(self, v):
+        """The arithmetic of the any-size forward of seres18_ibn (reid_ctx_set_hw_precision): None / -1 = another size needs the context
+        in mode 0 (default), "f32" / 0 = other sizes run exact fp32 whatever the mode, "f16x3" / 2 = they run fp32-class whatever the mode
+        (libreid_hip_anysize_x3.so).  256 x 128 is not affected."""
+        v = Engine.hw_precision_value(v)
+        check(self.lib.reid_ctx_set_hw_precision(self.h, v))
+        self._hw_precision = v
+
+    @property
+    def hw_precision(self):
+        """-1, 0 or 2: what set_hw_precision set last (the library's default is -1)."""
+        return getattr(self, "_hw_precision", -1)
+
+    def hw_precision_scope(self, v):
+        """Context manager: ``v`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            if v is None:
+                yield self
+                return
+            prev = self.hw_precision
+            self.set_hw_precision(v)
+            try:
+                yield self
+            finally:
+                if self.hw_precision != prev:
+                    try:
+                        self.set_hw_precision(prev)
+                    except _ffi.ReidHipError:      # `prev` was 2 and the weights bound meanwhile cannot be split: stay
+                        pass
+        return scope()
 
     def set_side_index(self, index):
         """Camera (ResNet18-IBN-SE: SERes18_IBN.py:269-270) or view (Swin: swin_transformer.py:301-302) index of every image of
@@ -1165,6 +1214,25 @@ class Engine:
         emb = np.empty(n * c + c, np.float32)
         check(_ffi.debug_lib().reid_debug_any_gem(self.h, n, hw, c, C.c_float(p), _ptr(x), _ptr(scale), _ptr(shift), _ptr(gem), _ptr(emb)))
         return gem, emb
+
+    def debug_any_conv(self, x, wt, stride, hw_precision=2, scale=None, shift=None, res=None, relu=False, relu_from=0):
+        """One trunk convolution of the any-size forward (reid_debug_any_conv): x [n, h, w, cin], wt [cout, r, r, cin] with r = 3 (pad 1) or
+        1 (pad 0).  Returns (out [n, ho, wo, cout], guard [cout] - the row behind the last pixel, NaN unless the kernel wrote out of
+        bounds -, the tile form launched: 0 for exact fp32)."""
+        x, wt = _f32(x), _f32(wt)
+        n, h, w, cin = x.shape
+        cout, r = wt.shape[0], wt.shape[1]
+        pad = 1 if r == 3 else 0
+        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - r) // stride + 1
+        sc, sh = (None, None) if scale is None else (_f32(scale), _f32(shift))
+        rr = None if res is None else _f32(res)
+        if rr is not None and rr.size != n * ho * wo * cout:
+            raise ValueError("debug_any_conv: the residual must have the output's %d elements" % (n * ho * wo * cout))
+        out = np.empty(n * ho * wo * cout + cout, np.float32)
+        form = C.c_int(0)
+        check(_ffi.debug_lib().reid_debug_any_conv(self.h, int(hw_precision), _ptr(x), n, h, w, cin, _ptr(wt), cout, r, int(stride), pad, _ptr(sc),
+                                                   _ptr(sh), _ptr(rr), int(bool(relu)), int(relu_from), _ptr(out), C.byref(form)))
+        return out[:-cout].reshape(n, ho, wo, cout), out[-cout:], form.value
 
     def cam_debias_dev(self, d_x, cams, n, d, la=0.05, iters=0):
         cams = np.ascontiguousarray(cams, dtype=np.int32).reshape(-1)

@@ -39,9 +39,10 @@ class Extractor(object):
         "f16x3" (default; $REID_PRECISION overrides the default) / "f32" / "f16" - see precision.py; a checkpoint the fp32-class
         arithmetic cannot represent runs in exact fp32, with one log line.  ``size`` (keyword, (W, H) like ``self.size``): the size
         crops are resized to - a Swin checkpoint takes multiples of 224 (default (224, 224)); the ResNet family (128, 256), and a
-        seres18_ibn checkpoint any (W, H) with sides in 32 .. 512 (DeepSORT's own (64, 128), feature_extractor.py:23) when exact fp32
-        is asked for: that forward has no other arithmetic, so ``precision="f32"`` must be given - nothing is demoted behind the
-        caller's back - and the object's log line names size and arithmetic."""
+        seres18_ibn checkpoint any (W, H) with sides in 32 .. 512 (DeepSORT's own (64, 128), feature_extractor.py:23) when its
+        arithmetic is asked for by name: ``precision="f32"`` (exact fp32) or ``precision="f16x3"`` (fp32-class, the any-size forward's
+        reid_ctx_set_hw_precision 2 around every call) must be given - $REID_PRECISION is a default, not a name, and nothing is demoted
+        behind the caller's back - and the object's log line names size and arithmetic."""
         if not use_cuda:
             raise RuntimeError("Extractor: the MI355X engine has no CPU path (use_cuda=False is not supported)")
         self.device = "cuda"
@@ -64,10 +65,11 @@ class Extractor(object):
             if size is not None and tuple(size) != self.size:
                 from .engine import check_hw
                 h, w = check_hw(tuple(size)[::-1])
-                if self.info.get("arch") != "seres18_ibn" or self._mode != _precision.EXACT:
+                if self.info.get("arch") != "seres18_ibn" or precision is None or self._mode == _precision.F16:
                     raise ValueError("Extractor: at a size other than (W, H) = (128, 256) the ResNet18-IBN family runs seres18_ibn "
-                                     "checkpoints in exact fp32 only (precision=\"f32\"); got size %r, %s, precision %s"
-                                     % (size, self.info.get("arch"), _precision.LABEL[self._mode]))
+                                     "checkpoints in exact fp32 (precision=\"f32\") or fp32-class (precision=\"f16x3\"), asked for by "
+                                     "name; got size %r, %s, precision %s"
+                                     % (size, self.info.get("arch"), "None" if precision is None else _precision.LABEL[self._mode]))
                 self.size = (w, h)
         self.net = get_engine(device)          # a bad size was refused above, before any device call
         setattr(self.net, "_swin_owner" if self._arch == "swin" else "_owner", None)
@@ -76,7 +78,8 @@ class Extractor(object):
         logger = logging.getLogger("root.tracker")
         where = model_path if not isinstance(model_path, dict) else "<state_dict>"
         if self._arch != "swin" and self.size != (128, 256):
-            logger.info("Loading weights from {}... Done! (size (W, H) = {}: exact fp32)".format(where, self.size))
+            logger.info("Loading weights from {}... Done! (size (W, H) = {}: {})".format(
+                where, self.size, "fp32-class f16x3" if self._mode == _precision.F32_CLASS else "exact fp32"))
         else:
             logger.info("Loading weights from {}... Done!".format(where))
 
@@ -104,6 +107,13 @@ class Extractor(object):
             eng._owner = self
 
     def _run(self, fn):
+        if self._arch != "swin" and self.size != (128, 256):
+            # another size: the fp32-class arithmetic is the any-size forward's own setting, put on for the call and taken off after it; after
+            # a fall back (precision.run) the object is exact fp32 and the setting stays as the engine has it
+            def scoped(eng):
+                with eng.hw_precision_scope(2 if self._mode == _precision.F32_CLASS else None):
+                    return fn(eng)
+            return _precision.run(self, self.net, "Extractor", scoped)
         return _precision.run(self, self.net, "Extractor", fn)
 
     def __call__(self, im_crops):

@@ -39,12 +39,19 @@ def smooth_tracklets(embeddings, seqs, indices_valid, device=0):
     return out
 
 
-def extract_descriptors(images, flip=True, device=0, size=None):
+def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=None):
     """float [n,3,H,W] after the caller's transform ((256, 128), or sides in 32 .. 512 for seres18_ibn weights in exact fp32), or a list
     of uint8 [h,w,3] images of any sizes, which the device resizes as PIL does - to ``size`` = (H, W), default (256, 128); the script's
-    VeRi geometry is (224, int(ratio * 224)) - and normalises with the ImageNet values (Engine.descriptor_images_u8)."""
+    VeRi geometry is (224, int(ratio * 224)) - and normalises with the ImageNet values (Engine.descriptor_images_u8).
+    ``hw_precision``: the arithmetic of another size for this call (Engine.set_hw_precision: "f32" / "f16x3"), restored afterwards; None
+    leaves the engine's setting alone."""
     if size is not None:
         size = check_hw(size)
+    if hw_precision is not None:
+        from .engine import Engine
+        Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
+        with get_engine(device).hw_precision_scope(hw_precision):
+            return extract_descriptors(images, flip, device, size)
     if isinstance(images, (list, tuple)) and len(images) and all(getattr(im, "dtype", None) == np.uint8 for im in images):
         return get_engine(device).descriptor_images_u8(images, flip_tta=flip, size=size)
     images = _np(images)

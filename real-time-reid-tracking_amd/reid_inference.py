@@ -127,7 +127,7 @@ def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width
     return n
 
 
-def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None):
+def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None, hw_precision=None):
     """Descriptors of ``images`` (float32 [n,3,256,128], host) into the device rows ``d_out`` (pointer to [n, 512 + num_class]
     fp32): upload in batches of ``bs`` images, one ``reid_descriptor_f32_nchw_dev`` per batch.  Unlike the reference function
     (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253).
@@ -142,7 +142,14 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
 
     ``arch="seres18_hw"``: the ResNet path at another input size - float32 [n,3,h,w] with sides in 32 .. 512, or uint8 images resized to
     ``size`` = (H, W) (required), e.g. the script's VeRi geometry ``size=(224, int(ratio * 224))``; seres18_ibn weights with the context in
-    exact fp32 (``reid_descriptor_f32_nchw_hw_dev`` / ``reid_descriptor_images_u8_hw``)."""
+    exact fp32 (``reid_descriptor_f32_nchw_hw_dev`` / ``reid_descriptor_images_u8_hw``), or - ``hw_precision`` "f32" / "f16x3"
+    (``Engine.set_hw_precision``) - in the arithmetic named, whatever the context's mode: set for this call and restored after it; None
+    leaves the engine's setting alone."""
+    if hw_precision is not None:
+        from .engine import Engine
+        if arch != "seres18_hw":
+            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw'; arch=%r takes none" % (arch,))
+        Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
     width = _descriptor_width(engine, arch)
     u8 = is_u8_images(images)
     if u8:
@@ -162,6 +169,9 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
         if view_index.shape[0] != n or (n and (view_index.min() < 0 or view_index.max() >= 2 ** 31)):
             raise ValueError("view_index must hold one non-negative index per image (%d), got %d" % (n, view_index.shape[0]))
         view_index = view_index.astype(np.int32)
+    if hw_precision is not None:                     # every argument is checked: the setting goes on for the device work and off after it
+        with engine.hw_precision_scope(hw_precision):
+            return inference_efficient(engine, images, d_out, flip, bs, arch, view_index, size if u8 else None)
     if u8:
         return _inference_u8(engine, images, d_out, flip, int(bs), arch, view_index, size, width)
     stage = DevArray(engine, (min(bs, max(n, 1)),) + images.shape[1:], np.float32)
@@ -185,7 +195,7 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
 
 def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, query_images, query_labels, query_cams,
                   query_seqs, num_gallery_cams=None, eps=0.5, la=0.05, k1=20, k2=6, flip=True, cluster_fn=None, taps=None,
-                  verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None):
+                  verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None, hw_precision=None):
     """(CMC float32 [ng], mAP float) of the script's chain for one gallery / query pair; weights must be loaded on the engine
     (``Engine.load_seres18`` / ``build_model``).  ``taps`` (a dict) receives host copies of the intermediates the
     reference-generated fixture holds: "desc", "debiased", "jaccard", "pseudo_labels", "smoothed".
@@ -194,7 +204,14 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     ``use_side`` (the script's --sie, ``arch="swin"`` only) passes each image's camera as the view index of both its views.
     Gallery and query images may each be a sequence of uint8 [h,w,3] arrays of any sizes instead (see ``inference_efficient``); ``size``
     = (H, W) is what a Swin resizes them to (default (448, 224); the ResNet family is fixed at 256x128 unless ``arch="seres18_hw"``, which
-    runs seres18_ibn weights in exact fp32 at the float images' own size or at ``size``: VeRi is ``size=(224, int(ratio * 224))``)."""
+    runs seres18_ibn weights in exact fp32 at the float images' own size or at ``size``: VeRi is ``size=(224, int(ratio * 224))``;
+    ``hw_precision`` "f32" / "f16x3" names that forward's arithmetic for this call - ``Engine.set_hw_precision``, restored afterwards - and
+    None leaves the engine's setting alone)."""
+    if hw_precision is not None:
+        from .engine import Engine
+        if arch != "seres18_hw":
+            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw'; arch=%r takes none" % (arch,))
+        Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
     if arch not in ARCHS:
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
     if use_side and arch != "swin":
@@ -214,9 +231,10 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     merged = DevArray(eng, (n, width), np.float32)
     dists = DevArray(eng, (n, n), np.float32)
     try:
-        inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None, size=size if u8[0] else None)
+        inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None, size=size if u8[0] else None,
+                            hw_precision=hw_precision)
         inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None,
-                            size=size if u8[1] else None)
+                            size=size if u8[1] else None, hw_precision=hw_precision)
         if taps is not None:
             taps["desc"] = merged.numpy()
         merged_cams = np.concatenate([gc, qc]).astype(np.int32)
