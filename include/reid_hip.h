@@ -147,6 +147,14 @@ int reid_embed_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* of
  * frame and non-empty (an empty slice fails in the reference's cv2.resize as well). */
 int reid_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame_hwc, int fh, int fw, const int32_t* boxes_xyxy, int n,
                         float* emb, float* logits);
+/* reid_embed_frame_u8 at out_h x out_w: DeepSort._get_features' windows ([external] deep_sort.py) through Extractor._preprocess of an
+ * extractor built at another size (feature_extractor.py:31-46).  Size, mean_std6 and refusals as reid_embed_ragged_u8_hw: (256, 128) is
+ * reid_embed_frame_u8 (every architecture and mode, mean_std6 NULL or 0.5 / 0.5); any other size (sides 32 .. 512) runs seres18_ibn under the
+ * reid_ctx_set_hw_precision rule, opened by the fused resize + stem + max-pool kernel of libreid_hip_anysize_front.so, which must lie
+ * beside this library like libreid_hip_anysize.so (REID_ERR_STATE naming the missing file, before anything is queued).  The embeddings
+ * are those of reid_embed_ragged_u8_hw on the same pixels, bit for bit. */
+int reid_embed_frame_u8_hw(reid_ctx* ctx, const uint8_t* frame_hwc, int fh, int fw, const int32_t* boxes_xyxy, int n, int out_h, int out_w,
+                           const float* mean_std6, float* emb, float* logits);
 /* normalised float images, fp32[n][3][256][128] NCHW: the model(im_batch) call of the plugin surface
  * (modification_tracking/models/__init__.py:93-121 returned object) */
 int reid_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, float* emb, float* logits);
@@ -369,6 +377,13 @@ int reid_frame_submit(reid_ctx* ctx, int slot, const uint8_t* packed, const int6
  * (REID_ERR_STATE, naming the file), a bad size or mean_std6 (REID_ERR_ARG). */
 int reid_frame_submit_swin(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m, int out_h,
                            int out_w, const float* mean_std6);
+/* submit for a tracker whose Extractor resizes to another crop size than 256 x 128 (feature_extractor.py:31-46 with `size=`; DeepSORT's
+ * own 128 x 64, the evaluation script's VeRi geometry, image_reid_inference.py:169-180): as reid_frame_submit - asynchronous, the same
+ * slot state, uploads and stream order, 512-wide embeddings - with the forward of reid_embed_ragged_u8_hw in passes of the same size,
+ * opened by the fused front end of libreid_hip_anysize_front.so.  out_h, out_w, mean_std6 (read before the call returns) and every
+ * refusal as reid_embed_frame_u8_hw; (256, 128) is reid_frame_submit.  Refused before anything is queued or the slot is touched. */
+int reid_frame_submit_hw(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m, int out_h, int out_w,
+                         const float* mean_std6);
 int reid_frame_cost(reid_ctx* ctx, int slot, reid_bank* bank, const int32_t* slots, int t, int metric, float max_dist,
                     const double* tracks_t4, const double* dets_m4, int want_emb);
 int reid_frame_fetch(reid_ctx* ctx, int slot, float* emb, float* cost_tm, double* iou_tm);

@@ -122,6 +122,20 @@ int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, const float
 int reid_debug_any_conv(reid_ctx* ctx, int hw_precision, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int r,
                         int stride, int pad, const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out,
                         int* form_out);
+/* The front end of the any-size forward from uint8 windows (tests/test_gpu_anysize_front.py) through the launcher reid_frame_submit_hw and
+ * reid_embed_frame_u8_hw call, on host operands: src [src_bytes] holds n windows, window i hw[2i] x hw[2i + 1] pixels at byte offsets[i],
+ * its rows one after the other (pitch 0) or `pitch` pixels apart (windows of one frame); every window must lie inside src.  They are
+ * resized to out_h x out_w (cv2-style bilinear), normalised with mean_std6 (NULL = 0.5 / 0.5), convolved with stem_w [64][192]
+ * (k = r * 24 + s * 3 + c, zero padded), scaled by scale / shift [64] and max-pooled (3, 2, 1).
+ *   fused 1   any_front_kernel of libreid_hip_anysize_front.so, one launch
+ *   fused 0   any_resize_norm_kernel, the generic GEMM's stem and maxpool3s2_kernel, as the other reid_*_hw entries run
+ * out [n H2 W2 64 + W2 64]: the pooled map NHWC and ONE guard pixel row (W2 * 64 floats) behind it, preset to 0xff bytes with the rest.
+ * The switch "any_front" (reid_debug_set_switch) picks the front end of the two entries: 1 = the kernel, 0 = the three launches, 2 (default) =
+ * the kernel for passes of at most 65 536 stem pixels (n H1 W1), where it measured faster, the three launches above.
+ * Returns the context's fault status. */
+int reid_debug_any_front(reid_ctx* ctx, int fused, const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int32_t* hw, int n,
+                         int pitch, int out_h, int out_w, const float* mean_std6, const float* stem_w, const float* scale, const float* shift,
+                         float* out);
 /* gem_neck of the last block's tail in one launch (launch_gem_neck_tail; tests/test_gpu_tail_stream.py): GeM + BNNeck of
  * relu(gate y + shortcut) with se_tail's gate, fp32 operands as in se_tail; equals se_tail form 4 followed by gem_neck bit for bit. */
 int reid_debug_gem_neck_fused(reid_ctx* ctx, int n, int hw, int c, int mid, int tiles, float p, const float* stats, const float* w1,

@@ -4,6 +4,7 @@
 #include "siblings_f16.h"
 #include "anysize.h"
 #include "anysize_x3.h"
+#include "anysize_front.h"
 #include <cmath>
 #include <dlfcn.h>
 #include <mutex>
@@ -1523,6 +1524,21 @@ static int anysize_x3_api(const AnysizeX3Api** out) {
     return REID_OK;
 }
 
+// ... and its front end from uint8 windows in one kernel (reid_frame_submit_hw, reid_embed_frame_u8_hw): anysize_front.h
+static int anysize_front_api(decltype(&anysize_front)* out) {
+    static std::mutex m;
+    static decltype(&anysize_front) front = nullptr;
+    std::lock_guard<std::mutex> lk(m);
+    if (!front) {
+        void* f[1];
+        REID_TRY(open_beside_self("libreid_hip_anysize_front.so", "the frame pipeline of ResNet18-IBN-SE at another input size needs",
+                                  {"anysize_front"}, f));
+        front = (decltype(front))f[0];
+    }
+    *out = front;
+    return REID_OK;
+}
+
 bool se_any_routes(const reid_ctx* ctx, int h, int w) { return h != IMG_H || w != IMG_W || ctx->anysize_force != 0; }
 
 int se_any_pass(const reid_ctx* ctx, int h, int w) {
@@ -1554,6 +1570,22 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
         REID_TRY(anysize_x3_api(&x3));
     }
     return REID_OK;
+}
+
+int se_any_front_ready(reid_ctx* ctx, int h, int w, const float** mean_std6, const char* who) {
+    static const float kHalf[6] = {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f};
+    if (!*mean_std6) *mean_std6 = kHalf;
+    for (int i = 0; i < 6; ++i) ARG_CHECK(std::isfinite((*mean_std6)[i]) && (i < 3 || (*mean_std6)[i] > 0.f));
+    REID_TRY(se_any_ready(ctx, h, w, who));
+    if (!se_any_routes(ctx, h, w)) {
+        if (memcmp(*mean_std6, kHalf, sizeof(kHalf)) != 0) {
+            reid_set_error("%s: at 256 x 128 the existing forward normalises with mean = std = 0.5 only", who);
+            return REID_ERR_ARG;
+        }
+        return REID_OK;
+    }
+    decltype(&anysize_front) front;
+    return anysize_front_api(&front);
 }
 
 static int any_launched(hipError_t e, const char* what) {
@@ -1640,15 +1672,21 @@ int launch_any_conv(reid_ctx* ctx, int arith, const float* x, int n, int H, int 
     return REID_OK;
 }
 
-// x: fp32 NHWC [n][h][w][3] on the device
-static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
-    Se18Weights& wt = ctx->se18;
+// The buffers of one pass of n images at h x w: the stem map (want_stem; the fused front end never writes one), the pooled map, the
+// trunk's ring and the GeM output
+struct AnyBufs {
+    int H1, W1, H2, W2;
+    size_t elems[11], per;
+    float *stem = nullptr, *pool, *tbase, *gem;
+};
+static int any_bufs(reid_ctx* ctx, int n, int h, int w, bool want_stem, AnyBufs& b) {
+    const Se18Weights& wt = ctx->se18;
     const bool keep = ctx->debug_keep != 0;
-    const int arith = ctx->hw_precision == 2 ? 2 : 0;   // the setting and nothing else picks the trunk's convolution launcher
-    const int H1 = (h + 6 - 7) / 2 + 1, W1 = (w + 6 - 7) / 2 + 1;        // conv 7x7 s2 p3
-    const int H2 = (H1 + 2 - 3) / 2 + 1, W2 = (W1 + 2 - 3) / 2 + 1;      // MaxPool2d(3, 2, 1)
+    b.H1 = (h + 6 - 7) / 2 + 1, b.W1 = (w + 6 - 7) / 2 + 1;              // conv 7x7 s2 p3
+    b.H2 = (b.H1 + 2 - 3) / 2 + 1, b.W2 = (b.W1 + 2 - 3) / 2 + 1;        // MaxPool2d(3, 2, 1)
+    const int H1 = b.H1, W1 = b.W1, H2 = b.H2, W2 = b.W2;
     ARG_CHECK((long long)n * H1 * W1 < (1ll << 31));                     // the GEMM's row index is an int (element offsets are 64-bit)
-    size_t elems[11];
+    size_t* elems = b.elems;
     elems[0] = (size_t)H1 * W1 * 64;
     elems[1] = (size_t)H2 * W2 * 64;
     size_t per = elems[1];
@@ -1663,20 +1701,65 @@ static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int 
         }
     }
     elems[10] = 512;
-    float *stem, *pool, *tbase, *gem;
-    REID_TRY(ctx_ws(ctx, "se18.stem", (size_t)n * elems[0] * 4, (void**)&stem));
-    REID_TRY(ctx_ws(ctx, "se18.pool", (size_t)n * per * 4, (void**)&pool));
-    REID_TRY(ctx_ws(ctx, "se18.t", (size_t)n * per * 4 * (keep ? 4 * 8 : 4), (void**)&tbase));
-    REID_TRY(ctx_ws(ctx, "se18.gem", (size_t)n * 512 * 4, (void**)&gem));
+    b.per = per;
+    if (want_stem) REID_TRY(ctx_ws(ctx, "se18.stem", (size_t)n * elems[0] * 4, (void**)&b.stem));
+    REID_TRY(ctx_ws(ctx, "se18.pool", (size_t)n * per * 4, (void**)&b.pool));
+    REID_TRY(ctx_ws(ctx, "se18.t", (size_t)n * per * 4 * (keep ? 4 * 8 : 4), (void**)&b.tbase));
+    REID_TRY(ctx_ws(ctx, "se18.gem", (size_t)n * 512 * 4, (void**)&b.gem));
+    return REID_OK;
+}
+
+// stem: conv7x7 s2 p3 + BN, no ReLU (SERes18_IBN.py:251-253), then MaxPool2d(3, 2, 1) with -inf padding (:254; maxpool3s2_kernel skips
+// the taps outside the map, at odd sizes too).  x: fp32 NHWC [n][h][w][3] on the device
+static int any_stem_pool(reid_ctx* ctx, const float* x, int n, int h, int w, const float* stem_w, const float* scale, const float* shift,
+                         float* stem, float* pool) {
+    REID_TRY(any_conv(ctx, A_STEM_F32, x, n, h, w, 3, stem_w, 64, 7, 2, 3, scale, shift, nullptr, 0, 0, stem));
+    return launch_maxpool3s2(ctx, stem, n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 64, pool);
+}
+
+// The front end of the any-size forward from uploaded uint8 windows, as the new entries and reid_debug_any_front launch it:
+// fused = any_front_kernel (libreid_hip_anysize_front.so), else the three launches of the other reid_*_hw entries - the same bits.
+// stem [n][H1][W1][64] is written by the three launches only (fused: may be NULL); pool [n][H2][W2][64].
+int launch_any_front(reid_ctx* ctx, int fused, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
+                     const float* mean_std6, const float* stem_w, const float* scale, const float* shift, float* stem, float* pool) {
+    if (fused) {
+        decltype(&anysize_front) front;
+        REID_TRY(anysize_front_api(&front));
+        const int H1 = (h - 1) / 2 + 1, W1 = (w - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
+        prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * n * H1 * W1 * 64 * 147.0, (double)n * h * w * 3.0 + (double)n * H2 * W2 * 64 * 4.0 + 64 * 147 * 4.0);
+        const hipError_t e = front(ctx->stream, d_src, d_off, d_hw, n, h, w, pitch, mean_std6, stem_w, scale, shift, pool);
+        prof_end(ctx);
+        if (e != hipSuccess) {
+            reid_set_error("libreid_hip_anysize_front.so anysize_front -> %s", hipGetErrorString(e));
+            return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+        }
+        return REID_OK;
+    }
+    ARG_CHECK(stem != nullptr);
+    const AnysizeApi* api;
+    REID_TRY(anysize_api(&api));
+    float* nhwc;
+    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)n * h * w * 3 * 4, (void**)&nhwc));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * w * 15.0);
+    const hipError_t e = api->resize(ctx->stream, d_src, d_off, d_hw, n, h, w, pitch, mean_std6, nhwc);
+    prof_end(ctx);
+    REID_TRY(any_launched(e, "anysize_resize_norm"));
+    return any_stem_pool(ctx, nhwc, n, h, w, stem_w, scale, shift, stem, pool);
+}
+
+// the forward behind the pooled map b.pool [n][H2][W2][64] (b.stem: stage 0, or NULL when nothing wrote one)
+static int seres18_trunk_any(reid_ctx* ctx, const AnyBufs& b, int n, float* d_emb, float* d_logits) {
+    Se18Weights& wt = ctx->se18;
+    const bool keep = ctx->debug_keep != 0;
+    const int arith = ctx->hw_precision == 2 ? 2 : 0;   // the setting and nothing else picks the trunk's convolution launcher
+    const size_t per = b.per;
+    const size_t* elems = b.elems;
+    float *stem = b.stem, *pool = b.pool, *tbase = b.tbase, *gem = b.gem;
     float* stage[11];
-    // stem: conv7x7 s2 p3 + BN, no ReLU (SERes18_IBN.py:251-253), then MaxPool2d(3, 2, 1) with -inf padding (:254; maxpool3s2_kernel skips
-    // the taps outside the map, at odd sizes too)
-    REID_TRY(any_conv(ctx, A_STEM_F32, x, n, h, w, 3, wt.stem_w, 64, 7, 2, 3, wt.stem_scale, wt.stem_shift, nullptr, 0, 0, stem));
-    REID_TRY(launch_maxpool3s2(ctx, stem, n, H1, W1, 64, pool));
     stage[0] = stem;
     stage[1] = pool;
     const float* cur = pool;
-    int H = H2, W = W2;
+    int H = b.H2, W = b.W2;
     for (int i = 0; i < 8; ++i) {
         const Se18Block& k = wt.blk[i];
         float* free_[3];
@@ -1739,6 +1822,15 @@ static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int 
     return REID_OK;
 }
 
+// x: fp32 NHWC [n][h][w][3] on the device
+static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
+    const Se18Weights& wt = ctx->se18;
+    AnyBufs b;
+    REID_TRY(any_bufs(ctx, n, h, w, true, b));
+    REID_TRY(any_stem_pool(ctx, x, n, h, w, wt.stem_w, wt.stem_scale, wt.stem_shift, b.stem, b.pool));
+    return seres18_trunk_any(ctx, b, n, d_emb, d_logits);
+}
+
 int se_any_run_nchw(reid_ctx* ctx, const float* d_x, int m, int h, int w, int mirror, float* d_emb, float* d_log) {
     const AnysizeApi* api;
     REID_TRY(anysize_api(&api));
@@ -1751,7 +1843,23 @@ int se_any_run_nchw(reid_ctx* ctx, const float* d_x, int m, int h, int w, int mi
     return seres18_forward_any(ctx, nhwc, m, h, w, d_emb, d_log);
 }
 
-static int se_any_run_windows(reid_ctx* ctx, const RaggedSrc& src, int i, int m, int h, int w, const float* mean_std6, float* d_emb, float* d_log) {
+// front: the caller is one of the frame pipeline's entries (reid_frame_submit_hw, reid_embed_frame_u8_hw), whose front end is the fused kernel
+// unless the switch any_front is 0 or reid_ctx_set_debug_keep is on (stage 0, the stem map, exists after the three launches only)
+// Measured (profiles/tracking_hw_bench.json): the kernel beats the three launches on a frame-sized pass of DeepSORT-sized crops (30 crops at
+// 128 x 64: 61 440 stem pixels) and loses at 30 crops of 224 x 268 (450 240) and at 1024 crops of either size, so the default keeps it to
+// passes of at most 65 536 stem pixels.  The bits are the same either way.
+constexpr long long ANY_FRONT_MAX_STEM_PIXELS = 65536;
+static int se_any_run_windows(reid_ctx* ctx, const RaggedSrc& src, int i, int m, int h, int w, const float* mean_std6, float* d_emb, float* d_log,
+                              bool front = false) {
+    const bool small = (long long)m * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) <= ANY_FRONT_MAX_STEM_PIXELS;
+    if (front && (ctx->any_front == 1 || (ctx->any_front == 2 && small)) && !ctx->debug_keep) {
+        const Se18Weights& wt = ctx->se18;
+        AnyBufs b;
+        REID_TRY(any_bufs(ctx, m, h, w, false, b));
+        REID_TRY(launch_any_front(ctx, 1, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, h, w, src.pitch, mean_std6, wt.stem_w, wt.stem_scale,
+                                  wt.stem_shift, nullptr, b.pool));
+        return seres18_trunk_any(ctx, b, m, d_emb, d_log);
+    }
     const AnysizeApi* api;
     REID_TRY(anysize_api(&api));
     float* nhwc;
@@ -1874,6 +1982,41 @@ extern "C" int reid_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame, int fh, 
     RaggedSrc src{};
     REID_TRY(src.frame(frame, fh, fw, boxes_xyxy, n));
     return se_embed_windows(ctx, src, emb, logits);
+}
+
+// reid_embed_frame_u8 at out_h x out_w: DeepSort._get_features' slices ([external] deep_sort.py) through Extractor._preprocess at the size
+// the extractor was built with (feature_extractor.py:31-46, `size=`), the any-size forward opened by the fused front end (anysize_front.h)
+extern "C" int reid_embed_frame_u8_hw(reid_ctx* ctx, const uint8_t* frame, int fh, int fw, const int32_t* boxes_xyxy, int n, int out_h, int out_w,
+                                      const float* mean_std6, float* emb, float* logits) {
+    ARG_CHECK(ctx && frame && boxes_xyxy && emb && fh >= 1 && fw >= 1 && n >= 0);
+    REID_TRY(se_any_front_ready(ctx, out_h, out_w, &mean_std6, "reid_embed_frame_u8_hw"));
+    if (!se_any_routes(ctx, out_h, out_w)) return reid_embed_frame_u8(ctx, frame, fh, fw, boxes_xyxy, n, emb, logits);
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    RaggedSrc src{};
+    REID_TRY(src.frame(frame, fh, fw, boxes_xyxy, n));
+    EmbedOut out{emb, logits, 512, ctx->se18.num_class};
+    REID_TRY(src.alloc(ctx, "io"));
+    REID_TRY(out.alloc(ctx, "io", n, 0, logits != nullptr));
+    return embed_host(
+        ctx, n, se_any_pass(ctx, out_h, out_w), [&](int i, int m, hipStream_t s) -> int { return src.up(i, m, s); },
+        [&](int i, int m, float* d_emb, float* d_log) -> int {
+            return se_any_run_windows(ctx, src, i, m, out_h, out_w, mean_std6, d_emb, d_log, true);
+        },
+        out);
+}
+
+// The frame pipeline's submit at out_h x out_w (reid_frame_submit_hw, bank.hip; contract: reid_internal.h)
+int any_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                       int out_w, const float* mean_std6, float** d_emb_out, bool side_copy) {
+    RaggedSrc src{packed, offsets, hw, n};
+    EmbedOut out{nullptr, nullptr, 512, ctx->se18.num_class};
+    REID_TRY(ragged_enqueue_begin(ctx, tag, src, out, false, side_copy));
+    REID_TRY(embed_dev_passes(n, se_any_pass(ctx, out_h, out_w), [&](int i, int m) -> int {
+        return se_any_run_windows(ctx, src, i, m, out_h, out_w, mean_std6, out.d_emb + (size_t)i * 512, nullptr, true);
+    }));
+    *d_emb_out = out.d_emb;
+    return REID_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ matching

@@ -616,6 +616,21 @@ extern "C" int reid_frame_submit_swin(reid_ctx* ctx, int slot, const uint8_t* pa
     });
 }
 
+// The same for ResNet18-IBN-SE at another crop size (any_ragged_enqueue: the forward of reid_embed_ragged_u8_hw behind the fused front end
+// of anysize_front.h) - Extractor(size=) of the tracker ([external] deep_sort.py, feature_extractor.py:31-46).  256 x 128 is reid_frame_submit.
+// Refusals come first here too: arguments, the size / architecture / precision rule, a missing side library.
+extern "C" int reid_frame_submit_hw(reid_ctx* ctx, int slot, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int m, int out_h,
+                                    int out_w, const float* mean_std6) {
+    ARG_CHECK(ctx && (slot == 0 || slot == 1) && m >= 0 && (m == 0 || (packed && offsets && hw)));
+    REID_TRY(se_any_front_ready(ctx, out_h, out_w, &mean_std6, "reid_frame_submit_hw"));
+    if (!se_any_routes(ctx, out_h, out_w)) return reid_frame_submit(ctx, slot, packed, offsets, hw, m);
+    CTX_ENTER(ctx);
+    for (int i = 0; i < m; ++i) ARG_CHECK(hw[2 * i] >= 1 && hw[2 * i + 1] >= 1 && offsets[i] >= 0);
+    return frame_submit_impl(ctx, slot, offsets, hw, m, 512, [&](const char* tag, const int64_t* off, const int32_t* hw_, float** d_emb) -> int {
+        return any_ragged_enqueue(ctx, tag, packed, off, hw_, m, out_h, out_w, mean_std6, d_emb, ctx->side_copy != 0 && ctx->stream != nullptr);
+    });
+}
+
 // Cost stage for `groups` camera streams batched into one frame slot (reid_frame_cost is the one-group case): the slot's m
 // detections are the cameras' detections one camera after the other (m_counts[g] each); group g's tracks are matched against ITS
 // detections only, on ITS bank.  Host arrays are the groups' concatenations; outputs are the groups' t_g x m_g blocks, concatenated.

@@ -26,6 +26,7 @@ const Switch kSwitches[] = {
     {"split_x3", &reid_ctx::split_x3}, {"x3_ablate", &reid_ctx::x3_ablate}, {"x3_unroll", &reid_ctx::x3_unroll}, {"x3_narrow", &reid_ctx::x3_narrow}, {"conv_x3s", &reid_ctx::conv_x3s}, {"x3s_sk_cap", &reid_ctx::x3s_sk_cap}, {"x3_l4_narrow_nmt", &reid_ctx::x3_l4_narrow_nmt}, {"split_x3_small", &reid_ctx::split_x3_small}, {"split_x3_min_blocks", &reid_ctx::split_x3_min_blocks}, {"f32_dist_bk16", &reid_ctx::f32_dist_bk16}, {"lin_x3", &reid_ctx::lin_x3},
     {"host_pipeline", &reid_ctx::host_pipeline}, {"x3_sk_cap", &reid_ctx::x3_sk_cap}, {"chain", &reid_ctx::chain}, {"split_gemm_min_tiles", &reid_ctx::split_gemm_min_tiles},
     {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc}, {"gem_tail_min", &reid_ctx::gem_tail_min}, {"anysize_force", &reid_ctx::anysize_force},
+    {"any_front", &reid_ctx::any_front},
 };
 }  // namespace
 
@@ -765,6 +766,42 @@ extern "C" int reid_debug_any_conv(reid_ctx* ctx, int hw_precision, const float*
     REID_TRY(launch_any_conv(ctx, hw_precision, dx, n, h, w, cin, dw, cout, r, stride, pad, ds, dh, dr, relu, relu_from, dout));
     if (form_out) *form_out = ctx->any_conv_form;
     REID_TRY(dbg_download(ctx, out, dout, ny + cout));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// The front end of the any-size forward from uint8 windows through launch_any_front, the function reid_frame_submit_hw and
+// reid_embed_frame_u8_hw call: fused 1 = any_front_kernel (libreid_hip_anysize_front.so), 0 = resize, stem GEMM and max-pool in three launches.
+extern "C" int reid_debug_any_front(reid_ctx* ctx, int fused, const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int32_t* hw,
+                                    int n, int pitch, int out_h, int out_w, const float* mean_std6, const float* stem_w, const float* scale,
+                                    const float* shift, float* out) {
+    ARG_CHECK(ctx && (fused == 0 || fused == 1) && src && src_bytes >= 1 && offsets && hw && n >= 1 && pitch >= 0 && out_h >= 32 && out_h <= 512 &&
+              out_w >= 32 && out_w <= 512 && stem_w && scale && shift && out);
+    static const float kHalf[6] = {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f};
+    if (!mean_std6) mean_std6 = kHalf;
+    for (int i = 0; i < 6; ++i) ARG_CHECK(std::isfinite(mean_std6[i]) && (i < 3 || mean_std6[i] > 0.f));
+    for (int i = 0; i < n; ++i) {   // every window inside the source
+        const int64_t h = hw[2 * i], w = hw[2 * i + 1];
+        ARG_CHECK(h >= 1 && w >= 1 && offsets[i] >= 0 && (pitch == 0 || w <= pitch));
+        ARG_CHECK(offsets[i] + (pitch ? ((h - 1) * pitch + w) * 3 : h * w * 3) <= src_bytes);
+    }
+    CTX_ENTER(ctx);
+    const int H1 = (out_h - 1) / 2 + 1, W1 = (out_w - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
+    const size_t ny = (size_t)n * H2 * W2 * 64 + (size_t)W2 * 64;
+    uint8_t* dsrc;
+    long long* doff;
+    int* dhw;
+    float *dw, *ds, *dh, *dstem = nullptr, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgf.src", src, (size_t)src_bytes, &dsrc));
+    REID_TRY(dbg_upload(ctx, "dbgf.off", (const long long*)offsets, (size_t)n, &doff));
+    REID_TRY(dbg_upload(ctx, "dbgf.hw", (const int*)hw, (size_t)2 * n, &dhw));
+    REID_TRY(dbg_upload(ctx, "dbgf.w", stem_w, (size_t)64 * 192, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgf.scale", scale, (size_t)64, &ds));
+    REID_TRY(dbg_upload(ctx, "dbgf.shift", shift, (size_t)64, &dh));
+    if (!fused) REID_TRY(ctx_ws(ctx, "dbgf.stem", (size_t)n * H1 * W1 * 64 * 4, (void**)&dstem));
+    REID_TRY(dbg_output(ctx, "dbgf.out", ny, &dout));
+    REID_TRY(launch_any_front(ctx, fused, dsrc, doff, dhw, n, out_h, out_w, pitch, mean_std6, dw, ds, dh, dstem, dout));
+    REID_TRY(dbg_download(ctx, out, dout, ny));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }

@@ -491,6 +491,9 @@ struct reid_ctx {
     float* stage_ptr[11] = {nullptr};
     size_t stage_elems[11] = {0};   // floats per image of each stage tap of the last pass, when that pass ran the any-size forward (else 0)
     int anysize_force = 0;   // libreid_hip_debug.so switch: 256 x 128 through the any-size forward too (reid_*_hw entries; A/B and tests)
+    int any_front = 2;       // libreid_hip_debug.so switch: the front end of reid_frame_submit_hw / reid_embed_frame_u8_hw: 1 = any_front_kernel
+                             // (libreid_hip_anysize_front.so), 0 = the three launches of the other reid_*_hw entries (A/B inside one call),
+                             // 2 (default) = the kernel where it measured faster - passes of at most ANY_FRONT_MAX_STEM_PIXELS - else the launches
     int hw_precision = -1;   // reid_ctx_set_hw_precision: the arithmetic of the any-size forward: -1 = it needs the context in mode 0 (default),
                              // 0 = exact fp32 whatever the mode, 2 = fp32-class whatever the mode (libreid_hip_anysize_x3.so)
     int any_conv_form = 0;   // the tile form the last fp32-class any-size convolution launched (anysize_x3.h), written on the host only
@@ -763,6 +766,17 @@ bool se_any_routes(const reid_ctx* ctx, int h, int w);
 int se_any_ready(reid_ctx* ctx, int h, int w, const char* who);
 int se_any_pass(const reid_ctx* ctx, int h, int w);
 int se_any_run_nchw(reid_ctx* ctx, const float* d_x, int m, int h, int w, int mirror, float* d_emb, float* d_log);
+// The frame pipeline at out_h x out_w (reid_frame_submit_hw, reid_embed_frame_u8_hw).  se_any_front_ready: what such a call refuses, with
+// nothing queued - *mean_std6 NULL becomes 0.5 / 0.5, a value that is not finite or a std <= 0 is REID_ERR_ARG, then se_any_ready's rules,
+// at 256 x 128 another mean_std6 than 0.5 / 0.5 (REID_ERR_ARG), elsewhere libreid_hip_anysize_front.so (REID_ERR_STATE).
+// any_ragged_enqueue: ragged_enqueue_begin + passes of se_any_pass crops, as embed_ragged_enqueue.  launch_any_front: the front end of
+// one pass on uploaded windows -> pool [n][H2][W2][64]; fused 1 = any_front_kernel, 0 = resize, stem GEMM (into stem [n][H1][W1][64]) and
+// max-pool, the same bits - the forward and reid_debug_any_front call this one function.
+int se_any_front_ready(reid_ctx* ctx, int h, int w, const float** mean_std6, const char* who);
+int any_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                       int out_w, const float* mean_std6, float** d_emb_out, bool side_copy);
+int launch_any_front(reid_ctx* ctx, int fused, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
+                     const float* mean_std6, const float* stem_w, const float* scale, const float* shift, float* stem, float* pool);
 // debug.hip harnesses: the three kernel families of libreid_hip_anysize.so on device operands, with the context's profiling slot
 int launch_any_norm(reid_ctx* ctx, float* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta, const float* bn_scale,
                     const float* bn_shift);

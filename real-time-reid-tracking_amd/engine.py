@@ -530,8 +530,26 @@ class Engine:
         self.__dict__.setdefault("_frame_d", {})[slot] = self.swin_dim
         return n
 
+    @staticmethod
+    def _hw_crop_args(size, mean_std):
+        """(H, W) with each side in 32 .. 512 and mean[3] / std[3] (None: the library's 0.5 / 0.5), checked before any device call."""
+        h, w = check_hw(size)
+        _, _, ms = Engine._swin_crop_args((224, 224), mean_std)
+        return h, w, ms
+
+    def frame_submit_hw(self, slot, crops, size, mean_std=None):
+        """Stage 1 for a ResNet18-IBN-SE tracker at another crop size (reid_frame_submit_hw): as frame_submit, with the forward of
+        embed_ragged_u8(size=) - ``size`` = (H, W), sides 32 .. 512, and ``mean_std`` as there, checked before any device call.  (256, 128)
+        is frame_submit; any other size opens with the fused resize + stem + max-pool kernel (libreid_hip_anysize_front.so)."""
+        h, w, ms = self._hw_crop_args(size, mean_std)
+        slab, offs, hw, n = self._frame_pack(slot, crops)
+        check(self.lib.reid_frame_submit_hw(self.h, int(slot), _ptr(slab), _ptr(offs), _ptr(hw), n, h, w, _ptr(ms)))
+        self.__dict__.setdefault("_frame_n", {})[slot] = n
+        self.__dict__.setdefault("_frame_d", {})[slot] = 512
+        return n
+
     def frame_dim(self, slot):
-        """Width d of the embeddings of the frame last submitted to ``slot``: 512 (frame_submit) or the Swin's 96 (frame_submit_swin)."""
+        """Width d of the embeddings of the frame last submitted to ``slot``: 512 (frame_submit, frame_submit_hw) or the Swin's 96 (frame_submit_swin)."""
         return self.__dict__.get("_frame_d", {}).get(slot, 512)
 
     def frame_gather(self, slot, per, world):
@@ -626,14 +644,23 @@ class Engine:
         slots = np.ascontiguousarray(slots, np.int32)
         check(self.lib.reid_frame_update(self.h, int(slot), bank, _ptr(rows), _ptr(slots), len(rows)))
 
-    def embed_frame_u8(self, frame, boxes_xyxy, logits=False):
-        """uint8[H,W,3] frame + int boxes [n,4] (x1,y1,x2,y2; crop = frame[y1:y2, x1:x2]) -> float32[n,512]."""
+    def embed_frame_u8(self, frame, boxes_xyxy, logits=False, size=None, mean_std=None):
+        """uint8[H,W,3] frame + int boxes [n,4] (x1,y1,x2,y2; crop = frame[y1:y2, x1:x2]) -> float32[n,512].  ``size`` = (H, W), sides
+        32 .. 512, and ``mean_std`` as embed_ragged_u8 (reid_embed_frame_u8_hw: the same bits as embed_ragged_u8(size=) on the slices)."""
+        hw_out = None if size is None else check_hw(size)
+        if mean_std is not None and hw_out is None:
+            hw_out = (IMG_H, IMG_W)
+        _, _, ms = self._swin_crop_args((224, 224), mean_std)
         frame = np.ascontiguousarray(frame, dtype=np.uint8)
         if frame.ndim != 3 or frame.shape[2] != 3:
             raise ValueError("frame must be uint8[H,W,3], got %s" % (frame.shape,))
         boxes = np.ascontiguousarray(boxes_xyxy, dtype=np.int32).reshape(-1, 4)
         n = boxes.shape[0]
         emb, lg = self._outs(n, logits)
+        if hw_out is not None:
+            check(self.lib.reid_embed_frame_u8_hw(self.h, _ptr(frame), frame.shape[0], frame.shape[1], _ptr(boxes), n, hw_out[0], hw_out[1],
+                                                  _ptr(ms), _ptr(emb), _ptr(lg)))
+            return self._ret(emb, lg, logits)
         check(self.lib.reid_embed_frame_u8(self.h, _ptr(frame), frame.shape[0], frame.shape[1], _ptr(boxes), n, _ptr(emb),
                                            _ptr(lg)))
         return self._ret(emb, lg, logits)
@@ -1233,6 +1260,37 @@ class Engine:
         check(_ffi.debug_lib().reid_debug_any_conv(self.h, int(hw_precision), _ptr(x), n, h, w, cin, _ptr(wt), cout, r, int(stride), pad, _ptr(sc),
                                                    _ptr(sh), _ptr(rr), int(bool(relu)), int(relu_from), _ptr(out), C.byref(form)))
         return out[:-cout].reshape(n, ho, wo, cout), out[-cout:], form.value
+
+    def debug_any_front(self, crops, size, stem_w, scale, shift, mean_std=None, fused=True, frame=None):
+        """The front end of the any-size forward from uint8 windows (reid_debug_any_front): resize to ``size`` = (H, W) + normalise +
+        stem (stem_w [64, 192], scale / shift [64]) + max-pool, ``fused`` = any_front_kernel, else the three launches.  ``crops``: a list of
+        uint8[h_i, w_i, 3], or with ``frame`` = uint8[fh, fw, 3] int boxes [n, 4] (x1, y1, x2, y2) of windows of that frame.  Returns
+        (pool [n, H2, W2, 64], guard [W2 * 64] - the pixel row behind the output, NaN unless the kernel wrote out of bounds)."""
+        h, w, ms = self._hw_crop_args(size, mean_std)
+        stem_w, scale, shift = _f32(stem_w), _f32(scale), _f32(shift)
+        if stem_w.size != 64 * 192 or scale.size != 64 or shift.size != 64:
+            raise ValueError("debug_any_front: stem_w [64, 192], scale [64], shift [64]")
+        if frame is None:
+            src, offs, hw, _keep = self._pack_ragged(crops)
+            n, pitch, nbytes = len(crops), 0, int(sum(int(a) * int(b) * 3 for a, b in hw))
+        else:
+            frame = np.ascontiguousarray(frame, dtype=np.uint8)
+            boxes = np.asarray(crops, np.int64).reshape(-1, 4)
+            fh, fw = frame.shape[:2]
+            if frame.ndim != 3 or frame.shape[2] != 3 or not ((boxes[:, 0] >= 0) & (boxes[:, 1] >= 0) & (boxes[:, 2] <= fw) & (boxes[:, 3] <= fh) &
+                                                             (boxes[:, 2] > boxes[:, 0]) & (boxes[:, 3] > boxes[:, 1])).all():
+                raise ValueError("debug_any_front: frame uint8[fh, fw, 3] and non-empty boxes inside it")
+            n, pitch, nbytes = boxes.shape[0], fw, frame.size
+            offs = np.ascontiguousarray((boxes[:, 1] * fw + boxes[:, 0]) * 3, np.int64)
+            hw = np.ascontiguousarray(np.stack([boxes[:, 3] - boxes[:, 1], boxes[:, 2] - boxes[:, 0]], 1), np.int32)
+            src = _ptr(frame)
+        if n < 1:
+            raise ValueError("debug_any_front: at least one window")
+        h2, w2 = stage_shapes(h, w)[1][:2]
+        out = np.empty(n * h2 * w2 * 64 + w2 * 64, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_front(self.h, int(bool(fused)), src, C.c_int64(nbytes), _ptr(offs), _ptr(hw), n, pitch, h, w, _ptr(ms),
+                                                    _ptr(stem_w), _ptr(scale), _ptr(shift), _ptr(out)))
+        return out[:-w2 * 64].reshape(n, h2, w2, 64), out[-w2 * 64:]
 
     def cam_debias_dev(self, d_x, cams, n, d, la=0.05, iters=0):
         cams = np.ascontiguousarray(cams, dtype=np.int32).reshape(-1)

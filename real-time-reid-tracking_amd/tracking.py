@@ -31,25 +31,34 @@ def _two_streams(stream, on):
     stream.eng.frame_match_stream(stream.match_stream)
 
 
-def _check_arch(arch, size, mean_std):
-    """`arch`, `size`, `mean_std` of the stream classes, checked before any device call (ValueError)."""
+def _check_arch(arch, size, mean_std, hw_precision=None):
+    """`arch`, `size`, `mean_std`, `hw_precision` of the stream classes, checked before any device call (ValueError)."""
     if arch == "swin":
         Engine._swin_crop_args(size, mean_std)
+    elif arch == "seres18_hw":
+        Engine._hw_crop_args(size, mean_std)
     elif arch != "seres18":
-        raise ValueError("arch must be 'seres18' or 'swin', got %r" % (arch,))
+        raise ValueError("arch must be 'seres18', 'seres18_hw' or 'swin', got %r" % (arch,))
     elif tuple(size) != (224, 224) or mean_std is not None:
-        raise ValueError("size / mean_std belong to arch='swin' (a ResNet18-SE crop is always 256x128, ImageNet-normalised)")
+        raise ValueError("size / mean_std belong to arch='swin' and 'seres18_hw' (a 'seres18' crop is always 256x128, normalised with 0.5 / 0.5)")
+    if hw_precision is not None and arch != "seres18_hw":
+        raise ValueError("hw_precision belongs to arch='seres18_hw', got arch %r" % (arch,))
+    Engine.hw_precision_value(hw_precision)
 
 
-def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std):
+def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_precision=None):
     """`arch` of the stream classes: "seres18" (default) loads a ResNet18-SE family checkpoint, frames are 512 wide; "swin" - the
     reference's swin_transformer tracker model, modification_tracking/models/__init__.py:80 - loads with `Engine.load_swin`, every crop
     is resized to ``size`` = (H, W) multiples of 224 and normalised with ``mean_std`` (None: ImageNet), and the embeddings, the bank
-    and the cost stage are 96 wide."""
+    and the cost stage are 96 wide; "seres18_hw" - a ResNet18-IBN-SE (seres18_ibn) tracker at another crop size, Extractor(size=) of
+    feature_extractor.py:31-46 - resizes every crop to ``size`` = (H, W), sides 32 .. 512, normalises with ``mean_std`` (None: 0.5 / 0.5)
+    and runs the any-size forward in the arithmetic ``hw_precision`` names (`Engine.set_hw_precision`); frames are 512 wide."""
     if arch == "swin":
         stream.eng.load_swin(weights_blob, manifest)
     else:
         stream.eng.load_seres18(weights_blob, manifest)
+    if arch == "seres18_hw":
+        stream.eng.set_hw_precision(hw_precision)
     stream.arch, stream.size, stream.mean_std = arch, size, mean_std
 
 
@@ -57,6 +66,8 @@ def _frame_submit(stream, slot, crops):
     """What every class's `_submit` hook ends in: the frame's crops into `slot` through the stream's backbone."""
     if getattr(stream, "arch", "seres18") == "swin":
         return stream.eng.frame_submit_swin(slot, crops, stream.size, stream.mean_std)
+    if getattr(stream, "arch", "seres18") == "seres18_hw":
+        return stream.eng.frame_submit_hw(slot, crops, stream.size, stream.mean_std)
     return stream.eng.frame_submit(slot, crops)
 
 
@@ -67,11 +78,11 @@ def _one_stream_again(stream):
 
 class CameraStream:
     def __init__(self, weights_blob, manifest, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0, own_context=True,
-                 max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None):
-        _check_arch(arch, size, mean_std)
+                 max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -124,11 +135,11 @@ class MultiCameraStream:
     with one list entry per camera everywhere; one host thread, one wait per frame time."""
 
     def __init__(self, weights_blob, manifest, cameras, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None):
-        _check_arch(arch, size, mean_std)
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -213,11 +224,11 @@ class LookaheadCameraStream:
     """
 
     def __init__(self, weights_blob, manifest, frames_per_pass=2, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None):
-        _check_arch(arch, size, mean_std)
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
