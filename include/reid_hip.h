@@ -224,6 +224,23 @@ int reid_swin_descriptor_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const i
 /* out[m][n] = metric(x[m][d], y[n][d])        reid/losses/utils.py:12-35, reid/evaluate.py:58 */
 int reid_distmat(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric, float* out);
 int reid_distmat_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, float* d_out);
+/* The same matrix (reid/losses/utils.py:12-35, reid/evaluate.py:58) with the dot product in the fp32-class arithmetic on the f16 matrix
+ * pipe (csrc/distmat_x3.hip in libreid_hip_distmat_x3.so, which must lie beside this library - without the file these
+ * two calls are REID_ERR_STATE naming it and nothing else is affected).  Entry points of their own: no setting changes reid_distmat* or
+ * anything built on it.
+ * Arithmetic: xh = f16_rn(x), xl' = f16_rn((x - xh) 2^11), yh = f16_rn(y), yq = f16(yh 2^11), yl' = f16_rn((y - yh) 2^11) (f16 subnormals
+ * kept); per 32 columns three f16 products into one fp32 accumulator in the order xh.yq, xl'.yh, xh.yl'; x.y = 2^-11 of it.  The squared
+ * norms and the metric formulas are those of reid_distmat*: only the dot product differs.  K is never split: out[i][j] has the same bits
+ * whatever m, n or its position.  The dot product carries the three roundings of the split (about 2^-21 sum_k |x_k y_k|, against 2^-24
+ * per term of exact fp32) - an fp32-class value, NOT the bits of reid_distmat, and no rank (arg-min, top-k, CMC) is promised to agree
+ * with the exact entry where two distances lie closer than both entries' errors.
+ * Domain: |x| < 65504 and |y| 2^11 < 65504 (|y| < 31.98), every operand finite.  A value outside it raises the context's sticky fault
+ * word (bit 0 of reid_ctx_fault_peek): reid_distmat_x3 returns REID_ERR_STATE and its output is invalid; reid_distmat_x3_dev is
+ * asynchronous, there the next synchronising call (reid_ctx_sync) or the next entry reports it; it stays until reid_ctx_clear_fault, as
+ * in mode 2.  L2 and L2SQR are symmetric: the caller may put the larger-ranged set on the x side and read the transpose.
+ * Arguments as reid_distmat*: m == 0 or n == 0 returns REID_OK, a bad metric REID_ERR_ARG.  Profiling kind REID_K_DIST_GEMM. */
+int reid_distmat_x3(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric, float* out);
+int reid_distmat_x3_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, float* d_out);
 /* per-row minimum of the distance matrix; ties -> lowest column index.  From 2048 rows of y on the selection runs in the
  * epilogue of the distance GEMM (csrc/dist_select.hip) and the m x n matrix is never written; smaller problems go through a
  * scratch matrix of a few MB.  evaluate.py:58-63 (the top-1 of `score`). */

@@ -69,6 +69,8 @@ _SIGS = {
     "reid_debug_swin_stage": (_i, [_vp, _i, _vp, _sz, C.POINTER(_sz)]),
     "reid_distmat": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "reid_distmat_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "reid_distmat_x3": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "reid_distmat_x3_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     "reid_argmin_rows": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "reid_argmin_rows_dev": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "reid_knn": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),

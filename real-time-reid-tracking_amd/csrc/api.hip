@@ -4,6 +4,7 @@
 #include "siblings_f16.h"
 #include "anysize.h"
 #include "anysize_x3.h"
+#include "distmat_x3.h"
 #include "anysize_front.h"
 #include <cmath>
 #include <dlfcn.h>
@@ -2106,6 +2107,70 @@ static int pad_rows_to(reid_ctx* ctx, const char* name, const float* d_x, int m,
     *out = buf;
     *ld = dp;
     return REID_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ fp32-class distance matrix
+// reid_distmat_x3*: reid_distmat* with the dot product in the fp32-class arithmetic (dist_x3_kernel of libreid_hip_distmat_x3.so,
+// distmat_x3.h).  Entry points of their own: no setting moves an existing call, and nothing else calls them.  The squared norms come from
+// the launch the exact entry uses, on the same rows padded further with zeros (which add nothing to a sum of squares): only the dot
+// product differs between the two entries.  Workspace names of their own (distx3.*): interleaved exact calls keep their buffers.
+static int distmat_x3_api(decltype(&distmat_x3)* out) {
+    static std::mutex m;
+    static decltype(&distmat_x3) fn = nullptr;
+    std::lock_guard<std::mutex> lk(m);
+    if (!fn) {
+        void* f[1];
+        REID_TRY(open_beside_self("libreid_hip_distmat_x3.so", "the distance matrix in the fp32-class arithmetic (reid_distmat_x3) needs",
+                                  {"distmat_x3"}, f));
+        fn = (decltype(fn))f[0];
+    }
+    *out = fn;
+    return REID_OK;
+}
+
+extern "C" int reid_distmat_x3_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, float* d_out) {
+    ARG_CHECK(ctx && d_x && d_y && d_out && m >= 0 && n >= 0 && d >= 1);
+    CTX_ENTER(ctx);
+    ARG_CHECK(metric >= REID_METRIC_L2 && metric <= REID_METRIC_DOT);
+    if (m == 0 || n == 0) return REID_OK;
+    decltype(&distmat_x3) fn;
+    REID_TRY(distmat_x3_api(&fn));
+    const float *xp, *yp;
+    int ldx, ldy;
+    REID_TRY(pad_rows_to(ctx, "distx3.xpad", d_x, m, d, 32, &xp, &ldx));   // whole K steps, 16-byte rows, zero columns
+    REID_TRY(pad_rows_to(ctx, "distx3.ypad", d_y, n, d, 32, &yp, &ldy));
+    float *xx = nullptr, *yy = nullptr;
+    if (metric != REID_METRIC_DOT) {
+        REID_TRY(ctx_ws(ctx, "distx3.xx", (size_t)m * 4, (void**)&xx));
+        REID_TRY(ctx_ws(ctx, "distx3.yy", (size_t)n * 4, (void**)&yy));
+        REID_TRY(launch_row_sqnorm(ctx, xp, m, ldx, ldx, xx));
+        REID_TRY(launch_row_sqnorm(ctx, yp, n, ldy, ldy, yy));
+    }
+    prof_begin(ctx, REID_K_DIST_GEMM, 2.0 * m * n * d, 4.0 * ((double)m * d + (double)n * d + (double)m * n));
+    const hipError_t e = fn(ctx->stream, xp, m, yp, n, ldx, xx, yy, metric, d_out, ctx->fault, nullptr);
+    prof_end(ctx);
+    if (e != hipSuccess) {
+        reid_set_error("libreid_hip_distmat_x3.so distmat_x3 -> %s", hipGetErrorString(e));
+        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+    }
+    return REID_OK;
+}
+
+extern "C" int reid_distmat_x3(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric, float* out) {
+    ARG_CHECK(ctx && x && y && out && m >= 0 && n >= 0 && d >= 1);
+    CTX_ENTER(ctx);
+    ARG_CHECK(metric >= REID_METRIC_L2 && metric <= REID_METRIC_DOT);
+    if (m == 0 || n == 0) return REID_OK;
+    float *dx, *dy, *d_out;
+    REID_TRY(ctx_ws(ctx, "distx3.io.x", (size_t)m * d * 4, (void**)&dx));
+    REID_TRY(ctx_ws(ctx, "distx3.io.y", (size_t)n * d * 4, (void**)&dy));
+    REID_TRY(ctx_ws(ctx, "distx3.io.out", (size_t)m * n * 4, (void**)&d_out));
+    HIP_TRY(hipMemcpyAsync(dx, x, (size_t)m * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dy, y, (size_t)n * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(reid_distmat_x3_dev(ctx, dx, m, dy, n, d, metric, d_out));
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)m * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);   // an operand outside the domain: the matrix copied out is invalid
 }
 
 // The k smallest distances of every row of x to the rows of y with the selection fused into the distance GEMM

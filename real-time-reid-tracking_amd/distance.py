@@ -3,7 +3,7 @@ reid/faiss_utils.py:56-139.  Inputs may be numpy arrays or torch tensors (CPU or
 import numpy as np
 
 from . import _ffi
-from .engine import get_engine
+from .engine import Engine, get_engine
 
 
 def _np(a):
@@ -12,19 +12,26 @@ def _np(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-def euclidean_dist(x, y, device=0):
+def _distmat(x, y, metric, device, precision):
+    """precision None / "f32": today's call and bits; "f16x3": the dot product in the fp32-class arithmetic (reid_distmat_x3: |x| < 65504,
+    |y| < 31.98, other bits, no rank promised); anything else is a ValueError before the device is touched."""
+    Engine.distmat_precision_value(precision)
+    return get_engine(device).distmat(_np(x), _np(y), metric, precision=precision)
+
+
+def euclidean_dist(x, y, device=0, precision=None):
     """sqrt(clamp(|x|^2 + |y|^2 - 2 x.y^T, 1e-12)) - reid/losses/utils.py:21-35."""
-    return get_engine(device).distmat(_np(x), _np(y), _ffi.METRIC_L2)
+    return _distmat(x, y, _ffi.METRIC_L2, device, precision)
 
 
-def cosine_dist(x, y, device=0):
+def cosine_dist(x, y, device=0, precision=None):
     """(1 - cos)/2 - reid/losses/utils.py:12-18."""
-    return get_engine(device).distmat(_np(x), _np(y), _ffi.METRIC_COS_HALF)
+    return _distmat(x, y, _ffi.METRIC_COS_HALF, device, precision)
 
 
-def cosine_distance(x, y, device=0):
+def cosine_distance(x, y, device=0, precision=None):
     """1 - cos on L2-normalised rows: DeepSORT's appearance cost, gated by MAX_DIST 0.15 (deep_sort.yaml:3)."""
-    return get_engine(device).distmat(_np(x), _np(y), _ffi.METRIC_COS)
+    return _distmat(x, y, _ffi.METRIC_COS, device, precision)
 
 
 def nearest(x, y, metric=_ffi.METRIC_L2, device=0):

@@ -15,6 +15,7 @@ _ENGINES = {}
 IMG_H, IMG_W = 256, 128   # Extractor.size = (128, 256) as (W, H), feature_extractor.py:24
 SIZE_MIN, SIZE_MAX = 32, 512   # input sides of the any-size forward (reid_*_hw, include/reid_hip.h)
 HW_PRECISION_NAMES = {"f32": 0, "fp32": 0, "exact": 0, "f16x3": 2, "fp32-class": 2}   # Engine.set_hw_precision
+DISTMAT_PRECISION_NAMES = {"f32": 0, "f16x3": 2}   # Engine.distmat(precision=): the exact entry, reid_distmat_x3
 
 
 def check_hw(size):
@@ -1157,17 +1158,30 @@ class Engine:
         return out
 
     # ---- matching
-    def distmat(self, x, y, metric=_ffi.METRIC_L2):
+    @staticmethod
+    def distmat_precision_value(v):
+        """None / "f32" -> 0 (reid_distmat*: today's call and bits), "f16x3" -> 2 (reid_distmat_x3*); ValueError otherwise, "f16"
+        included - the fp16-storage mode has no distance matrix -, before any device call."""
+        if v is None:
+            return 0
+        if isinstance(v, str) and v in DISTMAT_PRECISION_NAMES:
+            return DISTMAT_PRECISION_NAMES[v]
+        raise ValueError("distmat precision must be None / \"f32\" (exact fp32) or \"f16x3\" (fp32-class, libreid_hip_distmat_x3.so), got %r" % (v,))
+
+    def distmat(self, x, y, metric=_ffi.METRIC_L2, precision=None):
+        """out[m][n] = metric(x[m][d], y[n][d]).  precision None / "f32": reid_distmat; "f16x3": reid_distmat_x3, the dot product in the
+        fp32-class arithmetic (domain |x| < 65504, |y| < 31.98; other bits than the exact entry, no rank promised)."""
+        fn = "reid_distmat_x3" if Engine.distmat_precision_value(precision) == 2 else "reid_distmat"
         x, y = _f32(x), _f32(y)
         if x.ndim != 2 or y.ndim != 2 or x.shape[1] != y.shape[1]:
             raise ValueError("distmat expects x[m,d], y[n,d]")
         out = np.empty((x.shape[0], y.shape[0]), np.float32)
-        check(self.lib.reid_distmat(self.h, _ptr(x), x.shape[0], _ptr(y), y.shape[0], x.shape[1], int(metric), _ptr(out)))
+        check(getattr(self.lib, fn)(self.h, _ptr(x), x.shape[0], _ptr(y), y.shape[0], x.shape[1], int(metric), _ptr(out)))
         return out
 
-    def distmat_dev(self, d_x, m, d_y, n, d, metric, d_out):
-        check(self.lib.reid_distmat_dev(self.h, C.c_void_p(d_x), int(m), C.c_void_p(d_y), int(n), int(d), int(metric),
-                                        C.c_void_p(d_out)))
+    def distmat_dev(self, d_x, m, d_y, n, d, metric, d_out, precision=None):
+        fn = "reid_distmat_x3_dev" if Engine.distmat_precision_value(precision) == 2 else "reid_distmat_dev"
+        check(getattr(self.lib, fn)(self.h, C.c_void_p(d_x), int(m), C.c_void_p(d_y), int(n), int(d), int(metric), C.c_void_p(d_out)))
 
     def argmin_rows(self, x, y, metric=_ffi.METRIC_L2):
         x, y = _f32(x), _f32(y)
