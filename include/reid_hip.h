@@ -221,7 +221,9 @@ int reid_swin_descriptor_ragged_u8(reid_ctx* ctx, const uint8_t* packed, const i
                                    int out_w, const float* mean_std6, int flip_tta, float* out);
 
 /* ---- matching ----------------------------------------------------------------------------- */
-/* out[m][n] = metric(x[m][d], y[n][d])        reid/losses/utils.py:12-35, reid/evaluate.py:58 */
+/* out[m][n] = metric(x[m][d], y[n][d])        reid/losses/utils.py:12-35, reid/evaluate.py:58
+ * Non-finite operands propagate as in the reference: every metric gives NaN where numpy / torch give NaN, REID_METRIC_L2 included (its
+ * clamp(min=1e-12) keeps NaN); an all-zero row is 0 / 0 = NaN under the cosine metrics; REID_METRIC_DOT gives +-inf where the sum does. */
 int reid_distmat(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric, float* out);
 int reid_distmat_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, float* d_out);
 /* The same matrix (reid/losses/utils.py:12-35, reid/evaluate.py:58) with the dot product in the fp32-class arithmetic on the f16 matrix
@@ -243,13 +245,19 @@ int reid_distmat_x3(reid_ctx* ctx, const float* x, int m, const float* y, int n,
 int reid_distmat_x3_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, float* d_out);
 /* per-row minimum of the distance matrix; ties -> lowest column index.  From 2048 rows of y on the selection runs in the
  * epilogue of the distance GEMM (csrc/dist_select.hip) and the m x n matrix is never written; smaller problems go through a
- * scratch matrix of a few MB.  evaluate.py:58-63 (the top-1 of `score`). */
+ * scratch matrix of a few MB.  evaluate.py:58-63 (the top-1 of `score`).
+ * Distances that are NaN - one rule for reid_argmin_rows* and reid_knn*, whichever path a shape takes: a NaN distance, of either sign bit,
+ * is NOT a candidate.  A row without any non-NaN distance answers idx = -1, val = NaN.  +inf and -inf are ordinary values (-inf is the
+ * smallest); ties go to the lowest column. */
 int reid_argmin_rows(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric,
                      int32_t* idx, float* val);
 int reid_argmin_rows_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric,
                          int32_t* d_idx, float* d_val);
 /* brute-force squared-L2 k-NN: D fp32[nq][k] ascending, I int32[nq][k]; ties -> lowest index.  k <= 64 and nb >= 2048: fused
  * distance + selection (no nq x nb matrix), otherwise distance matrix tiles + a top-k pass.
+ * A NaN distance is not a candidate (the rule at reid_argmin_rows): a row with fewer than k non-NaN distances - k > nb, or NaN in the
+ * operands - is padded with (I = -1, D = +inf).  reid_rerank_jaccard skips such an index (csrc/rerank.hip checks 0 <= index < n).
+ * (Tested for the two-pass and the fused fp32 path; the wide path of large searches, csrc/knn_wide.hip, expects finite operands.)
  * search_raw_array_pytorch / IndexFlatL2.search, reid/faiss_utils.py:56-139 */
 int reid_knn(reid_ctx* ctx, const float* xq, int nq, const float* xb, int nb, int d, int k, float* D, int32_t* I);
 int reid_knn_dev(reid_ctx* ctx, const float* d_xq, int nq, const float* d_xb, int nb, int d, int k,

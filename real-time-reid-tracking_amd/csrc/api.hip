@@ -2177,7 +2177,7 @@ extern "C" int reid_distmat_x3(reid_ctx* ctx, const float* x, int m, const float
 // (dist_select.hip): no m x n matrix.  Returns 1 when the shape is outside the fused kernel's range (k > 64, huge row pitch):
 // the caller then takes the two-pass path.
 static int select_fused_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int k, float* d_D,
-                            int32_t* d_I) {
+                            int32_t* d_I, bool empty_nan = false) {
     // small problems keep the two-pass form: their matrix is a few MB, and without a sample bound the sweep's first tile would
     // append every element
     constexpr int sample = 1024;
@@ -2192,6 +2192,7 @@ static int select_fused_dev(reid_ctx* ctx, const float* d_x, int m, const float*
     p.B = yp; p.ldb = ldy;
     p.M = m; p.N = n; p.K = ldx;
     p.metric = metric; p.k = k;
+    p.empty_nan = empty_nan;
     p.exp_skip = ctx->select_exp;   // 0 in the product; experiments set it through libreid_hip_debug.so (reid_debug_select_exp)
     if (!dist_select_supported(p)) return 1;
     if (metric != REID_METRIC_DOT) {
@@ -2236,7 +2237,7 @@ extern "C" int reid_argmin_rows_dev(reid_ctx* ctx, const float* d_x, int m, cons
     CTX_GUARD(ctx);
     ARG_CHECK(metric >= REID_METRIC_L2 && metric <= REID_METRIC_DOT);
     if (m == 0) return REID_OK;
-    const int st = ctx->select_two_pass ? 1 : select_fused_dev(ctx, d_x, m, d_y, n, d, metric, 1, d_val, d_idx);
+    const int st = ctx->select_two_pass ? 1 : select_fused_dev(ctx, d_x, m, d_y, n, d, metric, 1, d_val, d_idx, true);
     if (st != 1) return st;
     float* dist;
     REID_TRY(ctx_ws(ctx, "sel.dist", (size_t)m * n * 4, (void**)&dist));
@@ -2264,7 +2265,7 @@ extern "C" int reid_argmin_rows(reid_ctx* ctx, const float* x, int m, const floa
 
 extern "C" int reid_knn_dev(reid_ctx* ctx, const float* d_xq, int nq, const float* d_xb, int nb, int d, int k, float* d_D,
                             int32_t* d_I) {
-    ARG_CHECK(ctx && d_D && d_I && nq >= 0 && nb >= 1 && k >= 1);
+    ARG_CHECK(ctx && d_xq && d_xb && d_D && d_I && nq >= 0 && nb >= 1 && d >= 1 && k >= 1);
     CTX_GUARD(ctx);
     if (nq == 0) return REID_OK;
     if (!ctx->select_two_pass && knn_wide_eligible(ctx, nq, nb, d, k)) {

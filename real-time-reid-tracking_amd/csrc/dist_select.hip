@@ -49,7 +49,7 @@ __device__ __forceinline__ float unpack_val(unsigned long long k) {
 
 template <int METRIC>
 __device__ __forceinline__ float dist_of(float dot, float rs, float cq) {   // the arithmetic of gemm_f32_dma.hip's dist_epilogue
-    if (METRIC == REID_METRIC_L2) return sqrtf(fmaxf(l2sqr_of(dot, rs, cq), 1e-12f));
+    if (METRIC == REID_METRIC_L2) return l2_of_sqr(l2sqr_of(dot, rs, cq));
     if (METRIC == REID_METRIC_L2SQR) return l2sqr_of(dot, rs, cq);
     if (METRIC == REID_METRIC_COS_HALF) return (1.0f - dot / (sqrtf(rs) * cq)) / 2.0f;
     if (METRIC == REID_METRIC_COS) return 1.0f - dot / (sqrtf(rs) * cq);
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void dist_select_kernel(const SelectParams 
 #pragma unroll
                         for (int e = 0; e < 16; ++e) {
                             if (pass & (1u << e)) {
-                                v[e] = sqrtf(fmaxf(v[e], 1e-12f));
+                                v[e] = l2_of_sqr(v[e]);
                                 if (!(v[e] <= thr[rbase + (e & 3) + 8 * (e >> 2)])) pass &= ~(1u << e);
                             }
                         }
@@ -380,11 +380,12 @@ __global__ __launch_bounds__(256, 2) void dist_select_kernel(const SelectParams 
 }
 
 // One wave per row: merge of the row's S ascending lists final_keys[row][s][0..k) (padded with ~0) -> D[row][k], I[row][k] ascending,
-// padded with (+inf, -1).  The S * k keys sit in registers (NPL per lane, coalesced loads); k rounds of wave minimum, the owner
+// padded with (empty, -1): empty = +inf for reid_knn, NaN for reid_argmin_rows (a row whose every distance is NaN: the filter v <= thr
+// drops a NaN of either sign, so such a row has no key).  The S * k keys sit in registers (NPL per lane, coalesced loads); k rounds of wave minimum, the owner
 // retires its key.  Keys are unique (they carry the column), so exactly one lane retires per round.
 template <int NPL>
 __global__ __launch_bounds__(256) void select_merge_kernel(const unsigned long long* __restrict__ final_keys, int M, int S, int k,
-                                                           float* __restrict__ D, int32_t* __restrict__ I) {
+                                                           float* __restrict__ D, int32_t* __restrict__ I, float empty) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
     const unsigned long long* L = final_keys + (long long)row * S * k;
@@ -405,7 +406,7 @@ __global__ __launch_bounds__(256) void select_merge_kernel(const unsigned long l
             best = other < best ? other : best;
         }
         if (lane == 0) {
-            if (D) D[(long long)row * k + r] = best == ~0ull ? INFINITY : unpack_val(best);
+            if (D) D[(long long)row * k + r] = best == ~0ull ? empty : unpack_val(best);
             if (I) I[(long long)row * k + r] = best == ~0ull ? -1 : (int32_t)(best & 0xffffffffu);
         }
         if (best != ~0ull) {
@@ -603,7 +604,8 @@ int launch_dist_select(reid_ctx* ctx, const SelectParams& p, float* d_D, int32_t
         LAUNCH_CHECK();
         return REID_OK;
     }
-#define MERGE(NPL) hipLaunchKernelGGL((select_merge_kernel<NPL>), dim3(blocks), dim3(256), 0, ctx->stream, p.final_keys, p.M, p.S, p.k, d_D, d_I)
+#define MERGE(NPL) hipLaunchKernelGGL((select_merge_kernel<NPL>), dim3(blocks), dim3(256), 0, ctx->stream, p.final_keys, p.M, p.S, p.k, d_D, d_I, \
+                                      p.empty_nan ? NAN : INFINITY)
     if (slots <= 64) MERGE(1);
     else if (slots <= 128) MERGE(2);
     else if (slots <= 256) MERGE(4);

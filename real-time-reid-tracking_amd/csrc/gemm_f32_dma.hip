@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256, BK == 16 ? 3 : 2) void gemm_f32_dma_kernel(con
                 for (int e = 0; e < 16; ++e) {
                     float v = acc[a][b][e];
                     const float rs = rsq[e];
-                    if (METRIC == REID_METRIC_L2) v = sqrtf(fmaxf(l2sqr_of(v, rs, cq), 1e-12f));
+                    if (METRIC == REID_METRIC_L2) v = l2_of_sqr(l2sqr_of(v, rs, cq));
                     else if (METRIC == REID_METRIC_L2SQR) v = l2sqr_of(v, rs, cq);
                     else if (METRIC == REID_METRIC_COS_HALF) v = (1.0f - v / (sqrtf(rs) * cq)) / 2.0f;
                     else if (METRIC == REID_METRIC_COS) v = 1.0f - v / (sqrtf(rs) * cq);

@@ -100,6 +100,7 @@ struct SelectParams {
     const float* col_sq;
     unsigned int* gmin;         // [M][k] group minima of a sample of y as order-preserving keys (null: start from +inf)
     int metric, k, S, index_base, exp_skip;
+    int empty_nan;              // k = 1: the value of a row without a candidate (every distance NaN) is NaN (reid_argmin_rows), else +inf (reid_knn)
     unsigned long long* lists;  // scratch [M][S][SEL_CAP] (k > 1)
     int* counts;                // scratch [M][S]: lengths of the lists when the sweep ends (k > 1)
     unsigned long long* final_keys;   // scratch [M][S]: every segment's arg-min key (k = 1)
@@ -168,6 +169,11 @@ struct Gemm16Params {
 // (gemm_f32.hip, gemm_f32_dma.hip, dist_select.hip's bound pass and sweep).  Left as (rs + cq) - 2 * dot the multiply-add is
 // contracted or not per call site by the compiler, and a bound computed one way need not bound a value computed the other way.
 __device__ __forceinline__ float l2sqr_of(float dot, float rs, float cq) { return fmaf(-2.0f, dot, rs + cq); }
+// REID_METRIC_L2 = sqrt(clamp(|x - y|^2, min = 1e-12)) (reid/losses/utils.py:34).  The clamp keeps NaN as torch.clamp does - fmaxf would
+// return 1e-12 for it, the smallest value the metric takes, and a row with one NaN would be every query's nearest neighbour.  Every
+// other value gets fmaxf's bits.  IEEE 754-2019 maximum (NaN if either operand is): one v_maximum3_f32 on gfx950, where fmaxf was one
+// v_max_f32 - a compare and a select would be two instructions in an epilogue that is VALU-bound beside the other block's MFMAs.
+__device__ __forceinline__ float l2_of_sqr(float v) { return sqrtf(__builtin_elementwise_maximum(v, 1e-12f)); }
 
 // precision 2 range guard (reid_ctx.fault; include/reid_hip.h, reid_ctx_set_precision): every site that writes a split operand
 // [xh | xl'] keeps the largest magnitude it packed - as bits, so that NaN > inf > every finite value - and raises fault[0] when f16

@@ -11,6 +11,9 @@ __device__ __forceinline__ unsigned long long pack_key(float v, int idx) {
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ((unsigned long long)u << 32) | (unsigned int)idx;
 }
+// A NaN distance, of either sign bit, is no candidate (include/reid_hip.h, reid_argmin_rows / reid_knn): it maps to the empty key ~0, which
+// no comparison below ever selects.  (pack_key alone would put a NaN with the sign bit set - what inf - inf and 0 * inf give - before -inf.)
+__device__ __forceinline__ unsigned long long cand_key(float v, int idx) { return v == v ? pack_key(v, idx) : ~0ull; }
 __device__ __forceinline__ float unpack_val(unsigned long long k) {
     unsigned int u = (unsigned int)(k >> 32);
     u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
@@ -35,24 +38,24 @@ __device__ __forceinline__ unsigned long long block_min_u64(unsigned long long v
     return r;
 }
 
-// one block per row; NaNs sort last (their key is the largest)
+// one block per row; a NaN is no candidate: a row without any other value answers idx = -1, val = NaN
 __global__ __launch_bounds__(256) void argmin_rows_kernel(const float* __restrict__ dist, int n, long long ld,
                                                           int32_t* __restrict__ idx, float* __restrict__ val) {
     __shared__ unsigned long long sh[4];
     const float* row = dist + (long long)blockIdx.x * ld;
     unsigned long long best = ~0ull;
     for (int j = threadIdx.x; j < n; j += 256) {
-        const unsigned long long k = pack_key(row[j], j);
+        const unsigned long long k = cand_key(row[j], j);
         best = k < best ? k : best;
     }
     best = block_min_u64(best, sh);
     if (threadIdx.x == 0) {
-        idx[blockIdx.x] = (int32_t)(best & 0xffffffffu);
-        if (val) val[blockIdx.x] = unpack_val(best);
+        idx[blockIdx.x] = best == ~0ull ? -1 : (int32_t)(best & 0xffffffffu);
+        if (val) val[blockIdx.x] = best == ~0ull ? NAN : unpack_val(best);
     }
 }
 
-// k smallest of each row, ascending, ties -> lowest index.
+// k smallest of each row, ascending, ties -> lowest index; a NaN is no candidate (a row short of candidates is padded with +inf / -1).
 // One pass over the row: every thread keeps the FOUR smallest keys of the elements it visits, in registers; then k rounds of
 // "block minimum of the threads' heads", the winner pops its list.  A row's global top-k lies in its threads' top-4 lists unless
 // one thread holds five or more of them (elements are dealt round-robin: probability ~1e-6 per row at k = 20, n = 16 k); a
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     unsigned long long t0 = ~0ull, t1 = ~0ull, t2 = ~0ull, t3 = ~0ull;   // ascending
     int seen = 0;
     for (int j = threadIdx.x; j < n; j += 256, ++seen) {
-        unsigned long long key = pack_key(row[j], j);
+        unsigned long long key = cand_key(row[j], j);   // a NaN: ~0, never below t3
         if (key < t3) {   // insert, keeping the four smallest in order
             unsigned long long a;
             a = key < t0 ? t0 : key; t0 = key < t0 ? key : t0; key = a;
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     for (int r = 0; r < k; ++r) {
         unsigned long long best = ~0ull;
         for (int j = threadIdx.x; j < n; j += 256) {
-            const unsigned long long key = pack_key(row[j], j);
+            const unsigned long long key = cand_key(row[j], j);
             if ((first || key > last) && key < best) best = key;
         }
         best = block_min_u64(best, sh);
