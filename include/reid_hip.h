@@ -262,6 +262,27 @@ int reid_argmin_rows_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_
 int reid_knn(reid_ctx* ctx, const float* xq, int nq, const float* xb, int nb, int d, int k, float* D, int32_t* I);
 int reid_knn_dev(reid_ctx* ctx, const float* d_xq, int nq, const float* d_xb, int nb, int d, int k,
                  float* d_D, int32_t* d_I);
+/* The per-row minimum (evaluate.py:58-63, the top-1 of `score`) with the CANDIDATES from the fp32-class arithmetic of reid_distmat_x3 on
+ * the f16 matrix pipe and the ANSWER in exact fp32 (csrc/select_x3.hip in libreid_hip_select_x3.so, which must lie beside this library -
+ * without the file these calls are REID_ERR_STATE naming it and nothing else is affected).  Contract: inside the domain idx and val are
+ * the bits of reid_argmin_rows* - whatever m, n or the row's position, under all five metrics, ties to the lowest column.  The x3 kernel
+ * keeps per row and column tile the keys below a per-row threshold (no m x n matrix is written), the best 32 are recomputed in exact
+ * fp32 in the exact entry's summation order, and a row is answered from them only when its minimum lies strictly below what any other
+ * column can reach (the threshold minus a bound on the difference of the two arithmetics); every other row is recomputed from all n
+ * columns in exact fp32.  No row is answered approximately.
+ * Domain: that of reid_distmat_x3 - finite operands, |x| < 65504, |y| < 31.98.  A value outside it raises the context's sticky fault word
+ * (bit 0): the host entry returns REID_ERR_STATE and its output is invalid, the _dev entry reports it at the next synchronising call.
+ * The NaN rule of reid_argmin_rows* is not claimed.  m == 0 or n == 0 returns REID_OK; a bad metric is REID_ERR_ARG before anything is
+ * queued.  val / d_val may be NULL.  Entry points of their own: no setting changes reid_argmin_rows* or anything built on it. */
+int reid_argmin_rows_x3(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric, int32_t* idx, float* val);
+int reid_argmin_rows_x3_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int32_t* d_idx,
+                            float* d_val);
+/* Brute-force squared-L2 k-NN (search_raw_array_pytorch / IndexFlatL2.search, reid/faiss_utils.py:56-139) the same way: candidates from
+ * the fp32-class arithmetic, D and I the bits of reid_knn* inside the domain above, whatever nq, nb or the row's position; ties to the
+ * lowest index; a row with nb < k is padded with (I = -1, D = +inf) as reid_knn pads.  1 <= k <= 24, anything else is REID_ERR_ARG before
+ * anything is queued; nq == 0 or nb == 0 returns REID_OK.  Library, domain and fault reporting as reid_argmin_rows_x3*. */
+int reid_knn_x3(reid_ctx* ctx, const float* xq, int nq, const float* xb, int nb, int d, int k, float* D, int32_t* I);
+int reid_knn_x3_dev(reid_ctx* ctx, const float* d_xq, int nq, const float* d_xb, int nb, int d, int k, float* d_D, int32_t* d_I);
 /* k-reciprocal Jaccard re-ranking, compute_jaccard_distance reid/faiss_utils.py:147-244: x fp32[n][d] L2-normalised rows,
  * rank int32[n][k1] neighbour lists or NULL (then reid_knn supplies them, self included), out fp32[n][n].
  * 1 <= k1 <= 64, k1 <= n, k2 >= 1 (k2 == 1 skips the local query expansion, as in the reference). */

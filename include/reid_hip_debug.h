@@ -249,6 +249,13 @@ int reid_debug_select_exp(reid_ctx* ctx, int mode);
 /* Test switch of the large k-NN path (candidates on the f16 matrix pipe + exact fp32 refinement): enable = 0 -> fused fp32 search
  * for every size; force > 0 -> rows whose index is a multiple of it take the exact-row fallback. */
 int reid_debug_knn_wide(reid_ctx* ctx, int enable, int force);
+/* reid_argmin_rows_x3_dev (k = 1, any metric) / reid_knn_x3_dev (metric = REID_METRIC_L2SQR) through the launcher those entries call, on
+ * device operands (d_D [m][k] may be NULL, d_I [m][k]), with the test hook and the statistics they do not expose:
+ * force_fallback_every = f > 0 sends every row whose index is a multiple of f through the exact-row kernel (the hook reid_debug_knn_wide
+ * has); stats = {rows proven, rows recomputed by the exact-row kernel, tile form (1 = 128 x 64, 2 = 128 x 128), candidates per row KK}.
+ * Waits for the stream. */
+int reid_debug_select_x3(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int k, float* d_D,
+                         int32_t* d_I, int force_fallback_every, int32_t* stats);
 /* Switches the s_memtime stamps of the loader-wave conv kernel on / off (out_host [64*8*5] when disabling). */
 int reid_debug_conv_diag(reid_ctx* ctx, int enable, unsigned long long* out_host);
 /* Bare MFMA loop with fragments re-read from LDS (shape 32 = 32x32x16 f16, 16 = 16x16x32 f16). */

@@ -5,6 +5,7 @@
 #include "anysize.h"
 #include "anysize_x3.h"
 #include "distmat_x3.h"
+#include "select_x3.h"
 #include "anysize_front.h"
 #include <cmath>
 #include <dlfcn.h>
@@ -2171,6 +2172,127 @@ extern "C" int reid_distmat_x3(reid_ctx* ctx, const float* x, int m, const float
     HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)m * n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);   // an operand outside the domain: the matrix copied out is invalid
+}
+
+// ------------------------------------------------------------------------------------------------ rank-exact selection, fp32-class candidates
+// reid_argmin_rows_x3* / reid_knn_x3*: the answers of reid_argmin_rows* / reid_knn* bit for bit, with the candidates from the fp32-class
+// arithmetic (libreid_hip_select_x3.so, select_x3.h: candidate lists from the epilogue of the x3 kernel, exact-fp32 refinement, a proof
+// per row, the exact-row kernel where the proof fails).  Entry points of their own: no setting moves an existing call, nothing else calls
+// them.  Norms and padding as in reid_distmat_x3*; workspace names of their own (selx3.*).
+struct SelectX3Api {
+    decltype(&select_x3_ws_bytes) bytes = nullptr;
+    decltype(&select_x3) run = nullptr;
+};
+static int select_x3_api(SelectX3Api** out) {
+    static std::mutex m;
+    static SelectX3Api api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.run) {
+        void* f[2];
+        REID_TRY(open_beside_self("libreid_hip_select_x3.so",
+                                  "arg-min and k-NN with fp32-class candidates (reid_argmin_rows_x3, reid_knn_x3) need", {"select_x3_ws_bytes", "select_x3"},
+                                  f));
+        api.bytes = (decltype(api.bytes))f[0];
+        api.run = (decltype(api.run))f[1];
+    }
+    *out = &api;
+    return REID_OK;
+}
+
+// The launcher of both entries (and of reid_debug_select_x3).  d_D [m][k] may be NULL.  stats (host, may be NULL): waits for the stream and
+// returns {rows proven, rows recomputed, tile form, candidates per row}.
+int select_x3_launch(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int k, float* d_D, int32_t* d_I,
+                     int force_every, int32_t* stats) {
+    SelectX3Api* api;
+    REID_TRY(select_x3_api(&api));
+    const float *xp, *yp;
+    int ldx, ldy;
+    REID_TRY(pad_rows_to(ctx, "selx3.xpad", d_x, m, d, 32, &xp, &ldx));   // whole K steps, 16-byte rows, zero columns
+    REID_TRY(pad_rows_to(ctx, "selx3.ypad", d_y, n, d, 32, &yp, &ldy));
+    float *xx, *yy;
+    int* flags;
+    void* ws;
+    REID_TRY(ctx_ws(ctx, "selx3.xx", (size_t)m * 4, (void**)&xx));
+    REID_TRY(ctx_ws(ctx, "selx3.yy", (size_t)n * 4, (void**)&yy));
+    REID_TRY(ctx_ws(ctx, "selx3.flags", (size_t)m * 4, (void**)&flags));
+    const size_t bytes = api->bytes(m, n);
+    REID_TRY(ctx_ws(ctx, "selx3.ws", bytes, &ws));
+    REID_TRY(launch_row_sqnorm(ctx, xp, m, ldx, ldx, xx));   // the launch of the exact entries: zero columns add nothing to a sum of squares
+    REID_TRY(launch_row_sqnorm(ctx, yp, n, ldy, ldy, yy));
+    int form = 0;
+    prof_begin(ctx, REID_K_SELECT, 2.0 * m * n * d, 4.0 * ((double)m * d + (double)n * d));
+    const hipError_t e = api->run(ctx->stream, xp, m, yp, n, ldx, xx, yy, metric, k, d_D, d_I, ws, bytes, ctx->fault, force_every, flags, &form);
+    prof_end(ctx);
+    if (e != hipSuccess) {
+        reid_set_error("libreid_hip_select_x3.so select_x3 -> %s", hipGetErrorString(e));
+        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+    }
+    if (stats) {
+        std::vector<int> h((size_t)m);
+        HIP_TRY(hipMemcpyAsync(h.data(), flags, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        int redone = 0;
+        for (int v : h) redone += v != 0;
+        stats[0] = m - redone; stats[1] = redone; stats[2] = form; stats[3] = SELECT_X3_KK;
+    }
+    return REID_OK;
+}
+
+extern "C" int reid_argmin_rows_x3_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int32_t* d_idx,
+                                       float* d_val) {
+    ARG_CHECK(ctx && d_x && d_y && d_idx && m >= 0 && n >= 0 && d >= 1);
+    CTX_ENTER(ctx);
+    ARG_CHECK(metric >= REID_METRIC_L2 && metric <= REID_METRIC_DOT);
+    if (m == 0 || n == 0) return REID_OK;
+    return select_x3_launch(ctx, d_x, m, d_y, n, d, metric, 1, d_val, d_idx, 0, nullptr);
+}
+
+extern "C" int reid_argmin_rows_x3(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric, int32_t* idx, float* val) {
+    ARG_CHECK(ctx && x && y && idx && m >= 0 && n >= 0 && d >= 1);
+    CTX_ENTER(ctx);
+    ARG_CHECK(metric >= REID_METRIC_L2 && metric <= REID_METRIC_DOT);
+    if (m == 0 || n == 0) return REID_OK;
+    float *dx, *dy, *d_val;
+    int32_t* d_idx;
+    REID_TRY(ctx_ws(ctx, "selx3.io.x", (size_t)m * d * 4, (void**)&dx));
+    REID_TRY(ctx_ws(ctx, "selx3.io.y", (size_t)n * d * 4, (void**)&dy));
+    REID_TRY(ctx_ws(ctx, "selx3.io.I", (size_t)m * 4, (void**)&d_idx));
+    REID_TRY(ctx_ws(ctx, "selx3.io.D", (size_t)m * 4, (void**)&d_val));
+    HIP_TRY(hipMemcpyAsync(dx, x, (size_t)m * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dy, y, (size_t)n * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(reid_argmin_rows_x3_dev(ctx, dx, m, dy, n, d, metric, d_idx, d_val));
+    HIP_TRY(hipMemcpyAsync(idx, d_idx, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (val) HIP_TRY(hipMemcpyAsync(val, d_val, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);   // an operand outside the domain: what was copied out is invalid
+}
+
+extern "C" int reid_knn_x3_dev(reid_ctx* ctx, const float* d_xq, int nq, const float* d_xb, int nb, int d, int k, float* d_D, int32_t* d_I) {
+    ARG_CHECK(ctx && d_xq && d_xb && d_D && d_I && nq >= 0 && nb >= 0 && d >= 1);
+    CTX_ENTER(ctx);
+    ARG_CHECK(k >= 1 && k <= SELECT_X3_KMAX);
+    if (nq == 0 || nb == 0) return REID_OK;
+    return select_x3_launch(ctx, d_xq, nq, d_xb, nb, d, REID_METRIC_L2SQR, k, d_D, d_I, 0, nullptr);
+}
+
+extern "C" int reid_knn_x3(reid_ctx* ctx, const float* xq, int nq, const float* xb, int nb, int d, int k, float* D, int32_t* I) {
+    ARG_CHECK(ctx && xq && xb && D && I && nq >= 0 && nb >= 0 && d >= 1);
+    CTX_ENTER(ctx);
+    ARG_CHECK(k >= 1 && k <= SELECT_X3_KMAX);
+    if (nq == 0 || nb == 0) return REID_OK;
+    float *dx, *dy, *d_D;
+    int32_t* d_I;
+    REID_TRY(ctx_ws(ctx, "selx3.io.x", (size_t)nq * d * 4, (void**)&dx));
+    REID_TRY(ctx_ws(ctx, "selx3.io.y", (size_t)nb * d * 4, (void**)&dy));
+    REID_TRY(ctx_ws(ctx, "selx3.io.I", (size_t)nq * k * 4, (void**)&d_I));
+    REID_TRY(ctx_ws(ctx, "selx3.io.D", (size_t)nq * k * 4, (void**)&d_D));
+    HIP_TRY(hipMemcpyAsync(dx, xq, (size_t)nq * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dy, xb, (size_t)nb * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(reid_knn_x3_dev(ctx, dx, nq, dy, nb, d, k, d_D, d_I));
+    HIP_TRY(hipMemcpyAsync(D, d_D, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(I, d_I, (size_t)nq * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
 }
 
 // The k smallest distances of every row of x to the rows of y with the selection fused into the distance GEMM

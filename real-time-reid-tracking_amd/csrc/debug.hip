@@ -393,6 +393,17 @@ extern "C" int reid_debug_knn_wide(reid_ctx* ctx, int enable, int force) {
     return REID_OK;
 }
 
+// The selection with fp32-class candidates (libreid_hip_select_x3.so) through the launcher reid_argmin_rows_x3_dev / reid_knn_x3_dev call,
+// on device operands, with the test hook and the statistics those entries do not expose: force_fallback_every > 0 sends every row whose
+// index is a multiple of it through the exact-row kernel; stats = {rows proven, rows recomputed, tile form, candidates per row}.
+extern "C" int reid_debug_select_x3(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int k, float* d_D,
+                                    int32_t* d_I, int force_fallback_every, int32_t* stats) {
+    ARG_CHECK(ctx && d_x && d_y && d_I && stats && m >= 1 && n >= 1 && d >= 1 && force_fallback_every >= 0);
+    ARG_CHECK(metric >= REID_METRIC_L2 && metric <= REID_METRIC_DOT && k >= 1 && k <= 24);
+    CTX_ENTER(ctx);
+    return select_x3_launch(ctx, d_x, m, d_y, n, d, metric, k, d_D, d_I, force_fallback_every, stats);
+}
+
 // One Swin Linear layer on HOST operands through the f16 linear build of gemm_f16.hip, results back on the host (correctness
 // harness: row-position invariance, tests/test_gpu_parity.py).  mode 1 = fp16 storage (operands rounded to f16), 2 = fp32-class
 // (x packed to [xh | xl'], weights to [wh 2^11 | wh | wl'], K = 3 k virtual columns).  flags bit 0 = erf-GELU; bit 1 = f16 output

@@ -522,6 +522,11 @@ int ctx_fault_status(reid_ctx* ctx);
 bool knn_wide_eligible(reid_ctx* ctx, int nq, int nb, int d, int k);
 int knn_wide_dev(reid_ctx* ctx, const float* xp, int nq, const float* yp, int nb, int ld, const float* rs, const float* cq, int k, float* d_D,
                  int32_t* d_I);   // api.hip: REID_OK, or REID_ERR_STATE + message when the fault word is set
+// api.hip: the launcher of reid_argmin_rows_x3* / reid_knn_x3* (libreid_hip_select_x3.so, select_x3.h) on device operands; d_D may be null;
+// force_every > 0: rows whose index is a multiple of it take the exact-row kernel; stats (host, may be null): waits for the stream,
+// then {rows proven, rows recomputed, tile form, candidates per row}
+int select_x3_launch(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int k, float* d_D, int32_t* d_I,
+                     int force_every, int32_t* stats);
 
 // precision 2: largest |w| of the named tensors against the bound their split form allows; returns "" or "name (max |w| = v)"
 inline std::string split_range_violation(const float* blob, const std::map<std::string, std::pair<size_t, size_t>>& tab,

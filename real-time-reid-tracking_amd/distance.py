@@ -45,6 +45,19 @@ def search_raw_array(xb, xq, k, device=0):
     return get_engine(device).knn(_np(xq), _np(xb), k)
 
 
+def nearest_x3(x, y, metric=_ffi.METRIC_L2, device=0):
+    """`nearest` with the candidates from the fp32-class arithmetic on the f16 matrix pipe (reid_argmin_rows_x3): the same indices and
+    values bit for bit, for finite operands with |x| < 65504 and |y| < 31.98 (outside: ReidHipError, status -3)."""
+    return get_engine(device).argmin_rows(_np(x), _np(y), metric, precision="f16x3")
+
+
+def search_raw_array_x3(xb, xq, k, device=0):
+    """`search_raw_array` the same way (reid_knn_x3): the same (D, I) bit for bit, 1 <= k <= 24 (ValueError otherwise, before the device
+    is touched), the domain of `nearest_x3`."""
+    Engine.select_precision_entry("reid_knn", "f16x3", k)
+    return get_engine(device).knn(_np(xq), _np(xb), k, precision="f16x3")
+
+
 class IndexFlatL2:
     """The slice of faiss.IndexFlatL2 the reference uses (reid/faiss_utils.py:138-139,176-181): add + search."""
 

@@ -16,6 +16,7 @@ IMG_H, IMG_W = 256, 128   # Extractor.size = (128, 256) as (W, H), feature_extra
 SIZE_MIN, SIZE_MAX = 32, 512   # input sides of the any-size forward (reid_*_hw, include/reid_hip.h)
 HW_PRECISION_NAMES = {"f32": 0, "fp32": 0, "exact": 0, "f16x3": 2, "fp32-class": 2}   # Engine.set_hw_precision
 DISTMAT_PRECISION_NAMES = {"f32": 0, "f16x3": 2}   # Engine.distmat(precision=): the exact entry, reid_distmat_x3
+SELECT_X3_KMAX = 24                                # Engine.knn(precision="f16x3"): reid_knn_x3's largest k
 
 
 def check_hw(size):
@@ -1183,28 +1184,53 @@ class Engine:
         fn = "reid_distmat_x3_dev" if Engine.distmat_precision_value(precision) == 2 else "reid_distmat_dev"
         check(getattr(self.lib, fn)(self.h, C.c_void_p(d_x), int(m), C.c_void_p(d_y), int(n), int(d), int(metric), C.c_void_p(d_out)))
 
-    def argmin_rows(self, x, y, metric=_ffi.METRIC_L2):
+    @staticmethod
+    def select_precision_entry(name, precision, k=None):
+        """The C entry a selection call reaches: ``name`` for precision None / "f32" (today's call and bits), ``name`` + "_x3" for
+        "f16x3" (candidates from the fp32-class arithmetic, the same answer bit for bit; |x| < 65504, |y| < 31.98, k <= 24).  Any
+        other precision, or a k outside 1 .. 24 with "f16x3", is a ValueError before the device is touched."""
+        if Engine.distmat_precision_value(precision) != 2:
+            return name
+        if k is not None and not (isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= SELECT_X3_KMAX):
+            raise ValueError("knn with precision \"f16x3\" takes 1 <= k <= %d, got %r" % (SELECT_X3_KMAX, k))
+        return name.replace("_dev", "") + "_x3" + ("_dev" if name.endswith("_dev") else "")
+
+    def argmin_rows(self, x, y, metric=_ffi.METRIC_L2, precision=None):
+        fn = Engine.select_precision_entry("reid_argmin_rows", precision)
         x, y = _f32(x), _f32(y)
         idx = np.empty(x.shape[0], np.int32)
         val = np.empty(x.shape[0], np.float32)
-        check(self.lib.reid_argmin_rows(self.h, _ptr(x), x.shape[0], _ptr(y), y.shape[0], x.shape[1], int(metric),
-                                        _ptr(idx), _ptr(val)))
+        check(getattr(self.lib, fn)(self.h, _ptr(x), x.shape[0], _ptr(y), y.shape[0], x.shape[1], int(metric), _ptr(idx), _ptr(val)))
         return idx, val
 
-    def argmin_rows_dev(self, d_x, m, d_y, n, d, metric, d_idx, d_val=None):
-        check(self.lib.reid_argmin_rows_dev(self.h, C.c_void_p(d_x), int(m), C.c_void_p(d_y), int(n), int(d), int(metric),
-                                            C.c_void_p(d_idx), C.c_void_p(d_val or 0)))
+    def argmin_rows_dev(self, d_x, m, d_y, n, d, metric, d_idx, d_val=None, precision=None):
+        fn = Engine.select_precision_entry("reid_argmin_rows_dev", precision)
+        check(getattr(self.lib, fn)(self.h, C.c_void_p(d_x), int(m), C.c_void_p(d_y), int(n), int(d), int(metric),
+                                    C.c_void_p(d_idx), C.c_void_p(d_val or 0)))
 
-    def knn(self, xq, xb, k):
+    def knn(self, xq, xb, k, precision=None):
+        fn = Engine.select_precision_entry("reid_knn", precision, k)
         xq, xb = _f32(xq), _f32(xb)
         D = np.empty((xq.shape[0], k), np.float32)
         I = np.empty((xq.shape[0], k), np.int32)
-        check(self.lib.reid_knn(self.h, _ptr(xq), xq.shape[0], _ptr(xb), xb.shape[0], xq.shape[1], int(k), _ptr(D), _ptr(I)))
+        check(getattr(self.lib, fn)(self.h, _ptr(xq), xq.shape[0], _ptr(xb), xb.shape[0], xq.shape[1], int(k), _ptr(D), _ptr(I)))
         return D, I
 
-    def knn_dev(self, d_xq, nq, d_xb, nb, d, k, d_D, d_I):
-        check(self.lib.reid_knn_dev(self.h, C.c_void_p(d_xq), int(nq), C.c_void_p(d_xb), int(nb), int(d), int(k),
+    def knn_dev(self, d_xq, nq, d_xb, nb, d, k, d_D, d_I, precision=None):
+        fn = Engine.select_precision_entry("reid_knn_dev", precision, k)
+        check(getattr(self.lib, fn)(self.h, C.c_void_p(d_xq), int(nq), C.c_void_p(d_xb), int(nb), int(d), int(k),
                                     C.c_void_p(d_D), C.c_void_p(d_I)))
+
+    def debug_select_x3(self, d_x, m, d_y, n, d, metric, k, d_D, d_I, force_fallback_every=0):
+        """reid_debug_select_x3 on device operands: the launcher of the "f16x3" selection entries with its test hook; returns
+        {"proven", "recomputed", "form", "kk"}."""
+        stats = (C.c_int32 * 4)()
+        fn = _ffi.debug_lib().reid_debug_select_x3
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        check(fn(self.h, C.c_void_p(d_x), int(m), C.c_void_p(d_y), int(n), int(d), int(metric), int(k), C.c_void_p(d_D or 0), C.c_void_p(d_I),
+                 int(force_fallback_every), stats))
+        return dict(zip(("proven", "recomputed", "form", "kk"), (int(v) for v in stats)))
 
     def descriptor_f32_nchw(self, x, flip_tta=True):
         """float32 [n,3,H,W] (normalised by the caller) -> float32 [n, 512 + num_class] retrieval descriptor; sizes as embed_f32_nchw."""
