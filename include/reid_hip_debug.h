@@ -211,6 +211,26 @@ int reid_debug_layernorm(reid_ctx* ctx, int form, const float* x, int t, int c, 
  * cached for its weight buffer first. */
 int reid_debug_ln_linear(reid_ctx* ctx, const float* x, const float* ln_g, const float* ln_b, const float* w, const float* bias, int t, int c,
                          int n, float* out);
+/* swin_linear: one Linear layer, y = act(x [m][k] . w [n][k]^T + bias) + res, through linear() / linear16() of csrc/swin.hip - the
+ * functions every Linear of the Swin trunk and the classifier go through - so a case sees the forward's dispatch, padding and epilogue
+ * (tests/test_gpu_linear.py).  bias [n] and res [m][n] may be null.  The context is put into `precision` for the call and its switches
+ * (f32_conv, lin_x3, f16_lin_256, f16_cfg) pick the kernel.  Operands are prepared as the forward prepares them: precision 0 fp32 as
+ * given; 1 x and w rounded to f16 on the device, w padded with zero rows to a multiple of 64; 2 x packed to [xh | xl'] and the weight
+ * image [wh 2^11 | wh | wl'] built and cached by linear() itself (dropped again before the call returns) - unless flags bit 2 leaves x in
+ * fp32, the classifier's call, which stays on the exact kernel.  flags: bit 0 erf-GELU; bit 1 the residual aliases the output (the rows
+ * of the output buffer hold res when the launch starts, and res32 == out: fc2 and post_proj run so); bit 2 as above.
+ * out_form 0: fp32 rows of ldc floats into `out`; 1 (precision 1, no res): f16 rows of ldc halves into `out16`; 2 (precision 2, packed x,
+ * no res): rows [yh | yl'] of 2 n halves into `out16` as the two raw f16 planes (y = yh + yl' 2^-11 is left to the caller).  ldc >= n in
+ * precision 1 (the qkv row stride of the fp16-storage mode), ldc == n otherwise.
+ * The output comes back WITH its guard: `front` elements (64 floats / 128 halves), then m + 8 rows of ld = ldc (2 n for form 2) elements;
+ * every byte the launch leaves alone is 0xff.  out / out16 hold front + (m + 8) ld elements.
+ * *form = reid_ctx::conv_form of the launch, written by the launchers on the host (0: none was made):
+ *   gemm_f32_dma_kernel<64>   5064320 (<128>: 5128320, K-tiles of 16: 5128160);   gemm_f32_kernel<.., 64 | 128>   6064000 | 6128000;
+ *   gemm_f16_kernel LIN builds   64323, 128323, 256642, 256324;   lin_x3_kernel<128>   7128000.
+ * REID_ERR_ARG with nothing queued for m <= 0, k % 32 != 0 with f16 operands (k % 4 != 0 with fp32 ones), a null output pointer of the
+ * chosen form, a form the precision does not have; else what the launcher returns, else the context's fault status. */
+int reid_debug_swin_linear(reid_ctx* ctx, const float* x, const float* w, const float* bias, const float* res, int m, int n, int k,
+                           int precision, int flags, int out_form, int ldc, float* out, uint16_t* out16, int* form);
 /* swin_sfe: ShadowFeatureExtraction after its first convolution (sfe_norm_kernel + sfe_conv2_fc_kernel with the forward's grids).  c1
  * [n][h1][w1][12]; in_g / in_b [6] InstanceNorm affine of channels 0-5, bn_s / bn_t [6] folded BatchNorm of channels 6-11; c2_w [48][(kh, kw,
  * c) 48], c2_b [48], fc_w [96][48], fc_b [96] -> ab [n][24] (12 scales, 12 shifts) and tok [n][h1 / 2][w1 / 2][96]. */

@@ -2103,6 +2103,7 @@ int launch_lin_x3(reid_ctx* ctx, const Gemm16Params& p0, int kind, double flops,
     }
     prof_begin(ctx, kind, flops, bytes);
     hipLaunchKernelGGL((lin_x3_kernel<128>), dim3(((p.M + 255) / 256) * (p.N / 128)), dim3(256), 0, ctx->stream, p);
+    ctx->conv_form = 7128000;   // reid_ctx::conv_form: host only
     prof_end(ctx);
     LAUNCH_CHECK();
     return REID_OK;

@@ -1489,6 +1489,78 @@ extern "C" int reid_debug_ln_linear(reid_ctx* ctx, const float* x, const float* 
     return ctx_fault_status(ctx);
 }
 
+// One Linear layer through linear() / linear16() of swin.hip (swin_linear_for_test), operands prepared as the forward prepares them
+// (include/reid_hip_debug.h).  flags: bit 0 erf-GELU, bit 1 the residual IS the output buffer (fc2 / post_proj run in place), bit 2
+// precision 2 with x left in fp32 (the classifier's call).  The whole guarded output comes back: front elements, then m + 8 rows of ld.
+extern "C" int reid_debug_swin_linear(reid_ctx* ctx, const float* x, const float* w, const float* bias, const float* res, int m, int n, int k,
+                                      int precision, int flags, int out_form, int ldc, float* out, uint16_t* out16, int* form) {
+    ARG_CHECK(ctx && x && w && form && m > 0 && n > 0 && k > 0 && k % 4 == 0 && precision >= 0 && precision <= 2 && out_form >= 0 && out_form <= 2 &&
+              flags >= 0 && flags < 8);
+    const bool act = flags & 1, alias = flags & 2, x_fp32 = precision != 1 && (precision == 0 || (flags & 4));
+    ARG_CHECK(x_fp32 || k % 32 == 0);
+    ARG_CHECK(out_form == 0 ? out != nullptr : out16 != nullptr);
+    ARG_CHECK(out_form == 0 || (out_form == precision && !x_fp32 && !res));          // f16 rows: fp16 storage; [yh | yl']: fp32-class, packed x
+    ARG_CHECK(ldc >= n && (precision == 1 || ldc == n) && (out_form != 1 || n % 8 != 0 || ldc % 8 == 0));
+    ARG_CHECK((!alias || (res && out_form == 0)) && ((long long)m + 8) * (out_form == 2 ? 2 * (long long)n : ldc) < (1ll << 31));
+    CTX_ENTER(ctx);
+    CtxModes keep(ctx);
+    ctx->precision = precision;
+    typedef _Float16 f16;
+    const int npad = (n + 63) / 64 * 64, ld = out_form == 2 ? 2 * n : ldc;
+    const size_t front = out_form == 0 ? 64 : 128, total = front + (size_t)(m + 8) * ld;
+    float *dx, *dw, *dbias, *dres, *dout = nullptr;
+    f16 *dx16 = nullptr, *dw16 = nullptr, *dout16 = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbgsl.x", x, (size_t)m * k, &dx));
+    REID_TRY(ctx_ws(ctx, "dbgsl.w", (size_t)npad * k * 4, (void**)&dw));
+    HIP_TRY(hipMemsetAsync(dw, 0, (size_t)npad * k * 4, ctx->stream));               // rows n .. npad - 1 of the f16 image are zeros, as reid_swin_load leaves them
+    HIP_TRY(hipMemcpyAsync(dw, w, (size_t)n * k * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(dbg_upload(ctx, "dbgsl.bias", bias, (size_t)n, &dbias));
+    REID_TRY(dbg_upload(ctx, "dbgsl.res", res, (size_t)m * n, &dres));
+    if (out_form == 0) REID_TRY(dbg_output(ctx, "dbgsl.out", total, &dout));
+    else REID_TRY(dbg_output(ctx, "dbgsl.o16", total, &dout16));
+    const float* r = dres;
+    if (alias) {   // the forward's in-place form: the output rows hold the residual when the launch starts
+        HIP_TRY(hipMemcpy2DAsync(dout + front, (size_t)ld * 4, dres, (size_t)n * 4, (size_t)n * 4, m, hipMemcpyDeviceToDevice, ctx->stream));
+        r = dout + front;
+    }
+    const void* wdev = dw;
+    if (precision == 1) {
+        REID_TRY(ctx_ws(ctx, "dbgsl.x16", (size_t)m * k * 2, (void**)&dx16));
+        REID_TRY(ctx_ws(ctx, "dbgsl.w16", (size_t)npad * k * 2, (void**)&dw16));
+        REID_TRY(launch_f32_to_f16(ctx, dx, (size_t)m * k, dx16));
+        REID_TRY(launch_f32_to_f16(ctx, dw, (size_t)npad * k, dw16));
+        wdev = dw16;
+    } else if (!x_fp32) {
+        REID_TRY(ctx_ws(ctx, "dbgsl.x16", (size_t)m * 2 * k * 2, (void**)&dx16));
+        REID_TRY(launch_split_pack(ctx, dx, m, k, dx16));
+    }
+    // linear() caches the split weight image by the weights' address: this harness re-uses its buffer, so it drops the image in front of
+    // the call (what an earlier one left) and behind it
+    auto drop_image = [&]() {
+        auto it = ctx->split_w.find((const void*)dw);
+        if (it == ctx->split_w.end()) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(it->second);
+        ctx->split_w.erase(it);
+    };
+    drop_image();
+    ctx->conv_form = 0;
+    *form = 0;
+    const int st = swin_linear_for_test(ctx, precision == 1, dx, dx16, m, k, wdev, dbias, n, act, r, dout ? dout + front : nullptr,
+                                        dout16 ? dout16 + front : nullptr, ldc);
+    *form = ctx->conv_form;
+    if (st != REID_OK) {   // refused: the uploads above still read the caller's arrays
+        (void)hipStreamSynchronize(ctx->stream);
+        drop_image();
+        return st;
+    }
+    if (dout) REID_TRY(dbg_download(ctx, out, dout, total));
+    else REID_TRY(dbg_download(ctx, (f16*)out16, dout16, total));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    drop_image();
+    return ctx_fault_status(ctx);
+}
+
 // launch_sfe_norm_fc: sfe_norm_kernel + sfe_conv2_fc_kernel with the forward's grids.  c1 [n][h1][w1][12] -> ab [n][24] (12 scales, 12
 // shifts) and tok [n][h1 / 2][w1 / 2][96]
 extern "C" int reid_debug_swin_sfe(reid_ctx* ctx, const float* c1, int n, int h1, int w1, const float* in_g, const float* in_b, const float* bn_s,

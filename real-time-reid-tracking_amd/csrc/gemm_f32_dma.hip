@@ -10,6 +10,7 @@
 // XOR-swizzled 128-byte rows (conflict-free ds_read_b128), one s_waitcnt vmcnt(0) + one raw s_barrier per K-tile.
 // Requirements: K % 32 == 0, 16-byte aligned rows (lda, ldb % 4 == 0); everything else falls back to gemm_f32_kernel.
 #include "reid_internal.h"
+#include "lin_math.h"
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(256, BK == 16 ? 3 : 2) void gemm_f32_dma_kernel(con
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     float v = acc[a][b][e] + sh;
-                    if constexpr (ACT) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));   // nn.GELU() (erf form)
+                    if constexpr (ACT) v = gelu_erf_f32(v);   // nn.GELU() (erf form): one definition for every epilogue (lin_math.h)
                     if constexpr (RES) v += res[e];
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), c_rs, voff, (a * 32 + (e & 3) + 8 * (e >> 2)) * ldc * 4, 0);
                 }
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(256, BK == 16 ? 3 : 2) void gemm_f32_dma_kernel(con
                     }
                     const long long idx = orow * p.ldc + col;
                     float v = acc[a][b][e] + sh;
-                    if (p.act == 1) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+                    if (p.act == 1) v = gelu_erf_f32(v);
                     if (p.residual) v += p.residual[idx];
                     p.C[idx] = v;
                 }
@@ -315,10 +316,13 @@ void launch_epi(reid_ctx* ctx, const GemmParams& p) {
     const double cost64 = ((p.N + 63) / 64) * 64 * 1.12, cost128 = ((p.N + 127) / 128) * 128;
     if (EPI == E_BIAS || p.N <= 64 || cost64 < cost128) {
         hipLaunchKernelGGL((gemm_f32_dma_kernel<64, EPI>), dim3(nmt * ((p.N + 63) / 64)), dim3(256), 0, ctx->stream, p);
+        ctx->conv_form = 5064320;   // which tile ran, for the harnesses (reid_ctx::conv_form: host only)
     } else if (EPI == E_DIST && ctx->f32_dist_bk16) {     // three blocks per CU (see the kernel's header)
         hipLaunchKernelGGL((gemm_f32_dma_kernel<128, EPI, 16>), dim3(nmt * ((p.N + 127) / 128)), dim3(256), 0, ctx->stream, p);
+        ctx->conv_form = 5128160;
     } else {
         hipLaunchKernelGGL((gemm_f32_dma_kernel<128, EPI>), dim3(nmt * ((p.N + 127) / 128)), dim3(256), 0, ctx->stream, p);
+        ctx->conv_form = 5128320;
     }
 }
 

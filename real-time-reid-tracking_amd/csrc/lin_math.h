@@ -1,6 +1,19 @@
-// Arithmetic shared by the f16-operand linear kernels (gemm_f16.hip linear builds, two_linear_f16.hip): one definition, so the
-// fused and the unfused forms of a layer round the same way.
+// Arithmetic shared by the linear kernels (gemm_f16.hip linear builds, two_linear_f16.hip, conv3x3_x3.hip; the exact-fp32 epilogues of
+// gemm_f32_dma.hip and gemm_f32.hip): one definition, so the fused and the unfused forms of a layer round the same way.
 #pragma once
+
+// nn.GELU() (erf form) of the exact-fp32 linears, with the value MATERIALISED before the residual is added to it.  Written in place,
+// 0.5f * v * (1.0f + erff(..)) followed by v += res was contracted per instantiation: the buffer epilogue of gemm_f32_dma_kernel
+// (full 128-row tiles) ended in one v_fmac_f32 - fma(0.5 v, 1 + erf, res), a single rounding - and its element-by-element epilogue (the
+// ragged last tile) and gemm_f32_kernel in v_mul_f32 + v_add_f32, so a row's bits depended on the tile it sat in whenever a launch had
+// both GELU and a residual (tests/test_gpu_linear.py, test_equal_rows_give_equal_bits_in_every_tile_position).  The forward makes no
+// such launch (fc1 has no residual, fc2 no GELU), and without a residual the three sites already compiled to the same instructions:
+// its results are unchanged.
+__device__ __forceinline__ float gelu_erf_f32(float v) {
+    float g = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+    asm("" : "+v"(g));
+    return g;
+}
 
 // nn.GELU() (erf form), x * 0.5 * (1 + erf(x / sqrt 2)), for the fp16-storage mode.  erf by Abramowitz-Stegun 7.1.28,
 // 1 - (1 + a1 z + ... + a6 z^6)^-16, |error| <= 3e-7 - three orders below the f16 rounding of the value it produces.  Every

@@ -235,6 +235,8 @@ int launch_swin_tail(reid_ctx* ctx, const float* x, int n, int ntok, const float
 int swin_loaded_merge(reid_ctx* ctx, int stage, const float* x, int n, int h, int w, float* scratch, float* out);
 int swin_loaded_fuse(reid_ctx* ctx, const float* sfe, float* const* xs, int n, int h1, int w1, float* scratch16, float* a0, float* f3, float* f2,
                      float* f1);
+int swin_linear_for_test(reid_ctx* ctx, int f16_storage, const float* x32, const _Float16* x16, long long m, int k, const void* w,
+                         const float* bias, int n, int act, const float* res, float* out32, _Float16* out16, int ldc);
 // swin.hip: the two stems of the Swin forward, each writing c1 [n][h / 2][w / 2][12] - sfe_conv1_kernel from normalised NCHW images, and
 // swin_crop_front_kernel (libreid_hip_swin_crops.so, swin_crops.h) from uint8 windows; mean_std6 is a host pointer
 int launch_sfe_conv1(reid_ctx* ctx, const float* x, int n, int h, int w, const float* c1_w, const float* c1_b, float* c1);
@@ -506,7 +508,9 @@ struct reid_ctx {
     unsigned long long* conv_diag = nullptr;   // experiments (debug.hip): stamps of the loader-wave conv kernel
     // Which launch the last f16 convolution launcher made, written on the host only (harnesses read it, include/reid_hip_debug.h:
     // reid_debug_conv_layer_f16).  launch_gemm_f16: the tile configuration BN*1000 + BK*10 + NST; launch_conv3x3_f16: BN*10 + split K;
-    // launch_conv3x3_c64_f16: 1 plain, 2 with the fused SE tail.  No kernel sees it and no launch depends on it.
+    // launch_conv3x3_c64_f16: 1 plain, 2 with the fused SE tail.  The dense launchers a Linear layer can reach name themselves too
+    // (reid_debug_swin_linear): launch_epi (gemm_f32_dma.hip) 5000000 + BN * 1000 + BK * 10 (5064320, 5128320, 5128160), launch_bn
+    // (gemm_f32.hip) 6000000 + BN * 1000 (6064000, 6128000), launch_lin_x3 7128000.  No kernel sees it and no launch depends on it.
     int conv_form = 0;
     // precision 2 guards (include/reid_hip.h, reid_ctx_set_precision): the first conv / linear weight of the loaded checkpoint that
     // cannot be split ([wh 2^11 | wh | wl'] needs |w| 2^11 < 65504), empty when all can ...

@@ -1889,6 +1889,19 @@ int swin_loaded_fuse(reid_ctx* ctx, const float* sfe, float* const* xs, int n, i
     }
     return swin_fuse(ctx, *sw, sfe, xs, n, h1, w1, scratch16, a0, f3, f2, f1);
 }
+// linear() / linear16() above on device operands prepared as the forward prepares them: what reid_debug_swin_linear
+// (libreid_hip_debug.so) runs.  f16_storage != 0: linear16 - x16 f16 [m][k], w f16 [n padded to 64][k], out16 (row stride ldc) or out32.
+// Else linear() in the context's precision: x32 fp32 [m][k] or, with x16, the packed [xh | xl'] f16 [m][2k]; w fp32 [n][k]; out32 [m][n]
+// or, with out16, the packed [yh | yl'] f16 [m][2n] (ldc is then n).
+int swin_linear_for_test(reid_ctx* ctx, int f16_storage, const float* x32, const _Float16* x16, long long m, int k, const void* w,
+                         const float* bias, int n, int act, const float* res, float* out32, _Float16* out16, int ldc) {
+    if (f16_storage) return linear16(ctx, x16, m, k, k, (const f16*)w, bias, n, act, res, out16, out32, ldc);
+    if (ldc != n) {
+        reid_set_error("swin_linear_for_test: linear() writes rows of n = %d values (ldc %d)", n, ldc);
+        return REID_ERR_ARG;
+    }
+    return linear(ctx, x32, m, k, (const float*)w, bias, n, act, res, out32, x16, out16);
+}
 
 // The common body: from c1 [n][h / 2][w / 2][12] to the embeddings.  x != nullptr (the float entries): c1 is still to be written, by the
 // stem from NCHW - sfe_conv1_kernel's launch, first in the stem's one profiling bracket, where it has always been.  x == nullptr (the

@@ -1256,6 +1256,26 @@ class Engine:
 
     # ---- the kernels of libreid_hip_anysize.so on host operands (libreid_hip_debug.so; tests/test_gpu_anysize.py).  Each returns its
     # outputs WITH the guard pixel the harness keeps behind them (c more floats, NaN unless a kernel wrote out of bounds).
+    def debug_swin_linear(self, x, w, bias=None, res=None, precision=0, act=False, out_form=0, ldc=None, alias=False, x_fp32=False):
+        """One Linear layer through linear() / linear16() of csrc/swin.hip (reid_debug_swin_linear, include/reid_hip_debug.h): x [m, k],
+        w [n, k], bias [n], res [m, n].  out_form 0 fp32, 1 f16 rows (precision 1), 2 the [yh | yl'] pair (precision 2); ``alias``: the
+        residual is the output buffer; ``x_fp32``: precision 2 with x left unpacked (the classifier's call).  Returns (form, raw, front, ld):
+        the launchers' form code and the WHOLE guarded output as the launch left it - float32 (form 0) or uint16 f16 bits, ``front``
+        guard elements and then m + 8 rows of ``ld`` elements (ldc, or 2 n for form 2), bytes nothing wrote still 0xff."""
+        x, w = _f32(x), _f32(w)
+        (m, k), n = x.shape, w.shape[0]
+        ldc = n if ldc is None else int(ldc)
+        ld, front = (2 * n if out_form == 2 else ldc), (64 if out_form == 0 else 128)
+        raw = np.empty(front + (m + 8) * ld, np.float32 if out_form == 0 else np.uint16)
+        b = None if bias is None else _f32(bias)
+        r = None if res is None else _f32(res)
+        form = C.c_int(0)
+        check(_ffi.debug_lib().reid_debug_swin_linear(
+            self.h, _ptr(x), _ptr(w), _ptr(b), _ptr(r), C.c_int(m), C.c_int(n), C.c_int(k), C.c_int(int(precision)),
+            C.c_int(int(bool(act)) | 2 * int(bool(alias)) | 4 * int(bool(x_fp32))), C.c_int(int(out_form)), C.c_int(ldc),
+            _ptr(raw if out_form == 0 else None), _ptr(None if out_form == 0 else raw), C.byref(form)))
+        return form.value, raw, front, ld
+
     def debug_any_norm(self, x, half, in_gamma, in_beta, bn_scale=None, bn_shift=None):
         x = _f32(x)
         n, hw, c = x.shape
