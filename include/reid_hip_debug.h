@@ -263,6 +263,20 @@ int reid_debug_two_linear_ablate(reid_ctx* ctx, int bits);
 int reid_debug_two_linear(reid_ctx* ctx, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
                           const float* res, int m, int c, int hid, int act, int iters, float* out, float* ms, const float* ln_g,
                           const float* ln_b);
+/* two_linear_form: the same pair as a test harness (tests/test_gpu_two_linear.py): ONE launch through launch_split_pack (packed builds)
+ * and launch_two_linear, the functions the forward calls, in the context's own precision (2, or the launcher refuses) and switches
+ * (swin_two_linear).  Operands as above.  flags: bit 0 erf-GELU; bit 1 the LN build - x stays fp32 and LayerNorm(ln_g, ln_b; both
+ * required, and both null without the bit) runs in the kernel's prologue; bit 2 the forward's aliasing - LN build: ONE device buffer is
+ * x32, res and out (the MLP's call; res must be null, the residual is x); packed build: the output rows hold res when the launch starts
+ * and res == out.  Without bit 2 x, res and out are three buffers.
+ * The output comes back WITH its guard, by the conventions of reid_debug_swin_linear: 64 floats, then m + 8 rows of c floats; every
+ * byte the launch leaves alone is 0xff.  out holds 64 + (m + 8) c floats.  The tile images cached for the harness's weight buffers are
+ * dropped before and after the launch.
+ * Returns REID_ERR_ARG from launch_two_linear's own check (two_linear_supported: precision 2, swin_two_linear, c 96 or 192, hid a
+ * multiple of 32 up to 4 c) with the untouched output copied back; else the context's fault status - REID_ERR_STATE when the launch
+ * raised the range guard of the hidden split (|h| >= 65504 or NaN) or of the normalised input, the output still copied back. */
+int reid_debug_two_linear_form(reid_ctx* ctx, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                               const float* res, int m, int c, int hid, int flags, const float* ln_g, const float* ln_b, float* out);
 /* Experiment switch of the fused distance + selection kernel: 0 product behaviour, 1 / 2 skip phases (INCOMPLETE results: timing
  * only), 4 print candidate-list statistics. */
 int reid_debug_select_exp(reid_ctx* ctx, int mode);

@@ -990,6 +990,62 @@ extern "C" int reid_debug_two_linear(reid_ctx* ctx, const float* x, const float*
     return REID_OK;
 }
 
+// The same pair as a TEST harness (tests/test_gpu_two_linear.py), by the conventions of reid_debug_swin_linear below: one launch through
+// launch_split_pack (packed builds) + launch_two_linear in the context's own precision and switches, a guarded output returned whole,
+// the tile images of the harness's weight buffers dropped in front of the launch, the context's fault status as the result.
+// flags: bit 0 erf-GELU; bit 1 the LN build (x stays fp32, LayerNorm(ln_g, ln_b) in the kernel's prologue); bit 2 the forward's aliasing -
+// LN build: ONE buffer is x32, res and out (res must be null: the residual is x); packed build: the output rows hold res and res == out.
+extern "C" int reid_debug_two_linear_form(reid_ctx* ctx, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                                          const float* res, int m, int c, int hid, int flags, const float* ln_g, const float* ln_b, float* out) {
+    ARG_CHECK(ctx && x && w1 && b1 && w2 && b2 && out && m > 0 && c > 0 && c % 8 == 0 && hid > 0 && flags >= 0 && flags < 8);
+    const bool act = flags & 1, ln = flags & 2, alias = flags & 4;
+    ARG_CHECK(ln ? (ln_g && ln_b) : (!ln_g && !ln_b));
+    ARG_CHECK(ln && alias ? !res : res != nullptr);
+    ARG_CHECK(((long long)m + 8) * c < (1ll << 31) && (long long)hid * c < (1ll << 29));
+    CTX_ENTER(ctx);
+    typedef _Float16 f16;
+    const size_t front = 64, nx = (size_t)m * c, total = front + (size_t)(m + 8) * c;
+    float *dx, *dw1, *dw2, *db1, *db2, *dres, *dg, *dbt, *dout;
+    f16* a16 = nullptr;
+    REID_TRY(dbg_upload(ctx, "dbg2f.x", x, nx, &dx));
+    REID_TRY(dbg_upload(ctx, "dbg2f.w1", w1, (size_t)hid * c, &dw1));
+    REID_TRY(dbg_upload(ctx, "dbg2f.w2", w2, (size_t)hid * c, &dw2));
+    REID_TRY(dbg_upload(ctx, "dbg2f.b1", b1, (size_t)hid, &db1));
+    REID_TRY(dbg_upload(ctx, "dbg2f.b2", b2, (size_t)c, &db2));
+    REID_TRY(dbg_upload(ctx, "dbg2f.res", res, nx, &dres));
+    REID_TRY(dbg_upload(ctx, "dbg2f.lng", ln_g, (size_t)c, &dg));
+    REID_TRY(dbg_upload(ctx, "dbg2f.lnb", ln_b, (size_t)c, &dbt));
+    REID_TRY(dbg_output(ctx, "dbg2f.out", total, &dout));
+    float* o = dout + front;
+    const float *r = dres, *x32 = dx;
+    if (alias) {   // the output rows hold the residual when the launch starts; the LN build reads its input there too
+        HIP_TRY(hipMemcpyAsync(o, ln ? dx : dres, nx * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        r = o;
+        if (ln) x32 = o;
+    }
+    auto drop_images = [&]() {   // cached by blob address + 1 (launch_two_linear): this harness re-uses its buffers
+        for (const void* key : {(const void*)((const char*)dw1 + 1), (const void*)((const char*)dw2 + 1)}) {
+            auto it = ctx->split_w.find(key);
+            if (it == ctx->split_w.end()) continue;
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(it->second);
+            ctx->split_w.erase(it);
+        }
+    };
+    drop_images();
+    int st = REID_OK;
+    if (!ln) {
+        REID_TRY(ctx_ws(ctx, "dbg2f.a16", nx * 2 * 2, (void**)&a16));
+        st = launch_split_pack(ctx, dx, m, c, a16);
+    }
+    if (st == REID_OK) st = launch_two_linear(ctx, a16, m, c, hid, dw1, db1, dw2, db2, act, r, o, ln ? x32 : nullptr, dg, dbt);
+    // a refusal returns the launcher's code - with the output as it stands, so that the caller sees that nothing was written
+    REID_TRY(dbg_download(ctx, out, dout, total));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    drop_images();
+    return st != REID_OK ? st : ctx_fault_status(ctx);
+}
+
 // ------------------------------------------------------------------------------------------------ loop-back communicator (tests)
 // Several contexts of THIS process on ONE device act as the ranks of a job: every collective of csrc/comm.hip
 // (reid_allgather_dev and what is built on it - ragged row gathers, reid_frame_gather, reid_knn_gallery_sharded_dev -

@@ -1276,6 +1276,26 @@ class Engine:
             _ptr(raw if out_form == 0 else None), _ptr(None if out_form == 0 else raw), C.byref(form)))
         return form.value, raw, front, ld
 
+    def debug_two_linear_form(self, x, w1, b1, w2, b2, res=None, act=False, ln=None, alias=False):
+        """The fused pair of linears of csrc/two_linear_f16.hip in one launch (reid_debug_two_linear_form, include/reid_hip_debug.h):
+        out = res + w2 . act(w1 . [LN](x) + b1) + b2 with x / res [m, c], w1 [hid, c], w2 [c, hid], in the context's own precision (2, or
+        the launcher refuses).  ``ln`` = (gamma, beta): the LN build (x fp32 through the kernel's prologue); ``alias``: the forward's
+        aliasing - LN build: one buffer is x, res and out (``res`` must be None); packed build: res is the output rows.  Returns
+        (status, raw, front): the call's status WITHOUT raising (0, -1 a refusal, -3 the range guard; the message stays in
+        reid_last_error) and the WHOLE guarded output, ``front`` floats and then m + 8 rows of c, bytes nothing wrote still 0xff."""
+        x, w1, w2 = _f32(x), _f32(w1), _f32(w2)
+        (m, c), hid = x.shape, w1.shape[0]
+        if w1.shape != (hid, c) or w2.shape != (c, hid):
+            raise ValueError("debug_two_linear_form: operand shapes")
+        front = 64
+        raw = np.empty(front + (m + 8) * c, np.float32)
+        r = None if res is None else _f32(res)
+        g, b = (None, None) if ln is None else (_f32(ln[0]), _f32(ln[1]))
+        st = _ffi.debug_lib().reid_debug_two_linear_form(
+            self.h, _ptr(x), _ptr(w1), _ptr(_f32(b1)), _ptr(w2), _ptr(_f32(b2)), _ptr(r), C.c_int(m), C.c_int(c), C.c_int(hid),
+            C.c_int(int(bool(act)) | 2 * int(ln is not None) | 4 * int(bool(alias))), _ptr(g), _ptr(b), _ptr(raw))
+        return int(st), raw, front
+
     def debug_any_norm(self, x, half, in_gamma, in_beta, bn_scale=None, bn_shift=None):
         x = _f32(x)
         n, hw, c = x.shape
