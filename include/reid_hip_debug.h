@@ -309,6 +309,16 @@ int reid_debug_knn_merge(reid_ctx* ctx, const float* Dall, const int32_t* Iall, 
 int reid_debug_comm_loopback(reid_ctx** ctxs, int world);
 /* What a wave that stages data can issue beside the other wave's back-to-back v_mfma_f32_32x32x2_f32 (microbench.hip). */
 int reid_debug_coissue(reid_ctx* ctx, int mode, int iters, int roles, double* cyc_mfma_wave, double* cyc_other_wave);
+/* The two kernels of the 256 x 128 descriptor entries (csrc/postproc.hip; tests/test_gpu_postproc.py), each through the launcher
+ * descriptor_dev calls, on host operands.  Every output carries ONE guard row behind its last row, preset to 0xff bytes with the rest (what
+ * the launch leaves alone reads as NaN); each call returns the context's fault status.
+ *   descriptor  e1 / e2 [n][de], l1 / l2 [n][dl] -> out [(n + 1)(de + dl)]: row = cat(e1 / max(|e1|, 1e-12), l1 / max(|l1|, 1e-12)); with a
+ *               second view (e2 and l2, both or neither NULL) the mean of the two views' rows, divided by max(its norm, 1e-12).  A single
+ *               view is not renormalised.
+ *   flip_w      x [rows][w] -> y [(rows + 1) w]: every row with its columns reversed. */
+int reid_debug_descriptor(reid_ctx* ctx, const float* e1, const float* l1, const float* e2, const float* l2, int n, int de, int dl,
+                          float* out);
+int reid_debug_flip_w(reid_ctx* ctx, const float* x, long long rows, int w, float* y);
 
 #ifdef __cplusplus
 }

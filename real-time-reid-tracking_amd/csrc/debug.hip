@@ -1743,3 +1743,38 @@ extern "C" int reid_debug_bank_cost96(reid_ctx* ctx, reid_bank* bank, const int3
         }
     return ctx_fault_status(ctx);
 }
+
+// ------------------------------------------------------------------------------------------------ post-processing (tests/test_gpu_postproc.py)
+// descriptor_kernel through launch_descriptor, the launch the descriptor entries make, on host operands: e1 / e2 [n][de], l1 / l2 [n][dl],
+// e2 and l2 both NULL for a single view -> out [(n + 1)(de + dl)]: n rows and ONE guard row behind them, preset to 0xff bytes with the rest.
+extern "C" int reid_debug_descriptor(reid_ctx* ctx, const float* e1, const float* l1, const float* e2, const float* l2, int n, int de, int dl,
+                                     float* out) {
+    ARG_CHECK(ctx && e1 && l1 && out && n >= 1 && de >= 1 && dl >= 1 && (e2 == nullptr) == (l2 == nullptr));
+    CTX_ENTER(ctx);
+    const size_t d = (size_t)de + dl, no = ((size_t)n + 1) * d;
+    float *d1, *dl1, *d2, *dl2, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgp.e1", e1, (size_t)n * de, &d1));
+    REID_TRY(dbg_upload(ctx, "dbgp.l1", l1, (size_t)n * dl, &dl1));
+    REID_TRY(dbg_upload(ctx, "dbgp.e2", e2, (size_t)n * de, &d2));
+    REID_TRY(dbg_upload(ctx, "dbgp.l2", l2, (size_t)n * dl, &dl2));
+    REID_TRY(dbg_output(ctx, "dbgp.out", no, &dout));
+    REID_TRY(launch_descriptor(ctx, d1, dl1, d2, dl2, n, de, dl, dout));
+    REID_TRY(dbg_download(ctx, out, dout, no));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// flip_w_nchw_kernel through launch_flip_w_nchw (the mirrored view of the 256 x 128 descriptor entries), on host operands: x [rows][w] ->
+// y [(rows + 1) w]: the mirrored rows and ONE guard row behind them, preset to 0xff bytes with the rest.
+extern "C" int reid_debug_flip_w(reid_ctx* ctx, const float* x, long long rows, int w, float* y) {
+    ARG_CHECK(ctx && x && y && rows >= 1 && w >= 1);
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)rows * w;
+    float *dx, *dy;
+    REID_TRY(dbg_upload(ctx, "dbgp.x", x, nx, &dx));
+    REID_TRY(dbg_output(ctx, "dbgp.y", nx + w, &dy));
+    REID_TRY(launch_flip_w_nchw(ctx, dx, rows, w, dy));
+    REID_TRY(dbg_download(ctx, y, dy, nx + w));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}

@@ -6,7 +6,9 @@
 //     The reference inverts a 1263 x 1263 matrix per camera with LAPACK on the CPU.  Here everything stays a GEMM on the
 //     fp32 MFMA kernel: the Gram matrix, then Newton-Schulz  X <- X (2I - A X)  from X0 = I / ||A||_inf (A is symmetric
 //     positive definite with eigenvalues in [n la, ||A||_inf], so the iteration converges quadratically from the first step
-//     and every iterate is a polynomial in A, i.e. symmetric: no transposes), then the projection GEMM.
+//     and every iterate is a polynomial in A, i.e. symmetric: no transposes), then the projection GEMM and two rounds of
+//     residual correction on the projected rows (4 more GEMMs of n_c x d x d), which hold the result to an fp32 LAPACK
+//     inverse's accuracy up to condition number 3e4 (tests/test_gpu_postproc.py).
 #include "reid_internal.h"
 #include "pil_launch.h"
 #include <string.h>
@@ -151,6 +153,11 @@ __global__ void symmetrize_kernel(float* __restrict__ x, int dp) {
         x[(long long)c * dp + r] = m;
     }
 }
+// out = a + s * b (s = -1: the residual C - Y A of the projected rows; s = 1: the correction added to them); out may be a or b
+__global__ void add_scaled_kernel(const float* a, const float* b, float s, long long total, float* out) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x)
+        out[i] = a[i] + s * b[i];
+}
 // out rows (normalised with torch.norm semantics: plain division) scattered back to x[idx[r]][:d]
 __global__ __launch_bounds__(256) void normalize_scatter_kernel(const float* __restrict__ y, const int32_t* __restrict__ idx,
                                                                 int d, int dp, float* __restrict__ x) {
@@ -179,6 +186,22 @@ int gemm_nt_dev(reid_ctx* ctx, const float* a, int m, const float* b, int n, int
 }
 
 }  // namespace
+
+// descriptor_kernel, one block per row: e1 / e2 [n][de], l1 / l2 [n][dl] (e2 and l2 both nullptr: a single view) -> out [n][de + dl]
+int launch_descriptor(reid_ctx* ctx, const float* e1, const float* l1, const float* e2, const float* l2, int n, int de, int dl, float* out) {
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * (de + dl) * 4.0 * (e2 ? 3 : 2));
+    hipLaunchKernelGGL(descriptor_kernel, dim3(n), dim3(256), 0, ctx->stream, e1, l1, e2, l2, de, dl, out);
+    prof_end(ctx);
+    LAUNCH_CHECK();
+    return REID_OK;
+}
+
+// flip_w_nchw_kernel: y [rows][w] = x [rows][w] with its columns reversed
+int launch_flip_w_nchw(reid_ctx* ctx, const float* x, long long rows, int w, float* y) {
+    hipLaunchKernelGGL(flip_w_nchw_kernel, dim3(grid_for(rows * w)), dim3(256), 0, ctx->stream, x, rows, w, y);
+    LAUNCH_CHECK();
+    return REID_OK;
+}
 
 // x: [n][3][256][128] fp32 already normalised by the caller's transform (the evaluation script uses ImageNet mean/std,
 // data_transforms.py:56-130); out: [n][512 + num_class].  flip_tta != 0 averages the descriptor of the mirrored image.
@@ -215,11 +238,7 @@ static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, 
                 REID_TRY(se_any_run_nchw(ctx, d_x + (size_t)i * img, m, h, w, 1, e2 + (size_t)i * de, l2 + (size_t)i * nc));
             }
         }
-        prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * (de + nc) * 4.0 * (flip_tta ? 3 : 2));
-        hipLaunchKernelGGL(descriptor_kernel, dim3(n), dim3(256), 0, ctx->stream, e1, l1, e2, l2, de, nc, d_out);
-        prof_end(ctx);
-        LAUNCH_CHECK();
-        return REID_OK;
+        return launch_descriptor(ctx, e1, l1, e2, l2, n, de, nc, d_out);
     }
     REID_TRY(reid_embed_f32_nchw_dev(ctx, d_x, n, e1, l1));
     if (flip_tta) {
@@ -230,18 +249,12 @@ static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, 
         for (int i = 0; i < n; i += chunk) {
             const int m = n - i < chunk ? n - i : chunk;
             const long long rows = (long long)m * 3 * 256;
-            hipLaunchKernelGGL(flip_w_nchw_kernel, dim3(grid_for(rows * 128)), dim3(256), 0, ctx->stream, d_x + (size_t)i * img, rows,
-                               128, xf);
-            LAUNCH_CHECK();
+            REID_TRY(launch_flip_w_nchw(ctx, d_x + (size_t)i * img, rows, 128, xf));
             REID_TRY(before_view(1, i, m));
             REID_TRY(reid_embed_f32_nchw_dev(ctx, xf, m, e2 + (size_t)i * de, l2 + (size_t)i * nc));
         }
     }
-    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * (de + nc) * 4.0 * (flip_tta ? 3 : 2));
-    hipLaunchKernelGGL(descriptor_kernel, dim3(n), dim3(256), 0, ctx->stream, e1, l1, e2, l2, de, nc, d_out);
-    prof_end(ctx);
-    LAUNCH_CHECK();
-    return REID_OK;
+    return launch_descriptor(ctx, e1, l1, e2, l2, n, de, nc, d_out);
 }
 
 // the debug switch anysize_force belongs to the reid_*_hw entries: the entries without a size keep the 256 x 128 forward whatever it says
@@ -388,6 +401,9 @@ extern "C" int reid_cam_debias_dev(reid_ctx* ctx, float* d_x, const int32_t* cam
     REID_TRY(ctx_ws(ctx, "cd.X2", (size_t)dp * dp * 4, (void**)&X2));
     REID_TRY(ctx_ws(ctx, "cd.rowabs", (size_t)dp * 4, (void**)&rowabs));
     REID_TRY(ctx_ws(ctx, "cd.alpha", 16, (void**)&alpha));
+    float *res, *corr;
+    REID_TRY(ctx_ws(ctx, "cd.res", max_ni * dp * 4, (void**)&res));
+    REID_TRY(ctx_ws(ctx, "cd.corr", max_ni * dp * 4, (void**)&corr));
     hipStream_t st = ctx->stream;
     size_t off = 0;
     std::vector<int32_t> flat;
@@ -417,6 +433,7 @@ extern "C" int reid_cam_debias_dev(reid_ctx* ctx, float* d_x, const int32_t* cam
         // the residual no longer halves and keep the better of the last two iterates.
         float *xa = X, *xb = X2;
         float r_prev = INFINITY;
+        bool stopped = false;   // the rule below ended the iteration: xa is the inverse to fp32 accuracy (not when `iters` ran out first)
         for (int it = 0; it < iters; ++it) {
             REID_TRY(gemm_nt_dev(ctx, A, dp, xa, dp, dp, T));                        // T = A X   (X symmetric)
             HIP_TRY(hipMemsetAsync(alpha + 1, 0, 4, st));
@@ -432,17 +449,33 @@ extern "C" int reid_cam_debias_dev(reid_ctx* ctx, float* d_x, const int32_t* cam
             }
             if (!(r < r_prev)) {            // got worse (or NaN): the previous iterate is the answer
                 float* t = xa; xa = xb; xb = t;
+                stopped = true;
                 break;
             }
             // quadratic phase (r_prev < 1e-2 would square to < 1e-4) but no longer halving: noise floor, keep the current iterate
-            if ((r_prev < 1e-2f && r > 0.5f * r_prev) || r < 1e-6f) break;
+            if ((r_prev < 1e-2f && r > 0.5f * r_prev) || r < 1e-6f) {
+                stopped = true;
+                break;
+            }
             r_prev = r;
             REID_TRY(gemm_nt_dev(ctx, xa, dp, T2, dp, dp, xb));                      // X' = X (2I - A X)
             hipLaunchKernelGGL(symmetrize_kernel, dim3(grid_for((long long)dp * dp)), dim3(256), 0, st, xb, dp);
             LAUNCH_CHECK();
             float* t = xa; xa = xb; xb = t;
         }
-        REID_TRY(gemm_nt_dev(ctx, cen, ni, xa, dp, dp, cur));                        // (X_c - mean) P^T, P symmetric
+        REID_TRY(gemm_nt_dev(ctx, cen, ni, xa, dp, dp, cur));                        // Y = (X_c - mean) P^T, P symmetric
+        // Two rounds of residual correction on the projected rows, Y <- Y + (C - Y A) X with C the centred rows.  X carries entries of
+        // size 1 / (n la) while C lies mostly in the well-conditioned subspace of A, so C X alone loses kappa^2 eps to cancellation; the
+        // residual C - Y A is small and computed from A itself, which brings Y to what an fp32 LAPACK inverse gives (kappa eps).  Only
+        // behind a finished inverse: on an iterate cut short by `iters` a round would be one more Newton-Schulz step in disguise.
+        for (int round = 0; stopped && round < 2; ++round) {
+            REID_TRY(gemm_nt_dev(ctx, cur, ni, A, dp, dp, res));                     // Y A   (A symmetric)
+            hipLaunchKernelGGL(add_scaled_kernel, dim3(grid_for(tot)), dim3(256), 0, st, cen, res, -1.0f, tot, res);
+            LAUNCH_CHECK();
+            REID_TRY(gemm_nt_dev(ctx, res, ni, xa, dp, dp, corr));                   // (C - Y A) X
+            hipLaunchKernelGGL(add_scaled_kernel, dim3(grid_for(tot)), dim3(256), 0, st, cur, corr, 1.0f, tot, cur);
+            LAUNCH_CHECK();
+        }
         hipLaunchKernelGGL(normalize_scatter_kernel, dim3(ni), dim3(256), 0, st, cur, idx, d, dp, d_x);
         LAUNCH_CHECK();
     }
@@ -450,7 +483,7 @@ extern "C" int reid_cam_debias_dev(reid_ctx* ctx, float* d_x, const int32_t* cam
 }
 
 extern "C" int reid_cam_debias(reid_ctx* ctx, float* x, const int32_t* cams, int n, int d, float la, int iters) {
-    ARG_CHECK(ctx && x && cams && n >= 1 && d >= 1);
+    ARG_CHECK(ctx && x && cams && n >= 1 && d >= 1 && la > 0.f);
     CTX_GUARD(ctx);
     float* dx;
     REID_TRY(ctx_ws(ctx, "cd.x", (size_t)n * d * 4, (void**)&dx));

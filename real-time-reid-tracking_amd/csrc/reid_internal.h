@@ -327,6 +327,10 @@ int launch_rank_eval(reid_ctx*, const float* score, int nq, int ng, long long ld
                      const long long* qc, const long long* gl, const long long* gc, int32_t* cmc_sum, double* ap,
                      int32_t* valid);
 int launch_diou_cost(reid_ctx*, const double* tracks, int t, const double* dets, int m, double* out, int as_cost);
+// evaluation-script post-processing (postproc.hip): the retrieval descriptor of e1 / e2 [n][de], l1 / l2 [n][dl] (e2 and l2 both nullptr: a
+// single view, not renormalised) -> out [n][de + dl], and the column mirror of x [rows][w]
+int launch_descriptor(reid_ctx*, const float* e1, const float* l1, const float* e2, const float* l2, int n, int de, int dl, float* out);
+int launch_flip_w_nchw(reid_ctx*, const float* x, long long rows, int w, float* y);
 
 // ------------------------------------------------------------------------------------------------
 struct ProfSlot {

@@ -1322,6 +1322,31 @@ class Engine:
         check(_ffi.debug_lib().reid_debug_any_gem(self.h, n, hw, c, C.c_float(p), _ptr(x), _ptr(scale), _ptr(shift), _ptr(gem), _ptr(emb)))
         return gem, emb
 
+    def debug_descriptor(self, e1, l1, e2=None, l2=None):
+        """descriptor_kernel through the launcher the descriptor entries call (reid_debug_descriptor): e1 / e2 [n, de], l1 / l2 [n, dl], the
+        second view both or neither.  Returns (out [n, de + dl], guard [de + dl] - the row behind the output, NaN unless the kernel
+        wrote out of bounds)."""
+        e1, l1 = _f32(e1), _f32(l1)
+        (n, de), dl = e1.shape, l1.shape[1]
+        if l1.shape[0] != n or (e2 is None) != (l2 is None):
+            raise ValueError("debug_descriptor: e1 [n, de], l1 [n, dl] and both or neither of e2, l2")
+        e2, l2 = (None, None) if e2 is None else (_f32(e2), _f32(l2))
+        if e2 is not None and (e2.shape != e1.shape or l2.shape != l1.shape):
+            raise ValueError("debug_descriptor: the second view must have the first one's shapes")
+        d = de + dl
+        out = np.empty((n + 1) * d, np.float32)
+        check(_ffi.debug_lib().reid_debug_descriptor(self.h, _ptr(e1), _ptr(l1), _ptr(e2), _ptr(l2), n, de, dl, _ptr(out)))
+        return out[:-d].reshape(n, d), out[-d:]
+
+    def debug_flip_w(self, x):
+        """flip_w_nchw_kernel through the launcher the 256 x 128 descriptor entries call (reid_debug_flip_w): x [rows, w].  Returns
+        (y [rows, w], guard [w])."""
+        x = _f32(x)
+        rows, w = x.shape
+        y = np.empty((rows + 1) * w, np.float32)
+        check(_ffi.debug_lib().reid_debug_flip_w(self.h, _ptr(x), C.c_longlong(rows), w, _ptr(y)))
+        return y[:-w].reshape(rows, w), y[-w:]
+
     def debug_any_conv(self, x, wt, stride, hw_precision=2, scale=None, shift=None, res=None, relu=False, relu_from=0):
         """One trunk convolution of the any-size forward (reid_debug_any_conv): x [n, h, w, cin], wt [cout, r, r, cin] with r = 3 (pad 1) or
         1 (pad 0).  Returns (out [n, ho, wo, cout], guard [cout] - the row behind the last pixel, NaN unless the kernel wrote out of
