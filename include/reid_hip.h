@@ -367,6 +367,40 @@ int reid_descriptor_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int
 int reid_descriptor_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out);
 int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
                                  int out_w, const float* mean_std6, int flip_tta, float* out);
+/* ---- the evaluation chain's shifted mirrored view and attribute distance --------------------- */
+/* For --backbone seres18 / cares18 the script's second view is get_inference_transforms_flipped(..., strong_inference=True)
+ * (reid/image_reid_inference.py:179-181, reid/data_transforms.py:130-191): Resize -> RandomHorizontalFlip(p=1) -> Pad(10) ->
+ * RandomCrop((H, W)) -> ToTensor -> Normalize - the mirrored image shifted by up to +-pad pixels on each axis over a black border, which
+ * Normalize turns into (0 - mean) / std.  The entries below are reid_descriptor_f32_nchw_hw* / reid_descriptor_images_u8_hw with
+ * flip_tta = 1 and that second view: with (top, left) = shift_tl[2 i], shift_tl[2 i + 1] of image i (a HOST int32 [n][2], in the _dev
+ * entry too; RandomCrop.get_params' (i, j)),
+ *     sy = oy + top - pad;  sx = ox + left - pad;   view[c][oy][ox] = (0 <= sy < h && 0 <= sx < w) ? x[c][sy][w - 1 - sx] : fill3[c],
+ * exactly crop(pad(mirror(x))); (top, left) == (pad, pad) is the plain mirror and then the bits of flip_tta = 1.  Size, architecture,
+ * precision, hw_precision, pending side indices (they serve both views), pass sizes and every refusal are those of the entries without
+ * _shift: (256, 128) runs every architecture in every mode, another size seres18_ibn under the hw_precision rule.  The view is pure data
+ * movement (shift_mirror_nchw_kernel of libreid_hip_eval_links.so, which must lie beside this library - without the file these calls are
+ * REID_ERR_STATE naming it, before anything is queued, and nothing else is affected): at 256 x 128 it writes the workspace the plain
+ * mirror is written to, at another size a shifted copy of the pass on which the any-size forward runs unmirrored.
+ * reid_descriptor_images_u8_shift pads with the normalisation table's entry for pixel value 0 per channel, (0 / 255 - mean) / std in the
+ * table's own arithmetic: Pad(fill=0) on the 8-bit image followed by ToTensor + Normalize.
+ * REID_ERR_ARG before anything is queued: fill3 == NULL (float entries), pad outside 0 .. 32, a shift outside [0, 2 pad] (the message
+ * names the image index). */
+int reid_descriptor_f32_nchw_shift(reid_ctx* ctx, const float* x, int n, int h, int w, const int32_t* shift_tl, int pad, const float* fill3,
+                                   float* out);
+int reid_descriptor_f32_nchw_shift_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, const int32_t* shift_tl, int pad,
+                                       const float* fill3, float* d_out);
+int reid_descriptor_images_u8_shift(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                    int out_w, const float* mean_std6, const int32_t* shift_tl, int pad, float* out);
+/* For --dataset market1501 the script adds get_attribute_dist(labels, path) to the Jaccard matrix before DBSCAN
+ * (reid/image_reid_inference.py:276-289, reid/tricks/additional_market_attributes.py:11-38): euclidean_dist (reid/losses/utils.py:21-35)
+ * of the normalised 30-wide attribute rows with themselves.  In place on inout fp32 [n][n], a fp32 [n][d], 1 <= d <= 32:
+ *     inout[i][j] += sqrt(max(s_i + s_j - 2 a_i.a_j, 1e-12)),   s_i the squared norm of row i in fp32,
+ * one read and one write of the matrix and no second matrix (dist_add_l2_kernel of libreid_hip_eval_links.so; without the file
+ * REID_ERR_STATE naming it).  The dot product and the norms are ascending-k fp32 FMA chains and s_i + s_j one fp32 add, so the term is
+ * symmetric bit for bit.  n == 0 is REID_OK, d outside 1 .. 32 REID_ERR_ARG; a NaN in a propagates, as in reid_distmat (the clamp keeps
+ * it).  d_inout must be 16-byte aligned. */
+int reid_distmat_add_l2(reid_ctx* ctx, const float* a, int n, int d, float* inout);
+int reid_distmat_add_l2_dev(reid_ctx* ctx, const float* d_a, int n, int d, float* d_inout);
 /* diminish_camera_bias, reid/inference_utils.py:5-15, in place on x fp32 [n][d]: per camera id c (cams is a host int32[n],
  * ids >= 0) rows X_c <- normalize_rows((X_c - mean X_c) inverse(X_c^T X_c + n_c*la*I)^T).  The inverse is a Newton-Schulz
  * iteration of fp32 GEMMs that stops when the residual reaches the fp32 noise floor (iters = upper bound, <= 0: 40); behind a

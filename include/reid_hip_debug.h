@@ -319,6 +319,15 @@ int reid_debug_coissue(reid_ctx* ctx, int mode, int iters, int roles, double* cy
 int reid_debug_descriptor(reid_ctx* ctx, const float* e1, const float* l1, const float* e2, const float* l2, int n, int de, int dl,
                           float* out);
 int reid_debug_flip_w(reid_ctx* ctx, const float* x, long long rows, int w, float* y);
+/* The two kernels of libreid_hip_eval_links.so (csrc/eval_links.hip; tests/test_gpu_eval_links.py), each through the launcher the entries
+ * call, on host operands; guards preset to 0xff bytes with the rest; each call returns the context's fault status.
+ *   shift_mirror  x [m][3][h][w], shift_tl int32 [m][2], fill3 -> y [m 3 h w + w]: crop(pad(mirror(x))) and ONE guard row of w floats behind
+ *                 it (reid_descriptor_f32_nchw_shift).
+ *   dist_add_l2   a [n][d], inout [n n + n]: the matrix, updated in place as reid_distmat_add_l2 does, and ONE guard row of n floats
+ *                 behind it, which the call presets itself (what the caller put there is ignored). */
+int reid_debug_shift_mirror(reid_ctx* ctx, const float* x, int m, int h, int w, const int32_t* shift_tl, int pad, const float* fill3,
+                            float* y);
+int reid_debug_dist_add_l2(reid_ctx* ctx, const float* a, int n, int d, float* inout);
 
 #ifdef __cplusplus
 }

@@ -1778,3 +1778,39 @@ extern "C" int reid_debug_flip_w(reid_ctx* ctx, const float* x, long long rows, 
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }
+
+// ------------------------------------------------------------------------------------------------ evaluation links (tests/test_gpu_eval_links.py)
+// shift_mirror_nchw_kernel through launch_shift_mirror (the second view of the reid_descriptor_*_shift entries), on host operands:
+// x [m][3][h][w], shift_tl int32 [m][2] -> y [m 3 h w + w]: the view and ONE guard row behind it, preset to 0xff bytes with the rest.
+extern "C" int reid_debug_shift_mirror(reid_ctx* ctx, const float* x, int m, int h, int w, const int32_t* shift_tl, int pad,
+                                       const float* fill3, float* y) {
+    ARG_CHECK(ctx && x && shift_tl && fill3 && y && m >= 1 && h >= 1 && w >= 1 && pad >= 0);
+    for (int i = 0; i < 2 * m; ++i) ARG_CHECK(shift_tl[i] >= 0 && shift_tl[i] <= 2 * pad);
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)m * 3 * h * w;
+    float *dx, *dy;
+    int32_t* dtl;
+    REID_TRY(dbg_upload(ctx, "dbgl.x", x, nx, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgl.tl", shift_tl, (size_t)2 * m, &dtl));
+    REID_TRY(dbg_output(ctx, "dbgl.y", nx + w, &dy));
+    REID_TRY(launch_shift_mirror(ctx, dx, m, h, w, dtl, pad, fill3, dy));
+    REID_TRY(dbg_download(ctx, y, dy, nx + w));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// dist_add_l2_kernel through launch_dist_add_l2 (reid_distmat_add_l2*), on host operands: a [n][d], inout [n n + n] - the matrix, updated
+// in place, and ONE guard row behind it, preset to 0xff bytes here.
+extern "C" int reid_debug_dist_add_l2(reid_ctx* ctx, const float* a, int n, int d, float* inout) {
+    ARG_CHECK(ctx && a && inout && n >= 1 && d >= 1 && d <= 32);
+    CTX_ENTER(ctx);
+    const size_t nn = (size_t)n * n;
+    float *da, *dio;
+    REID_TRY(dbg_upload(ctx, "dbgl.a", a, (size_t)n * d, &da));
+    REID_TRY(dbg_output(ctx, "dbgl.io", nn + n, &dio));
+    HIP_TRY(hipMemcpyAsync(dio, inout, nn * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(launch_dist_add_l2(ctx, da, n, d, dio));
+    REID_TRY(dbg_download(ctx, inout, dio, nn + n));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}

@@ -11,6 +11,8 @@
 //     inverse's accuracy up to condition number 3e4 (tests/test_gpu_postproc.py).
 #include "reid_internal.h"
 #include "pil_launch.h"
+#include "eval_links.h"
+#include <mutex>
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -203,14 +205,91 @@ int launch_flip_w_nchw(reid_ctx* ctx, const float* x, long long rows, int w, flo
     return REID_OK;
 }
 
+// ---- libreid_hip_eval_links.so (eval_links.h), opened on the first call that needs it: the shifted mirrored view of the
+// reid_descriptor_*_shift entries and reid_distmat_add_l2*.
+struct EvalLinksApi {
+    decltype(&eval_links_shift_mirror) shift_mirror = nullptr;
+    decltype(&eval_links_dist_add_l2) dist_add_l2 = nullptr;
+};
+static int eval_links_api(const EvalLinksApi** out) {
+    static std::mutex m;
+    static EvalLinksApi api;
+    static bool ready = false;
+    std::lock_guard<std::mutex> lk(m);
+    if (!ready) {
+        void* f[2];
+        REID_TRY(open_beside_self("libreid_hip_eval_links.so",
+                                  "the shifted mirrored view (reid_descriptor_*_shift) and reid_distmat_add_l2 need",
+                                  {"eval_links_shift_mirror", "eval_links_dist_add_l2"}, f));
+        api.shift_mirror = (decltype(api.shift_mirror))f[0];
+        api.dist_add_l2 = (decltype(api.dist_add_l2))f[1];
+        ready = true;
+    }
+    *out = &api;
+    return REID_OK;
+}
+static int eval_links_status(const char* what, hipError_t e) {
+    if (e == hipSuccess) return REID_OK;
+    reid_set_error("libreid_hip_eval_links.so %s -> %s", what, hipGetErrorString(e));
+    return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+}
+
+// shift_mirror_nchw_kernel: y = crop(pad(mirror(x))) of x [m][3][h][w], (top, left) per image from d_shift_tl (device int32 [m][2])
+int launch_shift_mirror(reid_ctx* ctx, const float* x, int m, int h, int w, const int32_t* d_shift_tl, int pad, const float* fill3, float* y) {
+    const EvalLinksApi* ev;
+    REID_TRY(eval_links_api(&ev));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, 8.0 * m * 3 * h * w);
+    const hipError_t e = ev->shift_mirror(ctx->stream, x, m, h, w, d_shift_tl, pad, fill3, y);
+    prof_end(ctx);
+    return eval_links_status("eval_links_shift_mirror", e);
+}
+
+// dist_add_l2_kernel: d_inout [n][n] += euclidean_dist(a, a), a [n][d]
+int launch_dist_add_l2(reid_ctx* ctx, const float* a, int n, int d, float* d_inout) {
+    const EvalLinksApi* ev;
+    REID_TRY(eval_links_api(&ev));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 2.0 * n * n * d, 8.0 * n * n);
+    const hipError_t e = ev->dist_add_l2(ctx->stream, a, n, d, d_inout);
+    prof_end(ctx);
+    return eval_links_status("eval_links_dist_add_l2", e);
+}
+
+// The second view of the reid_descriptor_*_shift entries (strong_inference, reid/data_transforms.py:130-191): the mirror shifted by
+// (top - pad, left - pad) over a border of `fill`.  d_tl: device int32 [n][2] of the call's images (descriptor_dev's n).
+struct ShiftView {
+    const int32_t* d_tl;
+    int pad;
+    float fill[3];
+};
+
+// pad in 0 .. 32 and every (top, left) in [0, 2 pad]: REID_ERR_ARG naming the image otherwise
+static int shift_check(const char* who, const int32_t* shift_tl, int n, int pad) {
+    if (pad < 0 || pad > 32) {
+        reid_set_error("%s: pad %d outside 0 .. 32", who, pad);
+        return REID_ERR_ARG;
+    }
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 2; ++k)
+            if (shift_tl[2 * i + k] < 0 || shift_tl[2 * i + k] > 2 * pad) {
+                reid_set_error("%s: shift_tl of image %d: %s %d outside [0, 2 pad = %d]", who, i, k ? "left" : "top", shift_tl[2 * i + k],
+                               2 * pad);
+                return REID_ERR_ARG;
+            }
+    return REID_OK;
+}
+
 // x: [n][3][256][128] fp32 already normalised by the caller's transform (the evaluation script uses ImageNet mean/std,
 // data_transforms.py:56-130); out: [n][512 + num_class].  flip_tta != 0 averages the descriptor of the mirrored image.
 // before_view(v, i, m) runs before the forward of images [i, i + m) of view v (0 plain, 1 mirrored): nothing for the float entries,
 // the side indices of the pass for reid_descriptor_images_u8.
 // h x w other than 256 x 128 (or the debug switch anysize_force): the any-size forward of api.hip in passes of se_any_pass images, the
 // mirrored view read with reversed columns by its layout kernel (no flipped copy of the batch).
+// sv != nullptr (the *_shift entries, flip_tta on): the second view is the SHIFTED mirror - at 256 x 128 shift_mirror_nchw_kernel writes
+// pp.flip in place of flip_w_nchw_kernel, at another size it writes a shifted copy of the pass (pp.shift) and the any-size forward runs
+// on it with mirror = 0.  Everything else is the same call.
 template <class BeforeView>
-static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out, BeforeView before_view) {
+static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, int flip_tta, float* d_out, BeforeView before_view,
+                          const ShiftView* sv = nullptr) {
     ARG_CHECK(ctx && d_x && d_out && n >= 0);
     REID_TRY(se_any_ready(ctx, h, w, "reid_descriptor_*_hw"));
     CTX_ENTER(ctx);
@@ -234,8 +313,12 @@ static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, 
             const int pass = se_any_pass(ctx, h, w);
             for (int i = 0; i < n; i += pass) {
                 const int m = n - i < pass ? n - i : pass;
+                if (sv) {
+                    if (!xf) REID_TRY(ctx_ws(ctx, "pp.shift", (size_t)(n < pass ? n : pass) * img * 4, (void**)&xf));
+                    REID_TRY(launch_shift_mirror(ctx, d_x + (size_t)i * img, m, h, w, sv->d_tl + 2 * (size_t)i, sv->pad, sv->fill, xf));
+                }
                 REID_TRY(before_view(1, i, m));
-                REID_TRY(se_any_run_nchw(ctx, d_x + (size_t)i * img, m, h, w, 1, e2 + (size_t)i * de, l2 + (size_t)i * nc));
+                REID_TRY(se_any_run_nchw(ctx, sv ? xf : d_x + (size_t)i * img, m, h, w, sv ? 0 : 1, e2 + (size_t)i * de, l2 + (size_t)i * nc));
             }
         }
         return launch_descriptor(ctx, e1, l1, e2, l2, n, de, nc, d_out);
@@ -249,7 +332,8 @@ static int descriptor_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, 
         for (int i = 0; i < n; i += chunk) {
             const int m = n - i < chunk ? n - i : chunk;
             const long long rows = (long long)m * 3 * 256;
-            REID_TRY(launch_flip_w_nchw(ctx, d_x + (size_t)i * img, rows, 128, xf));
+            if (sv) REID_TRY(launch_shift_mirror(ctx, d_x + (size_t)i * img, m, 256, 128, sv->d_tl + 2 * (size_t)i, sv->pad, sv->fill, xf));
+            else REID_TRY(launch_flip_w_nchw(ctx, d_x + (size_t)i * img, rows, 128, xf));
             REID_TRY(before_view(1, i, m));
             REID_TRY(reid_embed_f32_nchw_dev(ctx, xf, m, e2 + (size_t)i * de, l2 + (size_t)i * nc));
         }
@@ -301,14 +385,62 @@ extern "C" int reid_descriptor_f32_nchw(reid_ctx* ctx, const float* x, int n, in
     return reid_descriptor_f32_nchw_hw(ctx, x, n, 256, 128, flip_tta, out);
 }
 
+// reid_descriptor_f32_nchw_hw* with flip_tta = 1 and the SHIFTED mirror as the second view.  What is refused, with nothing queued: the
+// arguments of the shift (REID_ERR_ARG), what reid_descriptor_f32_nchw_hw* refuses, a missing libreid_hip_eval_links.so (REID_ERR_STATE).
+static int shift_entry_ready(reid_ctx* ctx, const char* who, int n, int h, int w, const int32_t* shift_tl, int pad, const float* fill3) {
+    ARG_CHECK(ctx && shift_tl && n >= 0);
+    if (!fill3) {
+        reid_set_error("%s: fill3 is NULL (the border of the shifted view, e.g. (0 - mean) / std per channel)", who);
+        return REID_ERR_ARG;
+    }
+    REID_TRY(shift_check(who, shift_tl, n, pad));
+    REID_TRY(se_any_ready(ctx, h, w, who));
+    const EvalLinksApi* ev;
+    return eval_links_api(&ev);
+}
+
+extern "C" int reid_descriptor_f32_nchw_shift_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, const int32_t* shift_tl, int pad,
+                                                  const float* fill3, float* d_out) {
+    ARG_CHECK(ctx && d_x && d_out);
+    REID_TRY(shift_entry_ready(ctx, "reid_descriptor_f32_nchw_shift_dev", n, h, w, shift_tl, pad, fill3));
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    ShiftView sv{nullptr, pad, {fill3[0], fill3[1], fill3[2]}};
+    REID_TRY(ctx_ws(ctx, "pp.tl", (size_t)n * 8, (void**)&sv.d_tl));
+    HIP_TRY(hipMemcpyAsync((void*)sv.d_tl, shift_tl, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));   // shift_tl is the caller's: not read after this call returns
+    return descriptor_dev(ctx, d_x, n, h, w, 1, d_out, [](int, int, int) -> int { return REID_OK; }, &sv);
+}
+
+extern "C" int reid_descriptor_f32_nchw_shift(reid_ctx* ctx, const float* x, int n, int h, int w, const int32_t* shift_tl, int pad,
+                                              const float* fill3, float* out) {
+    ARG_CHECK(ctx && x && out);
+    REID_TRY(shift_entry_ready(ctx, "reid_descriptor_f32_nchw_shift", n, h, w, shift_tl, pad, fill3));
+    CTX_ENTER(ctx);
+    if (n == 0) return REID_OK;
+    int de = 0, nc = 0;
+    REID_TRY(reid_seres18_dims(ctx, &de, &nc));
+    const size_t img = (size_t)3 * h * w;
+    float *dx, *dout;
+    REID_TRY(ctx_ws(ctx, "pp.x", (size_t)n * img * 4, (void**)&dx));
+    REID_TRY(ctx_ws(ctx, "pp.out", (size_t)n * (de + (nc > 0 ? nc : 0)) * 4 + 16, (void**)&dout));
+    HIP_TRY(hipMemcpyAsync(dx, x, (size_t)n * img * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(reid_descriptor_f32_nchw_shift_dev(ctx, dx, n, h, w, shift_tl, pad, fill3, dout));
+    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * (de + nc) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 // uint8 images of any sizes in: transforms.Resize((256, 128)) as PIL computes it -> ToTensor -> Normalize on the device (PilPlan,
 // libreid_hip_pil_resize.so), then per pass of `chunk` images what reid_descriptor_f32_nchw_dev runs on that pass - the same passes, the
 // same kernels, so the same bits as reid_descriptor_f32_nchw on the images preprocessed on the host.  n pending side indices serve the
 // plain and the mirrored view of an image, as the script's model(img, cam.repeat(2)) and as reid_swin_descriptor_*; the float entry
 // computes the same when it is given the indices twice (its plain passes take the first n, its mirrored passes the next n).  None stays
 // pending.
-extern "C" int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
-                                            int out_w, const float* mean_std6, int flip_tta, float* out) {
+// shift_tl != nullptr (reid_descriptor_images_u8_shift): the second view is the shifted mirror over a border of the table's entry for
+// pixel value 0 - Pad(fill = 0) on the 8-bit image, then ToTensor + Normalize.
+static int descriptor_images_u8(reid_ctx* ctx, const char* who, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
+                                int out_h, int out_w, const float* mean_std6, int flip_tta, const int32_t* shift_tl, int pad, float* out) {
     ARG_CHECK(ctx);
     struct SideDrop {
         reid_ctx* ctx;
@@ -321,7 +453,12 @@ extern "C" int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed
     REID_TRY(pil_mean_std(&mean_std6));
     RaggedSrc src{packed, offsets, hw, n};
     REID_TRY(src.check());
-    REID_TRY(se_any_ready(ctx, out_h, out_w, "reid_descriptor_images_u8_hw"));
+    if (shift_tl) REID_TRY(shift_check(who, shift_tl, n, pad));
+    REID_TRY(se_any_ready(ctx, out_h, out_w, who));
+    if (shift_tl) {
+        const EvalLinksApi* ev;
+        REID_TRY(eval_links_api(&ev));
+    }
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
     int de = 0, nc = 0;
@@ -345,23 +482,83 @@ extern "C" int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed
     REID_TRY(src.alloc(ctx, "io"));
     REID_TRY(o.alloc(ctx, "ppd", n, 0, false));
     REID_TRY(plan.alloc(ctx, "io"));
+    ShiftView sv{nullptr, pad, {plan.table[0], plan.table[256], plan.table[512]}};
+    if (shift_tl) REID_TRY(ctx_ws(ctx, "pp.tl", (size_t)n * 8, (void**)&sv.d_tl));
     return embed_host(
         ctx, n, pass,
         [&](int i, int m, hipStream_t s) -> int {
             REID_TRY(src.up(i, m, s));
+            if (i == 0 && shift_tl) HIP_TRY(hipMemcpyAsync((void*)sv.d_tl, shift_tl, (size_t)n * 8, hipMemcpyHostToDevice, s));
             return i == 0 ? plan.up(s) : REID_OK;
         },
         [&](int i, int m, float* d_row, float*) -> int {
             REID_TRY(plan.launch(ctx, src, i, m, nullptr, plan.d_f32));
-            return descriptor_dev(ctx, plan.d_f32, m, out_h, out_w, flip_tta, d_row, [&](int, int, int) -> int {
-                if (!side.empty()) {
-                    ctx->side_idx.assign(side.begin() + i, side.begin() + i + m);
-                    ctx->side_cursor = 0;
-                }
-                return REID_OK;
-            });
+            const ShiftView pass_sv{sv.d_tl + 2 * (size_t)i, sv.pad, {sv.fill[0], sv.fill[1], sv.fill[2]}};
+            return descriptor_dev(
+                ctx, plan.d_f32, m, out_h, out_w, flip_tta, d_row,
+                [&](int, int, int) -> int {
+                    if (!side.empty()) {
+                        ctx->side_idx.assign(side.begin() + i, side.begin() + i + m);
+                        ctx->side_cursor = 0;
+                    }
+                    return REID_OK;
+                },
+                shift_tl ? &pass_sv : nullptr);
         },
         o);
+}
+
+extern "C" int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h,
+                                            int out_w, const float* mean_std6, int flip_tta, float* out) {
+    return descriptor_images_u8(ctx, "reid_descriptor_images_u8_hw", packed, offsets, hw, n, out_h, out_w, mean_std6, flip_tta, nullptr, 0, out);
+}
+
+extern "C" int reid_descriptor_images_u8_shift(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,
+                                               int out_h, int out_w, const float* mean_std6, const int32_t* shift_tl, int pad, float* out) {
+    if (ctx && !shift_tl) {   // the pending side indices are dropped as on every other refusal of this entry
+        ctx->side_idx.clear();
+        ctx->side_cursor = 0;
+    }
+    ARG_CHECK(ctx && shift_tl);
+    return descriptor_images_u8(ctx, "reid_descriptor_images_u8_shift", packed, offsets, hw, n, out_h, out_w, mean_std6, 1, shift_tl, pad, out);
+}
+
+// d_inout [n][n] += euclidean_dist(a, a) (reid/losses/utils.py:21-35), a [n][d] - the attribute term the evaluation script adds to the
+// Jaccard matrix (image_reid_inference.py:276-289) - in place, one read and one write of the matrix (dist_add_l2_kernel, eval_links.h).
+extern "C" int reid_distmat_add_l2_dev(reid_ctx* ctx, const float* d_a, int n, int d, float* d_inout) {
+    ARG_CHECK(ctx && n >= 0);
+    if (d < 1 || d > 32) {
+        reid_set_error("reid_distmat_add_l2: d = %d outside 1 .. 32", d);
+        return REID_ERR_ARG;
+    }
+    if (n == 0) return REID_OK;
+    ARG_CHECK(d_a && d_inout && ((uintptr_t)d_inout & 15) == 0);
+    const EvalLinksApi* ev;
+    REID_TRY(eval_links_api(&ev));
+    CTX_ENTER(ctx);
+    return launch_dist_add_l2(ctx, d_a, n, d, d_inout);
+}
+
+extern "C" int reid_distmat_add_l2(reid_ctx* ctx, const float* a, int n, int d, float* inout) {
+    ARG_CHECK(ctx && n >= 0);
+    if (d < 1 || d > 32) {
+        reid_set_error("reid_distmat_add_l2: d = %d outside 1 .. 32", d);
+        return REID_ERR_ARG;
+    }
+    if (n == 0) return REID_OK;
+    ARG_CHECK(a && inout);
+    const EvalLinksApi* ev;
+    REID_TRY(eval_links_api(&ev));
+    CTX_ENTER(ctx);
+    float *da, *dio;
+    REID_TRY(ctx_ws(ctx, "addl2.a", (size_t)n * d * 4, (void**)&da));
+    REID_TRY(ctx_ws(ctx, "addl2.io", (size_t)n * n * 4, (void**)&dio));
+    HIP_TRY(hipMemcpyAsync(da, a, (size_t)n * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dio, inout, (size_t)n * n * 4, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(launch_dist_add_l2(ctx, da, n, d, dio));
+    HIP_TRY(hipMemcpyAsync(inout, dio, (size_t)n * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
 }
 
 extern "C" int reid_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n,

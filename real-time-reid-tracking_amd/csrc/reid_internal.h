@@ -331,6 +331,11 @@ int launch_diou_cost(reid_ctx*, const double* tracks, int t, const double* dets,
 // single view, not renormalised) -> out [n][de + dl], and the column mirror of x [rows][w]
 int launch_descriptor(reid_ctx*, const float* e1, const float* l1, const float* e2, const float* l2, int n, int de, int dl, float* out);
 int launch_flip_w_nchw(reid_ctx*, const float* x, long long rows, int w, float* y);
+// postproc.hip: the two kernels of libreid_hip_eval_links.so (eval_links.h), opened on the first call - the shifted mirrored view
+// y = crop(pad(mirror(x))) of x [m][3][h][w] with (top, left) per image from the device array d_shift_tl and fill3 on the host, and
+// d_inout [n][n] += euclidean_dist(a, a) in place.  A missing library is REID_ERR_STATE naming it.
+int launch_shift_mirror(reid_ctx*, const float* x, int m, int h, int w, const int32_t* d_shift_tl, int pad, const float* fill3, float* y);
+int launch_dist_add_l2(reid_ctx*, const float* a, int n, int d, float* d_inout);
 
 // ------------------------------------------------------------------------------------------------
 struct ProfSlot {

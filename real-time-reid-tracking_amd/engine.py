@@ -411,6 +411,118 @@ class Engine:
         check(self.lib.reid_descriptor_images_u8(self.h, src, _ptr(offs), _ptr(hw), n, _ptr(ms), int(bool(flip_tta)), _ptr(out)))
         return out
 
+    # ---- the shifted mirrored view of the script's strong_inference (reid/data_transforms.py:130-191)
+    IMAGENET_MEAN_STD = (0.485, 0.456, 0.406, 0.229, 0.224, 0.225)   # the library's default for mean_std=None
+    SHIFT_PAD_MAX = 32
+
+    @staticmethod
+    def normalised_zero_fill(mean_std=None):
+        """float32 [3]: what a black (0) pixel becomes under ToTensor + Normalize(mean_std; None: ImageNet), in the arithmetic of the
+        device's normalisation table (pil_resize_norm_table): t = fp32(0) / fp32(255); (t - mean) / std, every step rounded to fp32.
+        The border of the shifted mirrored view - Pad(fill=0) on the 8-bit image comes before Normalize."""
+        ms = np.asarray(Engine.IMAGENET_MEAN_STD if mean_std is None else mean_std, np.float32).reshape(-1)
+        if ms.size != 6 or not np.isfinite(ms).all() or not (ms[3:] > 0).all():
+            raise ValueError("mean_std must be (mean[3], std[3]) with finite values and std > 0, got %r" % (mean_std,))
+        t = np.float32(0.0) / np.float32(255.0)
+        return ((t - ms[:3]).astype(np.float32) / ms[3:]).astype(np.float32)
+
+    @staticmethod
+    def check_shift(shift_tl, n, pad):
+        """(top, left) per image as int32 [n, 2] and pad, checked before any device call: pad in 0 .. 32, every shift in [0, 2 pad]."""
+        if isinstance(pad, bool) or not isinstance(pad, (int, np.integer)) or not 0 <= pad <= Engine.SHIFT_PAD_MAX:
+            raise ValueError("pad must be an integer in 0 .. %d, got %r" % (Engine.SHIFT_PAD_MAX, pad))
+        tl = np.asarray(shift_tl)
+        if tl.shape != (n, 2) or not np.issubdtype(tl.dtype, np.integer):
+            raise ValueError("shift_tl must be integers [n, 2] = (top, left) per image for %d images, got %s %s" % (n, tl.dtype, tl.shape))
+        bad = np.argwhere((tl < 0) | (tl > 2 * pad))
+        if bad.size:
+            i, k = (int(v) for v in bad[0])
+            raise ValueError("shift_tl of image %d: %s %d outside [0, 2 pad = %d]" % (i, ("top", "left")[k], int(tl[i, k]), 2 * int(pad)))
+        return np.ascontiguousarray(tl, dtype=np.int32), int(pad)
+
+    def descriptor_f32_nchw_shift(self, x, shift_tl, pad=10, fill=None):
+        """descriptor_f32_nchw(flip_tta=True) with the script's strong_inference second view: the mirrored image shifted by
+        (top - pad, left - pad) = shift_tl[i] - pad over a border of ``fill`` [3] (None: normalised_zero_fill() for ImageNet), i.e.
+        crop(pad(mirror(x))).  shift_tl == pad everywhere is the plain mirror and the bits of flip_tta=True
+        (reid_descriptor_f32_nchw_shift)."""
+        x = _f32(x)
+        if x.ndim != 4 or x.shape[1] != 3:
+            raise ValueError("descriptor_f32_nchw_shift expects [n,3,H,W] (%d x %d, or sides in [%d, %d]), got %s"
+                             % (IMG_H, IMG_W, SIZE_MIN, SIZE_MAX, x.shape))
+        h, w = check_hw(x.shape[2:])
+        tl, pad = Engine.check_shift(shift_tl, x.shape[0], pad)
+        fill = Engine.normalised_zero_fill() if fill is None else _f32(fill).reshape(-1)
+        if fill.size != 3:
+            raise ValueError("fill must be 3 floats (one per channel), got %r" % (fill,))
+        out = np.empty((x.shape[0], self.embed_dim + self.num_class), np.float32)
+        check(self.lib.reid_descriptor_f32_nchw_shift(self.h, _ptr(x), x.shape[0], h, w, _ptr(tl), pad, _ptr(fill), _ptr(out)))
+        return out
+
+    def descriptor_shift_dev(self, d_x, n, size, shift_tl, pad, fill, d_out):
+        """reid_descriptor_f32_nchw_shift_dev: images and descriptors on the device, shift_tl / fill on the host."""
+        h, w = check_hw(size)
+        tl, pad = Engine.check_shift(shift_tl, int(n), pad)
+        fill = _f32(fill).reshape(-1)
+        if fill.size != 3:
+            raise ValueError("fill must be 3 floats (one per channel), got %r" % (fill,))
+        check(self.lib.reid_descriptor_f32_nchw_shift_dev(self.h, C.c_void_p(d_x), int(n), h, w, _ptr(tl), pad, _ptr(fill), C.c_void_p(d_out)))
+
+    def descriptor_images_u8_shift(self, images, shift_tl, pad=10, mean_std=None, size=None):
+        """descriptor_images_u8(flip_tta=True) with the shifted mirrored view as its second view; the border is the normalisation
+        table's entry for pixel value 0 (normalised_zero_fill(mean_std)).  ``size`` None: (256, 128)
+        (reid_descriptor_images_u8_shift)."""
+        _, _, ms = self._swin_crop_args((224, 224), mean_std)
+        h, w = (IMG_H, IMG_W) if size is None else check_hw(size)
+        images = list(images)
+        n = len(images)
+        tl, pad = Engine.check_shift(shift_tl, n, pad)
+        src, offs, hw, _keep = self._pack_images(images)
+        nc = getattr(self, "num_class", 0)
+        if nc <= 0:
+            raise ValueError("a descriptor needs loaded weights with a classifier (Engine.load_seres18)")
+        out = np.empty((n, self.embed_dim + nc), np.float32)
+        check(self.lib.reid_descriptor_images_u8_shift(self.h, src, _ptr(offs), _ptr(hw), n, h, w, _ptr(ms), _ptr(tl), pad, _ptr(out)))
+        return out
+
+    # ---- the attribute distance of the Market-1501 evaluation (reid/image_reid_inference.py:276-289)
+    def distmat_add_l2(self, a, inout):
+        """inout [n, n] float32 += euclidean_dist(a, a) (reid/losses/utils.py:21-35), a [n, d], 1 <= d <= 32, in place; returns inout
+        (reid_distmat_add_l2)."""
+        a = _f32(a)
+        if a.ndim != 2 or not isinstance(inout, np.ndarray) or inout.dtype != np.float32 or inout.shape != (a.shape[0], a.shape[0]) \
+                or not inout.flags.c_contiguous:
+            raise ValueError("distmat_add_l2 expects a [n, d] and a C-contiguous float32 inout [n, n]")
+        check(self.lib.reid_distmat_add_l2(self.h, _ptr(a), a.shape[0], a.shape[1], _ptr(inout)))
+        return inout
+
+    def distmat_add_l2_dev(self, d_a, n, d, d_inout):
+        check(self.lib.reid_distmat_add_l2_dev(self.h, C.c_void_p(d_a), int(n), int(d), C.c_void_p(d_inout)))
+
+    def debug_shift_mirror(self, x, shift_tl, pad, fill):
+        """shift_mirror_nchw_kernel through the launcher the *_shift entries call (reid_debug_shift_mirror): x [m, 3, h, w].  Returns
+        (y [m, 3, h, w], guard [w])."""
+        x = _f32(x)
+        m, _, h, w = x.shape
+        tl = np.ascontiguousarray(shift_tl, dtype=np.int32).reshape(m, 2)
+        fill = _f32(fill).reshape(3)
+        y = np.empty(x.size + w, np.float32)
+        fn = _ffi.debug_lib().reid_debug_shift_mirror
+        fn.restype = C.c_int
+        check(fn(self.h, _ptr(x), C.c_int(m), C.c_int(h), C.c_int(w), _ptr(tl), C.c_int(int(pad)), _ptr(fill), _ptr(y)))
+        return y[:-w].reshape(x.shape), y[-w:]
+
+    def debug_dist_add_l2(self, a, inout):
+        """dist_add_l2_kernel through the launcher reid_distmat_add_l2* call (reid_debug_dist_add_l2): a [n, d], inout [n, n] (not
+        modified).  Returns (updated [n, n], guard [n])."""
+        a = _f32(a)
+        n, d = a.shape
+        buf = np.empty(n * n + n, np.float32)
+        buf[:n * n] = _f32(inout).reshape(-1)
+        fn = _ffi.debug_lib().reid_debug_dist_add_l2
+        fn.restype = C.c_int
+        check(fn(self.h, _ptr(a), C.c_int(n), C.c_int(d), _ptr(buf)))
+        return buf[:-n].reshape(n, n), buf[-n:]
+
     # ---- embedding
     def _outs(self, n, want_logits, dim=None, num_class=None):
         """Host arrays an embed call fills: emb[n, dim] and logits[n, num_class] or None (default sizes: the ResNet18-SE family's)."""

@@ -39,22 +39,34 @@ def smooth_tracklets(embeddings, seqs, indices_valid, device=0):
     return out
 
 
-def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=None):
+def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=None, strong_offsets=None, pad=10):
     """float [n,3,H,W] after the caller's transform ((256, 128), or sides in 32 .. 512 for seres18_ibn weights in exact fp32), or a list
     of uint8 [h,w,3] images of any sizes, which the device resizes as PIL does - to ``size`` = (H, W), default (256, 128); the script's
     VeRi geometry is (224, int(ratio * 224)) - and normalises with the ImageNet values (Engine.descriptor_images_u8).
     ``hw_precision``: the arithmetic of another size for this call (Engine.set_hw_precision: "f32" / "f16x3"), restored afterwards; None
-    leaves the engine's setting alone."""
+    leaves the engine's setting alone.
+    ``strong_offsets``: int [n, 2] of (top, left) per image (data_transforms.strong_inference_offsets) - the second view becomes the
+    script's strong_inference one, the mirror shifted by (top - pad, left - pad) over a black border (reid/data_transforms.py:130-191;
+    Engine.descriptor_f32_nchw_shift / descriptor_images_u8_shift; needs ``flip``).  None is today's call and bits."""
     if size is not None:
         size = check_hw(size)
+    if strong_offsets is not None:
+        from .engine import Engine
+        if not flip:
+            raise ValueError("strong_offsets shift the mirrored view: flip must be on")
+        strong_offsets, pad = Engine.check_shift(strong_offsets, len(images), pad)   # a bad value raises here, before any device call
     if hw_precision is not None:
         from .engine import Engine
         Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
         with get_engine(device).hw_precision_scope(hw_precision):
-            return extract_descriptors(images, flip, device, size)
+            return extract_descriptors(images, flip, device, size, strong_offsets=strong_offsets, pad=pad)
     if isinstance(images, (list, tuple)) and len(images) and all(getattr(im, "dtype", None) == np.uint8 for im in images):
+        if strong_offsets is not None:
+            return get_engine(device).descriptor_images_u8_shift(images, strong_offsets, pad=pad, size=size)
         return get_engine(device).descriptor_images_u8(images, flip_tta=flip, size=size)
     images = _np(images)
     if size is not None and tuple(images.shape[2:]) != size:
         raise ValueError("size %r is the resize target of uint8 images; these float images are %s" % (size, tuple(images.shape[2:])))
+    if strong_offsets is not None:
+        return get_engine(device).descriptor_f32_nchw_shift(images, strong_offsets, pad=pad)
     return get_engine(device).descriptor_f32_nchw(images, flip)

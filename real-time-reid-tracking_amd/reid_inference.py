@@ -26,8 +26,14 @@ With ``arch="swin"`` the descriptor link is ``reid_swin_descriptor_f32_nchw_dev`
 (logits, x_norm), swin_transformer.py:422-423 - and is num_class + 96 wide (``reid_swin_dims``); every later link takes that width as it
 is.  ``use_side`` hands the cameras over as the view indices of both views (inference_efficient :117-120, model(img, cam.repeat(2))).
 
-The Market-1501 attribute distance (:278-283, needs the dataset's .mat file) is not part of this harness.
+The two remaining links of the script's Market-1501 run are keywords of ``evaluate_reid``: ``strong_inference`` / ``strong_offsets`` make
+the second view of the ResNet family the shifted mirror of get_inference_transforms_flipped(strong_inference=True)
+(data_transforms.py:130-191, image_reid_inference.py:179-181; ``reid_descriptor_f32_nchw_shift_dev`` /
+``reid_descriptor_images_u8_shift``), and ``attribute_dist`` adds the attribute distance (:276-289, tricks.py) to the device Jaccard
+matrix before its one download (``reid_distmat_add_l2_dev``).
 """
+import os
+
 import numpy as np
 
 from .engine import IMG_H, IMG_W, check_hw, get_engine
@@ -108,7 +114,7 @@ def _check_u8_images(images, arch, size):
     return out, (h, w)
 
 
-def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width):
+def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width, strong_offsets=None, pad=10):
     """The uint8 path of inference_efficient: batches of ``bs`` images through the *_images_u8 entries, whose rows (about 5 KB per
     image) are copied into the device matrix."""
     n = len(images)
@@ -118,6 +124,8 @@ def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width
             if view_index is not None:
                 engine.set_side_index(view_index[i:i + bs])
             rows = engine.swin_descriptor_images_u8(part, size=size, flip_tta=flip)
+        elif strong_offsets is not None:
+            rows = engine.descriptor_images_u8_shift(part, strong_offsets[i:i + bs], pad=pad, size=size if arch == "seres18_hw" else None)
         elif arch == "seres18_hw":
             rows = engine.descriptor_images_u8(part, flip_tta=flip, size=size)
         else:
@@ -127,7 +135,19 @@ def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width
     return n
 
 
-def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None, hw_precision=None):
+def _check_strong(arch, flip, strong_offsets, n, pad):
+    """The strong_inference keywords, checked before any device call: the ResNet family only (the script gives the Swin the plain
+    mirror), with the mirrored view on, pad in 0 .. 32 and every (top, left) in [0, 2 pad] -> (int32 [n, 2], pad)."""
+    from .engine import Engine
+    if arch == "swin":
+        raise ValueError("strong_inference / strong_offsets are the ResNet family's second view; the script gives arch='swin' the plain mirror")
+    if not flip:
+        raise ValueError("strong_inference / strong_offsets shift the mirrored view: flip must be on")
+    return Engine.check_shift(strong_offsets, n, pad)
+
+
+def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None, hw_precision=None,
+                        strong_offsets=None, pad=10):
     """Descriptors of ``images`` (float32 [n,3,256,128], host) into the device rows ``d_out`` (pointer to [n, 512 + num_class]
     fp32): upload in batches of ``bs`` images, one ``reid_descriptor_f32_nchw_dev`` per batch.  Unlike the reference function
     (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253).
@@ -144,12 +164,19 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     ``size`` = (H, W) (required), e.g. the script's VeRi geometry ``size=(224, int(ratio * 224))``; seres18_ibn weights with the context in
     exact fp32 (``reid_descriptor_f32_nchw_hw_dev`` / ``reid_descriptor_images_u8_hw``), or - ``hw_precision`` "f32" / "f16x3"
     (``Engine.set_hw_precision``) - in the arithmetic named, whatever the context's mode: set for this call and restored after it; None
-    leaves the engine's setting alone."""
+    leaves the engine's setting alone.
+
+    ``strong_offsets``: int [n, 2] of (top, left) per image with ``pad`` (data_transforms.strong_inference_offsets): the second view is the
+    script's strong_inference one - the mirror shifted by (top - pad, left - pad) over a black border, black being (0 - mean) / std of the
+    ImageNet values (``reid_descriptor_f32_nchw_shift_dev`` / ``reid_descriptor_images_u8_shift``).  ``arch="swin"`` takes none: the
+    script gives the Swin the plain mirror.  None is today's call and bits."""
     if hw_precision is not None:
         from .engine import Engine
         if arch != "seres18_hw":
             raise ValueError("hw_precision is the arithmetic of arch='seres18_hw'; arch=%r takes none" % (arch,))
         Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
+    if strong_offsets is not None:
+        strong_offsets, pad = _check_strong(arch, flip, strong_offsets, len(images), pad)
     width = _descriptor_width(engine, arch)
     u8 = is_u8_images(images)
     if u8:
@@ -171,9 +198,14 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
         view_index = view_index.astype(np.int32)
     if hw_precision is not None:                     # every argument is checked: the setting goes on for the device work and off after it
         with engine.hw_precision_scope(hw_precision):
-            return inference_efficient(engine, images, d_out, flip, bs, arch, view_index, size if u8 else None)
+            return inference_efficient(engine, images, d_out, flip, bs, arch, view_index, size if u8 else None,
+                                       strong_offsets=strong_offsets, pad=pad)
     if u8:
-        return _inference_u8(engine, images, d_out, flip, int(bs), arch, view_index, size, width)
+        return _inference_u8(engine, images, d_out, flip, int(bs), arch, view_index, size, width, strong_offsets, pad)
+    fill = None
+    if strong_offsets is not None:
+        from .engine import Engine
+        fill = Engine.normalised_zero_fill()
     stage = DevArray(engine, (min(bs, max(n, 1)),) + images.shape[1:], np.float32)
     try:
         for i in range(0, n, bs):
@@ -183,6 +215,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
                 if view_index is not None:
                     engine.set_side_index(view_index[i:i + bs])
                 engine.swin_descriptor_dev(stage.ptr, part.shape[0], part.shape[2], part.shape[3], flip, d_out + i * width * 4)
+            elif strong_offsets is not None:
+                engine.descriptor_shift_dev(stage.ptr, part.shape[0], part.shape[2:], strong_offsets[i:i + bs], pad, fill, d_out + i * width * 4)
             elif arch == "seres18_hw":
                 engine.descriptor_dev(stage.ptr, part.shape[0], flip, d_out + i * width * 4, size=part.shape[2:])
             else:
@@ -195,7 +229,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
 
 def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, query_images, query_labels, query_cams,
                   query_seqs, num_gallery_cams=None, eps=0.5, la=0.05, k1=20, k2=6, flip=True, cluster_fn=None, taps=None,
-                  verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None, hw_precision=None):
+                  verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None, hw_precision=None,
+                  strong_inference=False, strong_offsets=None, attribute_dist=None, pad=10):
     """(CMC float32 [ng], mAP float) of the script's chain for one gallery / query pair; weights must be loaded on the engine
     (``Engine.load_seres18`` / ``build_model``).  ``taps`` (a dict) receives host copies of the intermediates the
     reference-generated fixture holds: "desc", "debiased", "jaccard", "pseudo_labels", "smoothed".
@@ -206,7 +241,34 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     = (H, W) is what a Swin resizes them to (default (448, 224); the ResNet family is fixed at 256x128 unless ``arch="seres18_hw"``, which
     runs seres18_ibn weights in exact fp32 at the float images' own size or at ``size``: VeRi is ``size=(224, int(ratio * 224))``;
     ``hw_precision`` "f32" / "f16x3" names that forward's arithmetic for this call - ``Engine.set_hw_precision``, restored afterwards - and
-    None leaves the engine's setting alone)."""
+    None leaves the engine's setting alone).
+    ``strong_inference`` / ``strong_offsets``: the script's second view for the ResNet family (--backbone seres18 / cares18,
+    image_reid_inference.py:179-181) - the mirror shifted by up to +-``pad`` pixels on each axis over a black border.
+    ``strong_offsets`` is int [ng + nq, 2] of (top, left) per image, gallery first; ``strong_inference=True`` without offsets draws them
+    (data_transforms.strong_inference_offsets, torch's global generator).  Either with ``arch="swin"`` is a ValueError: the script gives
+    the Swin the plain mirror.  ``attribute_dist``: the Market-1501 term (:276-289) - an [N, 30] array of already looked-up attribute rows
+    (gallery first), or a ``(labels, mat_path)`` pair for tricks.attribute_rows; the rows are normalised on the host, uploaded and
+    euclidean_dist(rows, rows) is added to the device Jaccard matrix (``reid_distmat_add_l2_dev``) before its download.
+    ``taps["jaccard"]`` stays the matrix before the add; ``taps["dists"]`` is the one handed to DBSCAN / ``cluster_fn``.  With these
+    keywords left out the call and its bits are what they were."""
+    if strong_inference or strong_offsets is not None:
+        n_all = len(gallery_labels) + len(query_labels)
+        if strong_offsets is None:
+            from .data_transforms import strong_inference_offsets
+            _check_strong(arch, flip, np.zeros((n_all, 2), np.int32), n_all, pad)     # arch, flip and pad, before anything is drawn
+            strong_offsets = strong_inference_offsets(n_all, pad)
+        strong_offsets, pad = _check_strong(arch, flip, strong_offsets, n_all, pad)
+    attr_rows = None
+    if attribute_dist is not None:
+        from . import tricks
+        if isinstance(attribute_dist, tuple) and len(attribute_dist) == 2 and isinstance(attribute_dist[1], (str, os.PathLike)):
+            attr_rows = tricks.attribute_rows(attribute_dist[0], attribute_dist[1])
+        else:
+            attr_rows = np.asarray(attribute_dist, np.float32)
+        if attr_rows.ndim != 2 or attr_rows.shape[0] != len(gallery_labels) + len(query_labels) or not 1 <= attr_rows.shape[1] <= 32:
+            raise ValueError("attribute_dist must give one row of 1 .. 32 attributes per image (%d, gallery first), got %s"
+                             % (len(gallery_labels) + len(query_labels), attr_rows.shape))
+        attr_rows = tricks.normalize_rows(attr_rows)
     if hw_precision is not None:
         from .engine import Engine
         if arch != "seres18_hw":
@@ -231,10 +293,12 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     merged = DevArray(eng, (n, width), np.float32)
     dists = DevArray(eng, (n, n), np.float32)
     try:
+        strong = {} if strong_offsets is None else {"pad": pad}
         inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None, size=size if u8[0] else None,
-                            hw_precision=hw_precision)
+                            hw_precision=hw_precision, **(strong and dict(strong, strong_offsets=strong_offsets[:ng])))
         inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None,
-                            size=size if u8[1] else None, hw_precision=hw_precision)
+                            size=size if u8[1] else None, hw_precision=hw_precision,
+                            **(strong and dict(strong, strong_offsets=strong_offsets[ng:])))
         if taps is not None:
             taps["desc"] = merged.numpy()
         merged_cams = np.concatenate([gc, qc]).astype(np.int32)
@@ -243,9 +307,21 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
         if taps is not None:
             taps["debiased"] = merged.numpy()
         eng.rerank_jaccard_dev(merged.ptr, n, width, k1, k2, dists.ptr)     # negatives already clamped (faiss_utils.py:239-240)
+        if attr_rows is not None:                                           # dists += attribute_dist (:288-289), on the device
+            if taps is not None:
+                taps["jaccard"] = dists.numpy()
+            d_attr = DevArray(eng, attr_rows.shape, np.float32)
+            try:
+                eng.h2d(d_attr.ptr, attr_rows)
+                eng.distmat_add_l2_dev(d_attr.ptr, n, attr_rows.shape[1], dists.ptr)
+                eng.sync()
+            finally:
+                d_attr.free()
         host_dists = dists.numpy()                                          # the reference's dists.cpu().numpy() (:297)
         if taps is not None:
-            taps["jaccard"] = host_dists
+            if attr_rows is None:
+                taps["jaccard"] = host_dists
+            taps["dists"] = host_dists
         cams = int(num_gallery_cams) if num_gallery_cams is not None else int(gc.max()) + 1
         cluster = cluster_fn or (lambda dd: dbscan_pseudo_labels(dd, eps, min(10, cams + 1)))
         pseudo = np.asarray(cluster(host_dists)).astype(np.int64).reshape(-1)
