@@ -111,6 +111,19 @@ int reid_debug_any_se_tail(reid_ctx* ctx, int n, int hw, int c, int mid, const f
                            const float* shortcut, float* out, float* gate);
 int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, const float* x, const float* scale, const float* shift, float* gem_out,
                        float* emb);
+/* The TripletAttention block tail of libreid_hip_anysize_ca.so (csrc/anysize_ca.h; tests/test_gpu_anysize_ca.py) through the launcher the
+ * any-size forward calls for cares18_ibn, on host operands: y, shortcut NHWC fp32 [n][h][w][c], prm [3 gates: cw, hc, hw][100] = conv weight
+ * [2][7][7], folded BN scale, shift; 2 <= h, w <= 128, c in {64, 128, 256, 512} (anything else REID_ERR_ARG).
+ *   out = relu(1/3 * ((y s_hw[h, w] + y s_cw[c, w]) + y s_hc[h, c]) + shortcut),  out [n h w c + c] with ONE guard pixel behind the last.
+ * maps / gates (may be NULL), per = h w + c w + h c floats per image, in the layout of csrc/anysize_ca.h:
+ *   maps  [n][2 per]      hw [2][h][w] | cw [2][c][w] | hc [2][h][c], channel 0 = unbiased std, channel 1 = mean
+ *   gates [n per + c]     hw [h][w] | cw [w][c] (transposed) | hc [h][c] per image, then ONE guard of c floats
+ * out and the workspace are set to 0xff bytes before the launch: an element the kernels leave alone reads as NaN.
+ * The switch "any_ca" (reid_debug_set_switch) picks the tail of the any-size trunk for cares18_ibn: 1 (default) = this library, 0 =
+ * launch_ta_tail of csrc/attention_f32.hip, for A/B timing of whole passes in one process.
+ * Returns the context's fault status. */
+int reid_debug_any_ca_tail(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const float* y, const float* shortcut, float* out,
+                           float* maps, float* gates);
 /* One trunk convolution of the any-size forward (tests/test_gpu_anysize_x3.py) through the launcher the forward calls, on host operands:
  * x [n][h][w][cin], wgt [cout][r][r][cin], out [n ho wo cout + cout] with ONE guard row (cout floats) behind the last pixel, preset to 0xff
  * bytes with the rest.  r = 3 with pad 1 or r = 1 with pad 0, stride 1 or 2, cin % 32 == 0, cout % 64 == 0.  out = acc * scale + shift (both

@@ -7,6 +7,7 @@
 #include "distmat_x3.h"
 #include "select_x3.h"
 #include "anysize_front.h"
+#include "anysize_ca.h"
 #include <cmath>
 #include <dlfcn.h>
 #include <mutex>
@@ -206,6 +207,18 @@ extern "C" int reid_ctx_set_hw_precision(reid_ctx* ctx, int v) {
         return REID_ERR_ARG;
     }
     ctx->hw_precision = v;
+    return REID_OK;
+}
+
+extern "C" int reid_ctx_set_hw_siblings(reid_ctx* ctx, int on) {
+    ARG_CHECK(ctx);
+    CTX_GUARD(ctx);
+    if (on != 0 && on != 1) {
+        reid_set_error("reid_ctx_set_hw_siblings: the value must be 0 (other input sizes run seres18_ibn only) or 1 (they run cares18_ibn "
+                       "too)");
+        return REID_ERR_ARG;
+    }
+    ctx->hw_siblings = on;
     return REID_OK;
 }
 
@@ -1541,6 +1554,26 @@ static int anysize_front_api(decltype(&anysize_front)* out) {
     return REID_OK;
 }
 
+// ... and the TripletAttention block tail of cares18_ibn (reid_ctx_set_hw_siblings 1): anysize_ca.h
+struct AnysizeCaApi {
+    decltype(&anysize_ca_workspace_bytes) ws_bytes = nullptr;
+    decltype(&anysize_ca_tail) tail = nullptr;
+};
+static int anysize_ca_api(const AnysizeCaApi** out) {
+    static std::mutex m;
+    static AnysizeCaApi api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.tail) {
+        void* f[2];
+        REID_TRY(open_beside_self("libreid_hip_anysize_ca.so", "CARes18-IBN at an input size other than 256 x 128 needs",
+                                  {"anysize_ca_workspace_bytes", "anysize_ca_tail"}, f));
+        api.ws_bytes = (decltype(api.ws_bytes))f[0];
+        api.tail = (decltype(api.tail))f[1];
+    }
+    *out = &api;
+    return REID_OK;
+}
+
 bool se_any_routes(const reid_ctx* ctx, int h, int w) { return h != IMG_H || w != IMG_W || ctx->anysize_force != 0; }
 
 int se_any_pass(const reid_ctx* ctx, int h, int w) {
@@ -1559,8 +1592,14 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
         reid_set_error("%s: call reid_seres18_load first", who);
         return REID_ERR_STATE;
     }
-    if (wt.arch != 0 || (ctx->hw_precision < 0 && ctx->precision != 0)) {   // reid_ctx_set_hw_precision 0 / 2 names the arithmetic itself
-        static const char* const kArch[3] = {"seres18_ibn", "cares18_ibn", "emares18_ibn"};
+    static const char* const kArch[3] = {"seres18_ibn", "cares18_ibn", "emares18_ibn"};
+    if (ctx->hw_siblings && wt.arch == 2) {
+        reid_set_error("%s: input size %d x %d: loaded architecture %s has no any-size tail; with reid_ctx_set_hw_siblings 1 only cares18_ibn "
+                       "runs at sizes other than 256 x 128 beside seres18_ibn", who, h, w, kArch[wt.arch]);
+        return REID_ERR_ARG;
+    }
+    const bool arch_ok = wt.arch == 0 || (wt.arch == 1 && ctx->hw_siblings);
+    if (!arch_ok || (ctx->hw_precision < 0 && ctx->precision != 0)) {   // reid_ctx_set_hw_precision 0 / 2 names the arithmetic itself
         reid_set_error("%s: input size %d x %d runs seres18_ibn in precision mode 0 (exact fp32) only; loaded architecture %s, precision "
                        "mode %d (256 x 128 runs every architecture and mode)", who, h, w, kArch[wt.arch], ctx->precision);
         return REID_ERR_ARG;
@@ -1570,6 +1609,10 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
     if (ctx->hw_precision == 2) {
         const AnysizeX3Api* x3;
         REID_TRY(anysize_x3_api(&x3));
+    }
+    if (wt.arch == 1 && ctx->any_ca != 0) {
+        const AnysizeCaApi* ca;
+        REID_TRY(anysize_ca_api(&ca));
     }
     return REID_OK;
 }
@@ -1618,6 +1661,30 @@ int launch_any_se_tail(reid_ctx* ctx, const float* y, const float* sc, int n, in
     const hipError_t e = api->se_tail(ctx->stream, y, sc, n, hw, c, mid, w1, w2t, pooled, out, gate_out);
     prof_end(ctx);
     return any_launched(e, "anysize_se_tail");
+}
+
+int launch_any_ca_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int H, int W, int C, const float* prm, float* out,
+                       const float** maps_out, const float** gates_out) {
+    const AnysizeCaApi* api;
+    REID_TRY(anysize_ca_api(&api));
+    const size_t bytes = api->ws_bytes(n, H, W, C);
+    if (!bytes) {
+        reid_set_error("libreid_hip_anysize_ca.so: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", H, W,
+                       C, n);
+        return REID_ERR_ARG;
+    }
+    void* ws;
+    REID_TRY(ctx_ws(ctx, "any.ca", bytes, &ws));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * H * W * C * 20.0);
+    const hipError_t e = api->tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
+    prof_end(ctx);
+    if (e != hipSuccess) {
+        reid_set_error("libreid_hip_anysize_ca.so anysize_ca_tail -> %s", hipGetErrorString(e));
+        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+    }
+    if (maps_out) *maps_out = (const float*)ws;
+    if (gates_out) *gates_out = (const float*)ws + (size_t)n * 2 * ((size_t)H * W + (size_t)C * W + (size_t)H * C);
+    return REID_OK;
 }
 
 int launch_any_gem(reid_ctx* ctx, const float* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out,
@@ -1788,7 +1855,12 @@ static int seres18_trunk_any(reid_ctx* ctx, const AnyBufs& b, int n, float* d_em
             shortcut = sc;
         }
         float* out = c1;   // conv1's output is dead after conv2
-        REID_TRY(launch_any_se_tail(ctx, y, shortcut, n, hw, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr));
+        if (wt.arch == 1) {   // CARes18_IBN: TripletAttention + shortcut + ReLU (CARes18.py:150-157); any_ca 0: the 256 x 128 forward's kernels
+            if (ctx->any_ca) REID_TRY(launch_any_ca_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out));
+            else REID_TRY(launch_ta_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out));
+        } else {
+            REID_TRY(launch_any_se_tail(ctx, y, shortcut, n, hw, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr));
+        }
         stage[2 + i] = out;
         cur = out;
         H = Ho;

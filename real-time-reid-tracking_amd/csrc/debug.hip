@@ -26,7 +26,7 @@ const Switch kSwitches[] = {
     {"split_x3", &reid_ctx::split_x3}, {"x3_ablate", &reid_ctx::x3_ablate}, {"x3_unroll", &reid_ctx::x3_unroll}, {"x3_narrow", &reid_ctx::x3_narrow}, {"conv_x3s", &reid_ctx::conv_x3s}, {"x3s_sk_cap", &reid_ctx::x3s_sk_cap}, {"x3_l4_narrow_nmt", &reid_ctx::x3_l4_narrow_nmt}, {"split_x3_small", &reid_ctx::split_x3_small}, {"split_x3_min_blocks", &reid_ctx::split_x3_min_blocks}, {"f32_dist_bk16", &reid_ctx::f32_dist_bk16}, {"lin_x3", &reid_ctx::lin_x3},
     {"host_pipeline", &reid_ctx::host_pipeline}, {"x3_sk_cap", &reid_ctx::x3_sk_cap}, {"chain", &reid_ctx::chain}, {"split_gemm_min_tiles", &reid_ctx::split_gemm_min_tiles},
     {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc}, {"gem_tail_min", &reid_ctx::gem_tail_min}, {"anysize_force", &reid_ctx::anysize_force},
-    {"any_front", &reid_ctx::any_front},
+    {"any_front", &reid_ctx::any_front}, {"any_ca", &reid_ctx::any_ca},
 };
 }  // namespace
 
@@ -742,6 +742,29 @@ extern "C" int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, 
     REID_TRY(launch_any_gem(ctx, dx, n, hw, c, dp, dsc, dsh, dg, de));
     if (dg) REID_TRY(dbg_download(ctx, gem_out, dg, ne));
     REID_TRY(dbg_download(ctx, emb, de, ne));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// The TripletAttention tail of libreid_hip_anysize_ca.so (anysize_ca.h; tests/test_gpu_anysize_ca.py) through launch_any_ca_tail, the function
+// the any-size forward calls.  The workspace is set to 0xff bytes with one guard pixel behind it before the launch, as out is.
+extern "C" int reid_debug_any_ca_tail(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const float* y, const float* shortcut,
+                                      float* out, float* maps, float* gates) {
+    ARG_CHECK(ctx && n >= 1 && h >= 1 && w >= 1 && c >= 64 && prm && y && shortcut && out);
+    CTX_ENTER(ctx);
+    const size_t ny = (size_t)n * h * w * c, per = (size_t)h * w + (size_t)c * w + (size_t)h * c;
+    float *dprm, *dy, *dsc, *dout, *dws;
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", prm, (size_t)300, &dprm));
+    REID_TRY(dbg_upload(ctx, "dbgt.x", y, ny, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgt.sc", shortcut, ny, &dsc));
+    REID_TRY(dbg_output(ctx, "dbgt.out", ny + c, &dout));
+    REID_TRY(dbg_output(ctx, "any.ca", (size_t)n * 3 * per + c, &dws));   // the workspace launch_any_ca_tail takes: grown first, so it is this one
+    const float *dmaps, *dgates;
+    REID_TRY(launch_any_ca_tail(ctx, dy, dsc, n, h, w, c, dprm, dout, &dmaps, &dgates));
+    ARG_CHECK(dmaps == dws && dgates == dws + (size_t)n * 2 * per);
+    REID_TRY(dbg_download(ctx, out, dout, ny + c));
+    REID_TRY(dbg_download(ctx, maps, dmaps, (size_t)n * 2 * per));
+    REID_TRY(dbg_download(ctx, gates, dgates, (size_t)n * per + c));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }

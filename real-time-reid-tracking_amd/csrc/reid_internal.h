@@ -513,6 +513,9 @@ struct reid_ctx {
                              // 2 (default) = the kernel where it measured faster - passes of at most ANY_FRONT_MAX_STEM_PIXELS - else the launches
     int hw_precision = -1;   // reid_ctx_set_hw_precision: the arithmetic of the any-size forward: -1 = it needs the context in mode 0 (default),
                              // 0 = exact fp32 whatever the mode, 2 = fp32-class whatever the mode (libreid_hip_anysize_x3.so)
+    int hw_siblings = 0;     // reid_ctx_set_hw_siblings: 1 = a loaded cares18_ibn runs at other sizes too (libreid_hip_anysize_ca.so)
+    int any_ca = 1;          // libreid_hip_debug.so switch: the TripletAttention tail of the any-size trunk: 1 = libreid_hip_anysize_ca.so,
+                             // 0 = launch_ta_tail (attention_f32.hip), for A/B timing of whole passes in one process
     int any_conv_form = 0;   // the tile form the last fp32-class any-size convolution launched (anysize_x3.h), written on the host only
     unsigned long long* conv_diag = nullptr;   // experiments (debug.hip): stamps of the loader-wave conv kernel
     // Which launch the last f16 convolution launcher made, written on the host only (harnesses read it, include/reid_hip_debug.h:
@@ -780,7 +783,8 @@ int bank_geometry(const reid_bank* b, int* max_tracks, int* budget, int* d);
 int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns);
 // ---- ResNet18-IBN-SE at input sizes other than 256 x 128 (api.hip; kernels: anysize.h).  The reid_*_hw entries hand 256 x 128 to the
 // existing entries unless the debug switch anysize_force is set (se_any_routes).  se_any_ready: everything such a call would refuse, with
-// nothing queued - a side outside 32 .. 512 (REID_ERR_ARG), weights not loaded (REID_ERR_STATE), an architecture other than seres18_ibn or
+// nothing queued - a side outside 32 .. 512 (REID_ERR_ARG), weights not loaded (REID_ERR_STATE), an architecture other than seres18_ibn
+// (or, with reid_ctx_set_hw_siblings 1, cares18_ibn, which then needs libreid_hip_anysize_ca.so: REID_ERR_STATE) or
 // a precision mode other than 0 while reid_ctx_set_hw_precision is -1 (REID_ERR_ARG naming both), libreid_hip_anysize.so and, at
 // hw_precision 2, libreid_hip_anysize_x3.so (REID_ERR_STATE).  se_any_pass: images per pass, the
 // context's chunk scaled by 256 * 128 / (h * w) and clamped to 1 .. 4096.  se_any_run_nchw: one pass from fp32 NCHW [m][3][h][w] on the
@@ -808,6 +812,11 @@ int launch_any_se_tail(reid_ctx* ctx, const float* y, const float* sc, int n, in
                        float* out, float* gate_out);
 int launch_any_gem(reid_ctx* ctx, const float* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out,
                    float* emb);
+// the TripletAttention tail of the any-size trunk (cares18_ibn; anysize_ca.h) on device operands [n][H][W][C], prm = Se18Block::ta; the
+// workspace ("any.ca", anysize_ca_workspace_bytes) comes from ctx_ws.  maps_out / gates_out (may be NULL): where the call's maps and gates
+// lie in it, in the layout of anysize_ca.h, valid until the next call.  The forward and reid_debug_any_ca_tail call this one function.
+int launch_any_ca_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int H, int W, int C, const float* prm, float* out,
+                       const float** maps_out = nullptr, const float** gates_out = nullptr);
 // one trunk convolution of the any-size forward (NHWC fp32 in / out, folded BN, identity residual, ReLU from column relu_from on) in the
 // arithmetic `arith`: 0 = launch_gemm_f32 (exact fp32), 2 = any_conv_x3_kernel of libreid_hip_anysize_x3.so (fp32-class; R = 3 pad 1 or
 // R = 1 pad 0) on the cached split form of wgt.  The forward and reid_debug_any_conv call this one function.

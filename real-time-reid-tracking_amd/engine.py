@@ -212,6 +212,44 @@ class Engine:
                         pass
         return scope()
 
+    @staticmethod
+    def hw_siblings_value(v):
+        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_siblings); ValueError otherwise, before any device call."""
+        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+            return int(v)
+        raise ValueError("hw_siblings must be False / 0 (other input sizes run seres18_ibn only) or True / 1 (cares18_ibn too), got %r" % (v,))
+
+    def set_hw_siblings(self, on):
+        """CARes18-IBN at input sizes other than 256 x 128 (reid_ctx_set_hw_siblings): False (default) = the reid_*_hw entries refuse a
+        loaded cares18_ibn at another size, True = it runs there with the TripletAttention tail of libreid_hip_anysize_ca.so, under the
+        size, precision and pass-size rules of seres18_ibn.  emares18_ibn stays refused; 256 x 128 is not affected."""
+        v = Engine.hw_siblings_value(on)
+        check(self.lib.reid_ctx_set_hw_siblings(self.h, v))
+        self._hw_siblings = bool(v)
+
+    @property
+    def hw_siblings(self):
+        """What set_hw_siblings set last (the library's default is False)."""
+        return getattr(self, "_hw_siblings", False)
+
+    def hw_siblings_scope(self, on):
+        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            if on is None:
+                yield self
+                return
+            prev = self.hw_siblings
+            self.set_hw_siblings(on)
+            try:
+                yield self
+            finally:
+                if self.hw_siblings != prev:
+                    self.set_hw_siblings(prev)
+        return scope()
+
     def set_side_index(self, index):
         """Camera (ResNet18-IBN-SE: SERes18_IBN.py:269-270) or view (Swin: swin_transformer.py:301-302) index of every image of
         the following embed call; ``None`` / empty clears."""
@@ -781,7 +819,8 @@ class Engine:
 
     def embed_f32_nchw(self, x, logits=False):
         """float32 [n,3,H,W] -> float32 [n,512] (and logits).  (256, 128) runs the loaded architecture in the context's precision;
-        any other H, W in 32 .. 512 the any-size forward (reid_embed_f32_nchw_hw: seres18_ibn weights, exact fp32)."""
+        any other H, W in 32 .. 512 the any-size forward (reid_embed_f32_nchw_hw: seres18_ibn weights - cares18_ibn with set_hw_siblings(True) -
+        in exact fp32, or the arithmetic set_hw_precision names)."""
         x = _f32(x)
         if x.ndim != 4 or x.shape[1] != 3:
             raise ValueError("embed_f32_nchw expects float32[n,3,H,W] (%d x %d, or sides in [%d, %d]), got %s"
@@ -1407,6 +1446,21 @@ class Engine:
             self.h, _ptr(x), _ptr(w1), _ptr(_f32(b1)), _ptr(w2), _ptr(_f32(b2)), _ptr(r), C.c_int(m), C.c_int(c), C.c_int(hid),
             C.c_int(int(bool(act)) | 2 * int(ln is not None) | 4 * int(bool(alias))), _ptr(g), _ptr(b), _ptr(raw))
         return int(st), raw, front
+
+    def debug_any_ca_tail(self, y, shortcut, prm):
+        """The TripletAttention tail of libreid_hip_anysize_ca.so through the any-size forward's launcher (reid_debug_any_ca_tail): y,
+        shortcut [n, h, w, c], prm [3, 100].  Returns (out [n h w c + c], maps [n, 2 per], gates [n per + c]) in the layouts of
+        include/reid_hip_debug.h, guards included."""
+        y, shortcut, prm = _f32(y), _f32(shortcut), _f32(prm)
+        n, h, w, c = y.shape
+        if shortcut.shape != y.shape or prm.size != 300:
+            raise ValueError("debug_any_ca_tail: operand shapes")
+        per = h * w + c * w + h * c
+        out = np.empty(y.size + c, np.float32)
+        maps = np.empty((n, 2 * per), np.float32)
+        gates = np.empty(n * per + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_ca_tail(self.h, n, h, w, c, _ptr(prm), _ptr(y), _ptr(shortcut), _ptr(out), _ptr(maps), _ptr(gates)))
+        return out, maps, gates
 
     def debug_any_norm(self, x, half, in_gamma, in_beta, bn_scale=None, bn_shift=None):
         x = _f32(x)

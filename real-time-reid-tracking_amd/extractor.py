@@ -34,7 +34,7 @@ def pack_checkpoint(state_dict):
 
 
 class Extractor(object):
-    def __init__(self, model_path, use_cuda=True, device=0, precision=None, size=None):
+    def __init__(self, model_path, use_cuda=True, device=0, precision=None, size=None, hw_siblings=False):
         """``Extractor(model_path, use_cuda=True)`` as feature_extractor.py:15-29.  ``precision`` (keyword, not in the reference):
         "f16x3" (default; $REID_PRECISION overrides the default) / "f32" / "f16" - see precision.py; a checkpoint the fp32-class
         arithmetic cannot represent runs in exact fp32, with one log line.  ``size`` (keyword, (W, H) like ``self.size``): the size
@@ -42,11 +42,15 @@ class Extractor(object):
         seres18_ibn checkpoint any (W, H) with sides in 32 .. 512 (DeepSORT's own (64, 128), feature_extractor.py:23) when its
         arithmetic is asked for by name: ``precision="f32"`` (exact fp32) or ``precision="f16x3"`` (fp32-class, the any-size forward's
         reid_ctx_set_hw_precision 2 around every call) must be given - $REID_PRECISION is a default, not a name, and nothing is demoted
-        behind the caller's back - and the object's log line names size and arithmetic."""
+        behind the caller's back - and the object's log line names size and arithmetic.  ``hw_siblings=True`` (keyword) lets a cares18_ibn
+        checkpoint take such a size too, under the same rule: Engine.set_hw_siblings(True) around every call (the TripletAttention tail
+        of libreid_hip_anysize_ca.so); emares18_ibn has no other size."""
         if not use_cuda:
             raise RuntimeError("Extractor: the MI355X engine has no CPU path (use_cuda=False is not supported)")
         self.device = "cuda"
         self._mode = _precision.resolve(precision)
+        from .engine import Engine as _Engine
+        self._hw_siblings = bool(_Engine.hw_siblings_value(hw_siblings))      # a bad value raises here, before any device call
         if isinstance(model_path, dict):
             state_dict = model_path            # already-loaded state_dict (tests, benchmarks)
         else:
@@ -65,7 +69,8 @@ class Extractor(object):
             if size is not None and tuple(size) != self.size:
                 from .engine import check_hw
                 h, w = check_hw(tuple(size)[::-1])
-                if self.info.get("arch") != "seres18_ibn" or precision is None or self._mode == _precision.F16:
+                sized = ("seres18_ibn", "cares18_ibn") if self._hw_siblings else ("seres18_ibn",)
+                if self.info.get("arch") not in sized or precision is None or self._mode == _precision.F16:
                     raise ValueError("Extractor: at a size other than (W, H) = (128, 256) the ResNet18-IBN family runs seres18_ibn "
                                      "checkpoints in exact fp32 (precision=\"f32\") or fp32-class (precision=\"f16x3\"), asked for by "
                                      "name; got size %r, %s, precision %s"
@@ -111,7 +116,8 @@ class Extractor(object):
             # another size: the fp32-class arithmetic is the any-size forward's own setting, put on for the call and taken off after it; after
             # a fall back (precision.run) the object is exact fp32 and the setting stays as the engine has it
             def scoped(eng):
-                with eng.hw_precision_scope(2 if self._mode == _precision.F32_CLASS else None):
+                sib = True if self._hw_siblings and self.info.get("arch") == "cares18_ibn" else None
+                with eng.hw_precision_scope(2 if self._mode == _precision.F32_CLASS else None), eng.hw_siblings_scope(sib):
                     return fn(eng)
             return _precision.run(self, self.net, "Extractor", scoped)
         return _precision.run(self, self.net, "Extractor", fn)

@@ -18,13 +18,15 @@ def show_avai_models():
     print(list(__model_factory.keys()))
 
 
-def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True, precision=None, version=None, hw_precision=None):
+def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True, precision=None, version=None, hw_precision=None, hw_siblings=None):
     """Same signature, same ``KeyError`` text as models/__init__.py:93-121; constructors are called with
     (num_classes, loss, pretrained, use_gpu).  ``precision`` (keyword, this engine's addition): the arithmetic the model runs
     in - None = $REID_PRECISION, else "f16x3", the mode bench.py reports (precision.py).  ``version`` (keyword): "v1" / "v2" of
     'swin_transformer', the reference's ``swin_t(..., version=)`` (image_reid_inference.py:202-208); other names take none.
     ``hw_precision`` (keyword): 'seres18_ibn' at inputs other than 256 x 128 - None = exact fp32 for such a call, "f16x3" = the fp32-class
-    arithmetic (backbone.SERes18IBN); the siblings have no other size and the Swin takes none."""
+    arithmetic (backbone.SERes18IBN); the Swin takes none.
+    ``hw_siblings`` (keyword): True lets 'cares18_ibn' take inputs other than 256 x 128 too (backbone.CARes18IBN, Engine.set_hw_siblings);
+    every other name takes none."""
     avai_models = list(__model_factory.keys())
     if name not in avai_models:
         raise KeyError('Unknown model: {}. Must be one of {}'.format(name, avai_models))
@@ -37,4 +39,8 @@ def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True
         if name == 'swin_transformer':
             raise ValueError("model '{}' has no hw_precision argument".format(name))
         extra['hw_precision'] = hw_precision
+    if hw_siblings is not None:
+        if name != 'cares18_ibn':
+            raise ValueError("model '{}' has no hw_siblings argument".format(name))
+        extra['hw_siblings'] = hw_siblings
     return __model_factory[name](num_classes=num_classes, loss=loss, pretrained=pretrained, use_gpu=use_gpu, precision=precision, **extra)

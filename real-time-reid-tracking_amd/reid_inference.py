@@ -46,11 +46,13 @@ def dbscan_pseudo_labels(dists, eps=0.5, min_samples=5):
     return DBSCAN(eps=eps, min_samples=min_samples, metric="precomputed", n_jobs=-1).fit_predict(dists)
 
 
-ARCHS = ("seres18", "swin", "seres18_hw")
+ARCHS = ("seres18", "swin", "seres18_hw", "cares18_hw")
+HW_ARCHS = ("seres18_hw", "cares18_hw")
 # "seres18_hw": the ResNet path at the images' own size - the script's --dataset veri runs the ResNet family at
 # Resize((224, int(ratio * 224))), ratio the mean width / height of the dataset (data_transforms.py:121, image_reid_inference.py:169-180).
 # Float images carry the size, uint8 images are resized to ``size`` (required); seres18_ibn weights, exact fp32 (reid_*_hw).  The default
 # "seres18" stays fixed at 256 x 128, every architecture of the family and every precision mode.
+# "cares18_hw": the same with cares18_ibn weights (the script's --backbone cares18): Engine.set_hw_siblings(True) for the call, restored after it.
 
 
 def _descriptor_width(engine, arch):
@@ -71,7 +73,7 @@ def _check_images(images, arch):
         if images.ndim != 4 or images.shape[1] != 3 or images.shape[2] <= 0 or images.shape[3] <= 0 or images.shape[2] % 224 or \
                 images.shape[3] % 224:
             raise ValueError("images must be float32 [n,3,h,w] with h, w multiples of 224, got %s" % (images.shape,))
-    elif arch == "seres18_hw":
+    elif arch in HW_ARCHS:
         if images.ndim != 4 or images.shape[1] != 3:
             raise ValueError("images must be float32 [n,3,h,w], got %s" % (images.shape,))
         check_hw(images.shape[2:])
@@ -95,9 +97,9 @@ def _check_u8_images(images, arch, size):
     from .engine import Engine
     if arch == "swin":
         h, w, _ = Engine._swin_crop_args((448, 224) if size is None else size, None)
-    elif arch == "seres18_hw":
+    elif arch in HW_ARCHS:
         if size is None:
-            raise ValueError("arch='seres18_hw' resizes uint8 images to size=(H, W), which must be given")
+            raise ValueError("arch='%s' resizes uint8 images to size=(H, W), which must be given" % arch)
         h, w = check_hw(size)
     else:
         if size is not None and tuple(int(v) for v in size) != (IMG_H, IMG_W):
@@ -125,8 +127,8 @@ def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width
                 engine.set_side_index(view_index[i:i + bs])
             rows = engine.swin_descriptor_images_u8(part, size=size, flip_tta=flip)
         elif strong_offsets is not None:
-            rows = engine.descriptor_images_u8_shift(part, strong_offsets[i:i + bs], pad=pad, size=size if arch == "seres18_hw" else None)
-        elif arch == "seres18_hw":
+            rows = engine.descriptor_images_u8_shift(part, strong_offsets[i:i + bs], pad=pad, size=size if arch in HW_ARCHS else None)
+        elif arch in HW_ARCHS:
             rows = engine.descriptor_images_u8(part, flip_tta=flip, size=size)
         else:
             rows = engine.descriptor_images_u8(part, flip_tta=flip)
@@ -164,7 +166,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     ``size`` = (H, W) (required), e.g. the script's VeRi geometry ``size=(224, int(ratio * 224))``; seres18_ibn weights with the context in
     exact fp32 (``reid_descriptor_f32_nchw_hw_dev`` / ``reid_descriptor_images_u8_hw``), or - ``hw_precision`` "f32" / "f16x3"
     (``Engine.set_hw_precision``) - in the arithmetic named, whatever the context's mode: set for this call and restored after it; None
-    leaves the engine's setting alone.
+    leaves the engine's setting alone.  ``arch="cares18_hw"``: the same entries on cares18_ibn weights (the script's --backbone cares18 with
+    --dataset veri), ``Engine.set_hw_siblings(True)`` for this call and restored after it.
 
     ``strong_offsets``: int [n, 2] of (top, left) per image with ``pad`` (data_transforms.strong_inference_offsets): the second view is the
     script's strong_inference one - the mirror shifted by (top - pad, left - pad) over a black border, black being (0 - mean) / std of the
@@ -172,8 +175,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     script gives the Swin the plain mirror.  None is today's call and bits."""
     if hw_precision is not None:
         from .engine import Engine
-        if arch != "seres18_hw":
-            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw'; arch=%r takes none" % (arch,))
+        if arch not in HW_ARCHS:
+            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw'; arch=%r takes none" % (arch,))
         Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
     if strong_offsets is not None:
         strong_offsets, pad = _check_strong(arch, flip, strong_offsets, len(images), pad)
@@ -196,9 +199,9 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
         if view_index.shape[0] != n or (n and (view_index.min() < 0 or view_index.max() >= 2 ** 31)):
             raise ValueError("view_index must hold one non-negative index per image (%d), got %d" % (n, view_index.shape[0]))
         view_index = view_index.astype(np.int32)
-    if hw_precision is not None:                     # every argument is checked: the setting goes on for the device work and off after it
-        with engine.hw_precision_scope(hw_precision):
-            return inference_efficient(engine, images, d_out, flip, bs, arch, view_index, size if u8 else None,
+    if hw_precision is not None or arch == "cares18_hw":   # every argument is checked: the settings go on for the device work and off after it
+        with engine.hw_precision_scope(hw_precision), engine.hw_siblings_scope(True if arch == "cares18_hw" else None):
+            return inference_efficient(engine, images, d_out, flip, bs, "seres18_hw", view_index, size if u8 else None,
                                        strong_offsets=strong_offsets, pad=pad)
     if u8:
         return _inference_u8(engine, images, d_out, flip, int(bs), arch, view_index, size, width, strong_offsets, pad)
@@ -217,7 +220,7 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
                 engine.swin_descriptor_dev(stage.ptr, part.shape[0], part.shape[2], part.shape[3], flip, d_out + i * width * 4)
             elif strong_offsets is not None:
                 engine.descriptor_shift_dev(stage.ptr, part.shape[0], part.shape[2:], strong_offsets[i:i + bs], pad, fill, d_out + i * width * 4)
-            elif arch == "seres18_hw":
+            elif arch in HW_ARCHS:
                 engine.descriptor_dev(stage.ptr, part.shape[0], flip, d_out + i * width * 4, size=part.shape[2:])
             else:
                 engine.descriptor_dev(stage.ptr, part.shape[0], flip, d_out + i * width * 4)
@@ -241,7 +244,8 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     = (H, W) is what a Swin resizes them to (default (448, 224); the ResNet family is fixed at 256x128 unless ``arch="seres18_hw"``, which
     runs seres18_ibn weights in exact fp32 at the float images' own size or at ``size``: VeRi is ``size=(224, int(ratio * 224))``;
     ``hw_precision`` "f32" / "f16x3" names that forward's arithmetic for this call - ``Engine.set_hw_precision``, restored afterwards - and
-    None leaves the engine's setting alone).
+    None leaves the engine's setting alone; ``arch="cares18_hw"`` is the same for cares18_ibn weights, with ``Engine.set_hw_siblings(True)``
+    for the call).
     ``strong_inference`` / ``strong_offsets``: the script's second view for the ResNet family (--backbone seres18 / cares18,
     image_reid_inference.py:179-181) - the mirror shifted by up to +-``pad`` pixels on each axis over a black border.
     ``strong_offsets`` is int [ng + nq, 2] of (top, left) per image, gallery first; ``strong_inference=True`` without offsets draws them
@@ -271,8 +275,8 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
         attr_rows = tricks.normalize_rows(attr_rows)
     if hw_precision is not None:
         from .engine import Engine
-        if arch != "seres18_hw":
-            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw'; arch=%r takes none" % (arch,))
+        if arch not in HW_ARCHS:
+            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw'; arch=%r takes none" % (arch,))
         Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
     if arch not in ARCHS:
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))

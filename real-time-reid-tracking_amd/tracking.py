@@ -31,18 +31,22 @@ def _two_streams(stream, on):
     stream.eng.frame_match_stream(stream.match_stream)
 
 
+HW_ARCHS = ("seres18_hw", "cares18_hw")   # the any-size forward: seres18_ibn, and cares18_ibn with Engine.set_hw_siblings(True)
+
+
 def _check_arch(arch, size, mean_std, hw_precision=None):
     """`arch`, `size`, `mean_std`, `hw_precision` of the stream classes, checked before any device call (ValueError)."""
     if arch == "swin":
         Engine._swin_crop_args(size, mean_std)
-    elif arch == "seres18_hw":
+    elif arch in HW_ARCHS:
         Engine._hw_crop_args(size, mean_std)
     elif arch != "seres18":
-        raise ValueError("arch must be 'seres18', 'seres18_hw' or 'swin', got %r" % (arch,))
+        raise ValueError("arch must be 'seres18', 'seres18_hw', 'cares18_hw' or 'swin', got %r" % (arch,))
     elif tuple(size) != (224, 224) or mean_std is not None:
-        raise ValueError("size / mean_std belong to arch='swin' and 'seres18_hw' (a 'seres18' crop is always 256x128, normalised with 0.5 / 0.5)")
-    if hw_precision is not None and arch != "seres18_hw":
-        raise ValueError("hw_precision belongs to arch='seres18_hw', got arch %r" % (arch,))
+        raise ValueError("size / mean_std belong to arch='swin' and 'seres18_hw' / 'cares18_hw' (a 'seres18' crop is always 256x128, normalised "
+                         "with 0.5 / 0.5)")
+    if hw_precision is not None and arch not in HW_ARCHS:
+        raise ValueError("hw_precision belongs to arch='seres18_hw' / 'cares18_hw', got arch %r" % (arch,))
     Engine.hw_precision_value(hw_precision)
 
 
@@ -52,13 +56,16 @@ def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_prec
     is resized to ``size`` = (H, W) multiples of 224 and normalised with ``mean_std`` (None: ImageNet), and the embeddings, the bank
     and the cost stage are 96 wide; "seres18_hw" - a ResNet18-IBN-SE (seres18_ibn) tracker at another crop size, Extractor(size=) of
     feature_extractor.py:31-46 - resizes every crop to ``size`` = (H, W), sides 32 .. 512, normalises with ``mean_std`` (None: 0.5 / 0.5)
-    and runs the any-size forward in the arithmetic ``hw_precision`` names (`Engine.set_hw_precision`); frames are 512 wide."""
+    and runs the any-size forward in the arithmetic ``hw_precision`` names (`Engine.set_hw_precision`); frames are 512 wide; "cares18_hw" - the same with a CARes18-IBN (cares18_ibn) checkpoint: the context's
+    `Engine.set_hw_siblings` is switched on, and stays on for the stream's life."""
     if arch == "swin":
         stream.eng.load_swin(weights_blob, manifest)
     else:
         stream.eng.load_seres18(weights_blob, manifest)
-    if arch == "seres18_hw":
+    if arch in HW_ARCHS:
         stream.eng.set_hw_precision(hw_precision)
+    if arch == "cares18_hw":
+        stream.eng.set_hw_siblings(True)
     stream.arch, stream.size, stream.mean_std = arch, size, mean_std
 
 
@@ -66,7 +73,7 @@ def _frame_submit(stream, slot, crops):
     """What every class's `_submit` hook ends in: the frame's crops into `slot` through the stream's backbone."""
     if getattr(stream, "arch", "seres18") == "swin":
         return stream.eng.frame_submit_swin(slot, crops, stream.size, stream.mean_std)
-    if getattr(stream, "arch", "seres18") == "seres18_hw":
+    if getattr(stream, "arch", "seres18") in HW_ARCHS:
         return stream.eng.frame_submit_hw(slot, crops, stream.size, stream.mean_std)
     return stream.eng.frame_submit(slot, crops)
 
