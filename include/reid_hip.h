@@ -149,7 +149,7 @@ int reid_embed_frame_u8(reid_ctx* ctx, const uint8_t* frame_hwc, int fh, int fw,
                         float* emb, float* logits);
 /* reid_embed_frame_u8 at out_h x out_w: DeepSort._get_features' windows ([external] deep_sort.py) through Extractor._preprocess of an
  * extractor built at another size (feature_extractor.py:31-46).  Size, mean_std6 and refusals as reid_embed_ragged_u8_hw: (256, 128) is
- * reid_embed_frame_u8 (every architecture and mode, mean_std6 NULL or 0.5 / 0.5); any other size (sides 32 .. 512) runs seres18_ibn (with reid_ctx_set_hw_siblings 1 also cares18_ibn) under the
+ * reid_embed_frame_u8 (every architecture and mode, mean_std6 NULL or 0.5 / 0.5); any other size (sides 32 .. 512) runs seres18_ibn (with reid_ctx_set_hw_siblings 1 also cares18_ibn, with reid_ctx_set_hw_ema 1 also emares18_ibn) under the
  * reid_ctx_set_hw_precision rule, opened by the fused resize + stem + max-pool kernel of libreid_hip_anysize_front.so, which must lie
  * beside this library like libreid_hip_anysize.so (REID_ERR_STATE naming the missing file, before anything is queued).  The embeddings
  * are those of reid_embed_ragged_u8_hw on the same pixels, bit for bit. */
@@ -336,7 +336,7 @@ int reid_swin_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const i
  *   other sizes  a second forward, generic in H and W, for seres18_ibn weights in precision mode 0 (exact fp32): the convolutions on the
  *                generic implicit-GEMM kernel, InstanceNorm / SE / GeM for any number of pixels from libreid_hip_anysize.so, which must
  *                lie beside this library (REID_ERR_STATE naming it otherwise).  Another architecture or precision mode is REID_ERR_ARG
- *                naming both - nothing falls back (cares18_ibn runs with reid_ctx_set_hw_siblings 1, below).  A pass is chunk * 256 * 128 / (h * w) images, clamped to 1 .. 4096, so it needs no
+ *                naming both - nothing falls back (cares18_ibn runs with reid_ctx_set_hw_siblings 1, emares18_ibn with reid_ctx_set_hw_ema 1, below).  A pass is chunk * 256 * 128 / (h * w) images, clamped to 1 .. 4096, so it needs no
  *                more workspace than a pass of the 256 x 128 forward; results do not depend on the pass size.  Pending side indices
  *                (camera bias) apply as in the entries without _hw; reid_debug_stage reads the taps of the last pass, each
  *                [n][Ho][Wo][C] of its own map size.
@@ -358,7 +358,7 @@ int reid_swin_descriptor_images_u8(reid_ctx* ctx, const uint8_t* packed, const i
  *                 the split range (|w| 2^11 >= 65504) makes the call fail with REID_ERR_ARG naming the tensor, as reid_ctx_set_precision(2)
  *                 does, and so does loading one while v == 2.
  *   Any other value is REID_ERR_ARG.  (256, 128) is not affected by v, and cares18_ibn / emares18_ibn stay refused at other sizes (cares18_ibn:
- *   unless reid_ctx_set_hw_siblings below is 1, and then under this rule too). */
+ *   unless reid_ctx_set_hw_siblings below is 1, emares18_ibn: unless reid_ctx_set_hw_ema below is 1, and then under this rule too). */
 int reid_ctx_set_hw_precision(reid_ctx* ctx, int v);
 /* reid_ctx_set_hw_siblings(ctx, on): CARes18-IBN at input sizes other than 256 x 128, a setting of its own because the refusal above is
  * what callers of the default see.
@@ -370,9 +370,23 @@ int reid_ctx_set_hw_precision(reid_ctx* ctx, int v);
  *                with exact-fp32 stem and tails), the pass sizes and the side indices are those of seres18_ibn; every reid_*_hw entry,
  *                the _shift entries, reid_embed_frame_u8_hw and reid_frame_submit_hw follow.  emares18_ibn stays REID_ERR_ARG (its tail
  *                keeps a channel group's slab in LDS, which bounds the map): the message names it and says that only cares18_ibn has an
- *                any-size tail.
+ *                any-size tail (emares18_ibn has a setting of its own, reid_ctx_set_hw_ema below).
  *   Any other value is REID_ERR_ARG.  (256, 128) is never affected. */
 int reid_ctx_set_hw_siblings(reid_ctx* ctx, int on);
+/* reid_ctx_set_hw_ema(ctx, on): EMARes18-IBN at input sizes other than 256 x 128, a setting of its own because the two refusals above are
+ * what callers of the defaults see.
+ *   0 (default)  as above: at another size every reid_*_hw entry refuses a loaded emares18_ibn, status and message unchanged (the message
+ *                under reid_ctx_set_hw_siblings 1 included).
+ *   1            a loaded emares18_ibn runs at another size through the any-size forward with the EMA block tail of
+ *                libreid_hip_anysize_ema.so (csrc/anysize_ema.h: no slab in LDS, fp64 sums in a fixed order, fp32 convolutions and gates),
+ *                whatever reid_ctx_set_hw_siblings is.  The library must lie beside this one (REID_ERR_STATE naming it otherwise, before
+ *                anything is queued and before a frame slot is touched).  The size range (32 .. 512 per side), the
+ *                reid_ctx_set_hw_precision rule (-1 needs mode 0, 0 exact fp32, 2 fp32-class convolutions with exact-fp32 stem and
+ *                tails), the pass sizes and the side indices are those of seres18_ibn; every reid_*_hw entry, the _shift entries,
+ *                reid_embed_frame_u8_hw and reid_frame_submit_hw follow.  cares18_ibn is not affected: it still needs
+ *                reid_ctx_set_hw_siblings 1.
+ *   Any other value is REID_ERR_ARG and changes nothing.  (256, 128) is never affected. */
+int reid_ctx_set_hw_ema(reid_ctx* ctx, int on);
 int reid_embed_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits);
 int reid_embed_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits);
 int reid_embed_ragged_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,
@@ -392,7 +406,7 @@ int reid_descriptor_images_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int
  * exactly crop(pad(mirror(x))); (top, left) == (pad, pad) is the plain mirror and then the bits of flip_tta = 1.  Size, architecture,
  * precision, hw_precision, pending side indices (they serve both views), pass sizes and every refusal are those of the entries without
  * _shift: (256, 128) runs every architecture in every mode, another size seres18_ibn (and, with reid_ctx_set_hw_siblings 1,
- * cares18_ibn) under the hw_precision rule.  The view is pure data
+ * cares18_ibn, with reid_ctx_set_hw_ema 1 emares18_ibn) under the hw_precision rule.  The view is pure data
  * movement (shift_mirror_nchw_kernel of libreid_hip_eval_links.so, which must lie beside this library - without the file these calls are
  * REID_ERR_STATE naming it, before anything is queued, and nothing else is affected): at 256 x 128 it writes the workspace the plain
  * mirror is written to, at another size a shifted copy of the pass on which the any-size forward runs unmirrored.

@@ -124,6 +124,20 @@ int reid_debug_any_gem(reid_ctx* ctx, int n, int hw, int c, float p, const float
  * Returns the context's fault status. */
 int reid_debug_any_ca_tail(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const float* y, const float* shortcut, float* out,
                            float* maps, float* gates);
+/* The EMA block tail of libreid_hip_anysize_ema.so (csrc/anysize_ema.h; tests/test_gpu_anysize_ema.py) through the launcher the any-size
+ * forward calls for emares18_ibn, on host operands: y, shortcut NHWC fp32 [n][h][w][c], prm (cg = c / 32) = conv1x1 w [cg][cg], b [cg] |
+ * conv3x3 w [cg][cg][3][3], b [cg] | GroupNorm weight [cg], bias [cg]; 2 <= h, w <= 128, c in {64, 128, 256, 512} (anything else
+ * REID_ERR_ARG).
+ *   out = relu(y * sigmoid(weights[h, w]) + shortcut),  out [n h w c + c] with ONE guard pixel behind the last.
+ * sig / small (may be NULL), in the layout of csrc/anysize_ema.h:
+ *   sig   [n][h + w][c]      rows [0, h) the sigmoid of the 1x1 convolution of the row means, rows [h, h + w) that of the column means
+ *   small [n 4 c + c]        mu | rstd | s1 = softmax(agp(x1)) | s2 = softmax(agp(x2)), [4][c] per image, then ONE guard of c floats
+ * out and the workspace are set to 0xff bytes before the launch: an element the kernels leave alone reads as NaN.
+ * The switch "any_ema" (reid_debug_set_switch) picks the tail of the any-size trunk for emares18_ibn: 1 (default) = this library, 0 =
+ * launch_ema_tail of csrc/attention_f32.hip (REID_ERR_ARG where the group's slab does not fit LDS), for A/B timing of whole passes in one
+ * process.  Returns the context's fault status. */
+int reid_debug_any_ema_tail(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const float* y, const float* shortcut, float* out,
+                            float* sig, float* small);
 /* One trunk convolution of the any-size forward (tests/test_gpu_anysize_x3.py) through the launcher the forward calls, on host operands:
  * x [n][h][w][cin], wgt [cout][r][r][cin], out [n ho wo cout + cout] with ONE guard row (cout floats) behind the last pixel, preset to 0xff
  * bytes with the rest.  r = 3 with pad 1 or r = 1 with pad 0, stride 1 or 2, cin % 32 == 0, cout % 64 == 0.  out = acc * scale + shift (both

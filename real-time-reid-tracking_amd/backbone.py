@@ -87,7 +87,7 @@ class SERes18IBN:
     arch = "seres18_ibn"
 
     def __init__(self, num_classes=751, loss="triplet", pretrained=False, use_gpu=True, seed=0, num_cams=6, cam_factor=-1.0,
-                 precision=None, hw_precision=None, hw_siblings=False, **_):
+                 precision=None, hw_precision=None, hw_siblings=False, hw_ema=False, **_):
         if loss not in ("triplet", "softmax"):
             raise NotImplementedError                      # seres18_ibn(), SERes18_IBN.py:279-285
         self._mode = _precision.resolve(precision)         # "f16x3" unless the argument or $REID_PRECISION says otherwise (precision.py)
@@ -97,6 +97,10 @@ class SERes18IBN:
         self._hw_siblings = bool(Engine.hw_siblings_value(hw_siblings))
         if self._hw_siblings and self.arch != "cares18_ibn":
             raise ValueError("%s has no hw_siblings argument (cares18_ibn only)" % self.arch)
+        # emares18_ibn only: True = inputs of another size run too (Engine.set_hw_ema around such a call)
+        self._hw_ema = bool(Engine.hw_ema_value(hw_ema))
+        if self._hw_ema and self.arch != "emares18_ibn":
+            raise ValueError("%s has no hw_ema argument (emares18_ibn only)" % self.arch)
         self._hw_call = _HwClassCall(self) if hw == 2 else None
         self.num_classes = num_classes
         self.num_cams, self.cam_factor = num_cams, float(cam_factor)   # SERes18_IBN.py:193,198: cam_bias [num_cams,512] and its factor
@@ -205,7 +209,7 @@ class SERes18IBN:
             raise ValueError("expected [N,3,H,W] input, got %s" % (tuple(x.shape),))
         size = check_hw(tuple(x.shape[2:]))
         any_size = size != (IMG_H, IMG_W)
-        if any_size and self.arch != "seres18_ibn" and not getattr(self, "_hw_siblings", False):
+        if any_size and self.arch != "seres18_ibn" and not getattr(self, "_hw_siblings", False) and not getattr(self, "_hw_ema", False):
             raise ValueError("%s runs at [N,3,%d,%d] only (other sizes: seres18_ibn), got %s" % (self.arch, IMG_H, IMG_W, tuple(x.shape)))
         # another size runs the any-size forward: this CALL runs in exact fp32 (mode 0) or, with hw_precision="f16x3", in the fp32-class
         # arithmetic (reid_ctx_set_hw_precision 2 around the call); the model keeps its own mode and the engine gets its settings back
@@ -221,6 +225,14 @@ class SERes18IBN:
                     with e.hw_siblings_scope(True):
                         return fn(e)
                 return inner(scoped)
+        if any_size and getattr(self, "_hw_ema", False):          # emares18_ibn: likewise with the engine's hw_ema
+            inner_ema = run
+
+            def run(fn):
+                def scoped(e):
+                    with e.hw_ema_scope(True):
+                        return fn(e)
+                return inner_ema(scoped)
         if is_torch and x.is_cuda:
             if x.device.index != self._device:
                 self.to(x.device.index)
@@ -307,7 +319,9 @@ class CARes18IBN(SERes18IBN):
 class EMARes18IBN(SERes18IBN):
     """EMARes18_IBN (reid/backbones/EMA_Res18.py:118-181): every block ends in relu(EMA(y) + shortcut) (:79-86), EMA with 32
     channel groups (:10-38).  All three arithmetic modes; precision="f16" (fp16 storage) runs the tails of
-    libreid_hip_siblings_f16.so, which must lie beside libreid_hip.so."""
+    libreid_hip_siblings_f16.so, which must lie beside libreid_hip.so.  ``hw_ema=True``: inputs [N,3,H,W] of another size (sides 32 ..
+    512) run too, in exact fp32 or - ``hw_precision="f16x3"`` - fp32-class, as seres18_ibn's do, with the EMA tail of
+    libreid_hip_anysize_ema.so."""
     arch = "emares18_ibn"
 
 

@@ -8,6 +8,7 @@
 #include "select_x3.h"
 #include "anysize_front.h"
 #include "anysize_ca.h"
+#include "anysize_ema.h"
 #include <cmath>
 #include <dlfcn.h>
 #include <mutex>
@@ -219,6 +220,17 @@ extern "C" int reid_ctx_set_hw_siblings(reid_ctx* ctx, int on) {
         return REID_ERR_ARG;
     }
     ctx->hw_siblings = on;
+    return REID_OK;
+}
+
+extern "C" int reid_ctx_set_hw_ema(reid_ctx* ctx, int on) {
+    ARG_CHECK(ctx);
+    CTX_GUARD(ctx);
+    if (on != 0 && on != 1) {
+        reid_set_error("reid_ctx_set_hw_ema: the value must be 0 (other input sizes refuse emares18_ibn) or 1 (they run it)");
+        return REID_ERR_ARG;
+    }
+    ctx->hw_ema = on;
     return REID_OK;
 }
 
@@ -1574,6 +1586,26 @@ static int anysize_ca_api(const AnysizeCaApi** out) {
     return REID_OK;
 }
 
+// ... and the EMA block tail of emares18_ibn (reid_ctx_set_hw_ema 1): anysize_ema.h
+struct AnysizeEmaApi {
+    decltype(&anysize_ema_workspace_bytes) ws_bytes = nullptr;
+    decltype(&anysize_ema_tail) tail = nullptr;
+};
+static int anysize_ema_api(const AnysizeEmaApi** out) {
+    static std::mutex m;
+    static AnysizeEmaApi api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.tail) {
+        void* f[2];
+        REID_TRY(open_beside_self("libreid_hip_anysize_ema.so", "EMARes18-IBN at an input size other than 256 x 128 needs",
+                                  {"anysize_ema_workspace_bytes", "anysize_ema_tail"}, f));
+        api.ws_bytes = (decltype(api.ws_bytes))f[0];
+        api.tail = (decltype(api.tail))f[1];
+    }
+    *out = &api;
+    return REID_OK;
+}
+
 bool se_any_routes(const reid_ctx* ctx, int h, int w) { return h != IMG_H || w != IMG_W || ctx->anysize_force != 0; }
 
 int se_any_pass(const reid_ctx* ctx, int h, int w) {
@@ -1593,12 +1625,12 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
         return REID_ERR_STATE;
     }
     static const char* const kArch[3] = {"seres18_ibn", "cares18_ibn", "emares18_ibn"};
-    if (ctx->hw_siblings && wt.arch == 2) {
+    if (ctx->hw_siblings && wt.arch == 2 && !ctx->hw_ema) {
         reid_set_error("%s: input size %d x %d: loaded architecture %s has no any-size tail; with reid_ctx_set_hw_siblings 1 only cares18_ibn "
                        "runs at sizes other than 256 x 128 beside seres18_ibn", who, h, w, kArch[wt.arch]);
         return REID_ERR_ARG;
     }
-    const bool arch_ok = wt.arch == 0 || (wt.arch == 1 && ctx->hw_siblings);
+    const bool arch_ok = wt.arch == 0 || (wt.arch == 1 && ctx->hw_siblings) || (wt.arch == 2 && ctx->hw_ema);
     if (!arch_ok || (ctx->hw_precision < 0 && ctx->precision != 0)) {   // reid_ctx_set_hw_precision 0 / 2 names the arithmetic itself
         reid_set_error("%s: input size %d x %d runs seres18_ibn in precision mode 0 (exact fp32) only; loaded architecture %s, precision "
                        "mode %d (256 x 128 runs every architecture and mode)", who, h, w, kArch[wt.arch], ctx->precision);
@@ -1613,6 +1645,10 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
     if (wt.arch == 1 && ctx->any_ca != 0) {
         const AnysizeCaApi* ca;
         REID_TRY(anysize_ca_api(&ca));
+    }
+    if (wt.arch == 2 && ctx->any_ema != 0) {
+        const AnysizeEmaApi* ema;
+        REID_TRY(anysize_ema_api(&ema));
     }
     return REID_OK;
 }
@@ -1684,6 +1720,31 @@ int launch_any_ca_tail(reid_ctx* ctx, const float* y, const float* sc, int n, in
     }
     if (maps_out) *maps_out = (const float*)ws;
     if (gates_out) *gates_out = (const float*)ws + (size_t)n * 2 * ((size_t)H * W + (size_t)C * W + (size_t)H * C);
+    return REID_OK;
+}
+
+int launch_any_ema_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int H, int W, int C, const float* prm, float* out,
+                        const float** sig_out, const float** small_out) {
+    const AnysizeEmaApi* api;
+    REID_TRY(anysize_ema_api(&api));
+    const size_t bytes = api->ws_bytes(n, H, W, C);
+    if (!bytes) {
+        reid_set_error("libreid_hip_anysize_ema.so: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", H, W,
+                       C, n);
+        return REID_ERR_ARG;
+    }
+    void* ws;
+    REID_TRY(ctx_ws(ctx, "any.ema", bytes, &ws));
+    prof_begin(ctx, REID_K_ELEMENTWISE, (double)n * H * W * C * C / 32.0 * 36.0, (double)n * H * W * C * 20.0);
+    const hipError_t e = api->tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
+    prof_end(ctx);
+    if (e != hipSuccess) {
+        reid_set_error("libreid_hip_anysize_ema.so anysize_ema_tail -> %s", hipGetErrorString(e));
+        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+    }
+    const float* sig = (const float*)((const double*)ws + (size_t)n * anysize_ema_slabs(H, W, C) * 3 * C);
+    if (sig_out) *sig_out = sig;
+    if (small_out) *small_out = sig + (size_t)n * (H + W) * C;
     return REID_OK;
 }
 
@@ -1858,6 +1919,9 @@ static int seres18_trunk_any(reid_ctx* ctx, const AnyBufs& b, int n, float* d_em
         if (wt.arch == 1) {   // CARes18_IBN: TripletAttention + shortcut + ReLU (CARes18.py:150-157); any_ca 0: the 256 x 128 forward's kernels
             if (ctx->any_ca) REID_TRY(launch_any_ca_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out));
             else REID_TRY(launch_ta_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out));
+        } else if (wt.arch == 2) {   // EMARes18_IBN: EMA + shortcut + ReLU (EMA_Res18.py:79-86); any_ema 0: the 256 x 128 forward's kernel
+            if (ctx->any_ema) REID_TRY(launch_any_ema_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ema, out));
+            else REID_TRY(launch_ema_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ema, out));
         } else {
             REID_TRY(launch_any_se_tail(ctx, y, shortcut, n, hw, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr));
         }

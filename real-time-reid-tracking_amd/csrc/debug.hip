@@ -2,6 +2,7 @@
 // against libreid_hip.so: nothing here is part of the product library or of the drop-in C ABI.
 #include "reid_internal.h"
 #include "pil_launch.h"
+#include "anysize_ema.h"
 #include <string.h>
 #include <stdlib.h>
 #include <vector>
@@ -26,7 +27,7 @@ const Switch kSwitches[] = {
     {"split_x3", &reid_ctx::split_x3}, {"x3_ablate", &reid_ctx::x3_ablate}, {"x3_unroll", &reid_ctx::x3_unroll}, {"x3_narrow", &reid_ctx::x3_narrow}, {"conv_x3s", &reid_ctx::conv_x3s}, {"x3s_sk_cap", &reid_ctx::x3s_sk_cap}, {"x3_l4_narrow_nmt", &reid_ctx::x3_l4_narrow_nmt}, {"split_x3_small", &reid_ctx::split_x3_small}, {"split_x3_min_blocks", &reid_ctx::split_x3_min_blocks}, {"f32_dist_bk16", &reid_ctx::f32_dist_bk16}, {"lin_x3", &reid_ctx::lin_x3},
     {"host_pipeline", &reid_ctx::host_pipeline}, {"x3_sk_cap", &reid_ctx::x3_sk_cap}, {"chain", &reid_ctx::chain}, {"split_gemm_min_tiles", &reid_ctx::split_gemm_min_tiles},
     {"rerank_hbm_acc", &reid_ctx::rerank_hbm_acc}, {"gem_tail_min", &reid_ctx::gem_tail_min}, {"anysize_force", &reid_ctx::anysize_force},
-    {"any_front", &reid_ctx::any_front}, {"any_ca", &reid_ctx::any_ca},
+    {"any_front", &reid_ctx::any_front}, {"any_ca", &reid_ctx::any_ca}, {"any_ema", &reid_ctx::any_ema},
 };
 }  // namespace
 
@@ -765,6 +766,31 @@ extern "C" int reid_debug_any_ca_tail(reid_ctx* ctx, int n, int h, int w, int c,
     REID_TRY(dbg_download(ctx, out, dout, ny + c));
     REID_TRY(dbg_download(ctx, maps, dmaps, (size_t)n * 2 * per));
     REID_TRY(dbg_download(ctx, gates, dgates, (size_t)n * per + c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// The EMA tail of libreid_hip_anysize_ema.so (anysize_ema.h; tests/test_gpu_anysize_ema.py) through launch_any_ema_tail, the function the
+// any-size forward calls.  The workspace is set to 0xff bytes with one guard pixel behind it before the launch, as out is.
+extern "C" int reid_debug_any_ema_tail(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const float* y, const float* shortcut,
+                                       float* out, float* sig, float* small) {
+    ARG_CHECK(ctx && n >= 1 && h >= 1 && w >= 1 && c >= 64 && c <= 512 && c % 32 == 0 && prm && y && shortcut && out);
+    CTX_ENTER(ctx);
+    const int cg = c / 32;
+    const size_t ny = (size_t)n * h * w * c, nsig = (size_t)n * (h + w) * c, nsmall = (size_t)n * 4 * c;
+    const size_t npart = (size_t)n * anysize_ema_slabs(h, w, c) * 3 * c;   // doubles
+    float *dprm, *dy, *dsc, *dout, *dws;
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", prm, (size_t)cg * cg * 10 + 4 * cg, &dprm));
+    REID_TRY(dbg_upload(ctx, "dbgt.x", y, ny, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgt.sc", shortcut, ny, &dsc));
+    REID_TRY(dbg_output(ctx, "dbgt.out", ny + c, &dout));
+    REID_TRY(dbg_output(ctx, "any.ema", 2 * npart + nsig + nsmall + c, &dws));   // the workspace launch_any_ema_tail takes: grown first, so it is this one
+    const float *dsig, *dsmall;
+    REID_TRY(launch_any_ema_tail(ctx, dy, dsc, n, h, w, c, dprm, dout, &dsig, &dsmall));
+    ARG_CHECK(dsig == dws + 2 * npart && dsmall == dsig + nsig);
+    REID_TRY(dbg_download(ctx, out, dout, ny + c));
+    REID_TRY(dbg_download(ctx, sig, dsig, nsig));
+    REID_TRY(dbg_download(ctx, small, dsmall, nsmall + c));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return ctx_fault_status(ctx);
 }

@@ -514,6 +514,9 @@ struct reid_ctx {
     int hw_precision = -1;   // reid_ctx_set_hw_precision: the arithmetic of the any-size forward: -1 = it needs the context in mode 0 (default),
                              // 0 = exact fp32 whatever the mode, 2 = fp32-class whatever the mode (libreid_hip_anysize_x3.so)
     int hw_siblings = 0;     // reid_ctx_set_hw_siblings: 1 = a loaded cares18_ibn runs at other sizes too (libreid_hip_anysize_ca.so)
+    int hw_ema = 0;          // reid_ctx_set_hw_ema: 1 = a loaded emares18_ibn runs at other sizes too (libreid_hip_anysize_ema.so)
+    int any_ema = 1;         // libreid_hip_debug.so switch: the EMA tail of the any-size trunk: 1 = libreid_hip_anysize_ema.so, 0 =
+                             // launch_ema_tail (attention_f32.hip; refuses a map whose slab does not fit LDS), for A/B timing in one process
     int any_ca = 1;          // libreid_hip_debug.so switch: the TripletAttention tail of the any-size trunk: 1 = libreid_hip_anysize_ca.so,
                              // 0 = launch_ta_tail (attention_f32.hip), for A/B timing of whole passes in one process
     int any_conv_form = 0;   // the tile form the last fp32-class any-size convolution launched (anysize_x3.h), written on the host only
@@ -784,7 +787,8 @@ int open_beside_self(const char* file, const char* what, std::initializer_list<c
 // ---- ResNet18-IBN-SE at input sizes other than 256 x 128 (api.hip; kernels: anysize.h).  The reid_*_hw entries hand 256 x 128 to the
 // existing entries unless the debug switch anysize_force is set (se_any_routes).  se_any_ready: everything such a call would refuse, with
 // nothing queued - a side outside 32 .. 512 (REID_ERR_ARG), weights not loaded (REID_ERR_STATE), an architecture other than seres18_ibn
-// (or, with reid_ctx_set_hw_siblings 1, cares18_ibn, which then needs libreid_hip_anysize_ca.so: REID_ERR_STATE) or
+// (or, with reid_ctx_set_hw_siblings 1, cares18_ibn, which then needs libreid_hip_anysize_ca.so: REID_ERR_STATE; with reid_ctx_set_hw_ema 1,
+// emares18_ibn, which then needs libreid_hip_anysize_ema.so: REID_ERR_STATE) or
 // a precision mode other than 0 while reid_ctx_set_hw_precision is -1 (REID_ERR_ARG naming both), libreid_hip_anysize.so and, at
 // hw_precision 2, libreid_hip_anysize_x3.so (REID_ERR_STATE).  se_any_pass: images per pass, the
 // context's chunk scaled by 256 * 128 / (h * w) and clamped to 1 .. 4096.  se_any_run_nchw: one pass from fp32 NCHW [m][3][h][w] on the
@@ -817,6 +821,12 @@ int launch_any_gem(reid_ctx* ctx, const float* x, int n, int hw, int c, const fl
 // lie in it, in the layout of anysize_ca.h, valid until the next call.  The forward and reid_debug_any_ca_tail call this one function.
 int launch_any_ca_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int H, int W, int C, const float* prm, float* out,
                        const float** maps_out = nullptr, const float** gates_out = nullptr);
+// the EMA tail of the any-size trunk (emares18_ibn with reid_ctx_set_hw_ema 1; anysize_ema.h) on device operands [n][H][W][C], prm =
+// Se18Block::ema; the workspace ("any.ema", anysize_ema_workspace_bytes) comes from ctx_ws.  sig_out / small_out (may be NULL): where the
+// call's sigmoid vectors [n][H + W][C] and mu | rstd | s1 | s2 [n][4][C] lie in it, valid until the next call.  The forward and
+// reid_debug_any_ema_tail call this one function.
+int launch_any_ema_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int H, int W, int C, const float* prm, float* out,
+                        const float** sig_out = nullptr, const float** small_out = nullptr);
 // one trunk convolution of the any-size forward (NHWC fp32 in / out, folded BN, identity residual, ReLU from column relu_from on) in the
 // arithmetic `arith`: 0 = launch_gemm_f32 (exact fp32), 2 = any_conv_x3_kernel of libreid_hip_anysize_x3.so (fp32-class; R = 3 pad 1 or
 // R = 1 pad 0) on the cached split form of wgt.  The forward and reid_debug_any_conv call this one function.

@@ -250,6 +250,45 @@ class Engine:
                     self.set_hw_siblings(prev)
         return scope()
 
+    @staticmethod
+    def hw_ema_value(v):
+        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_ema); ValueError otherwise, before any device call."""
+        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+            return int(v)
+        raise ValueError("hw_ema must be False / 0 (other input sizes refuse emares18_ibn) or True / 1 (they run it), got %r" % (v,))
+
+    def set_hw_ema(self, on):
+        """EMARes18-IBN at input sizes other than 256 x 128 (reid_ctx_set_hw_ema): False (default) = the reid_*_hw entries refuse a
+        loaded emares18_ibn at another size, True = it runs there with the EMA tail of libreid_hip_anysize_ema.so, under the size,
+        precision and pass-size rules of seres18_ibn and whatever set_hw_siblings is.  cares18_ibn still needs set_hw_siblings; 256 x 128 is
+        not affected."""
+        v = Engine.hw_ema_value(on)
+        check(self.lib.reid_ctx_set_hw_ema(self.h, v))
+        self._hw_ema = bool(v)
+
+    @property
+    def hw_ema(self):
+        """What set_hw_ema set last (the library's default is False)."""
+        return getattr(self, "_hw_ema", False)
+
+    def hw_ema_scope(self, on):
+        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            if on is None:
+                yield self
+                return
+            prev = self.hw_ema
+            self.set_hw_ema(on)
+            try:
+                yield self
+            finally:
+                if self.hw_ema != prev:
+                    self.set_hw_ema(prev)
+        return scope()
+
     def set_side_index(self, index):
         """Camera (ResNet18-IBN-SE: SERes18_IBN.py:269-270) or view (Swin: swin_transformer.py:301-302) index of every image of
         the following embed call; ``None`` / empty clears."""
@@ -819,7 +858,8 @@ class Engine:
 
     def embed_f32_nchw(self, x, logits=False):
         """float32 [n,3,H,W] -> float32 [n,512] (and logits).  (256, 128) runs the loaded architecture in the context's precision;
-        any other H, W in 32 .. 512 the any-size forward (reid_embed_f32_nchw_hw: seres18_ibn weights - cares18_ibn with set_hw_siblings(True) -
+        any other H, W in 32 .. 512 the any-size forward (reid_embed_f32_nchw_hw: seres18_ibn weights - cares18_ibn with set_hw_siblings(True),
+        emares18_ibn with set_hw_ema(True) -
         in exact fp32, or the arithmetic set_hw_precision names)."""
         x = _f32(x)
         if x.ndim != 4 or x.shape[1] != 3:
@@ -1461,6 +1501,21 @@ class Engine:
         gates = np.empty(n * per + c, np.float32)
         check(_ffi.debug_lib().reid_debug_any_ca_tail(self.h, n, h, w, c, _ptr(prm), _ptr(y), _ptr(shortcut), _ptr(out), _ptr(maps), _ptr(gates)))
         return out, maps, gates
+
+    def debug_any_ema_tail(self, y, shortcut, prm):
+        """The EMA tail of libreid_hip_anysize_ema.so through the any-size forward's launcher (reid_debug_any_ema_tail): y, shortcut
+        [n, h, w, c], prm the cg * cg * 10 + 4 * cg floats of Se18Block::ema (cg = c / 32).  Returns (out [n h w c + c], sig [n, h + w, c],
+        small [n 4 c + c]) in the layouts of include/reid_hip_debug.h, guards included."""
+        y, shortcut, prm = _f32(y), _f32(shortcut), _f32(prm)
+        n, h, w, c = y.shape
+        cg = c // 32
+        if shortcut.shape != y.shape or c % 32 or prm.size != cg * cg * 10 + 4 * cg:
+            raise ValueError("debug_any_ema_tail: operand shapes")
+        out = np.empty(y.size + c, np.float32)
+        sig = np.empty((n, h + w, c), np.float32)
+        small = np.empty(n * 4 * c + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_ema_tail(self.h, n, h, w, c, _ptr(prm), _ptr(y), _ptr(shortcut), _ptr(out), _ptr(sig), _ptr(small)))
+        return out, sig, small
 
     def debug_any_norm(self, x, half, in_gamma, in_beta, bn_scale=None, bn_shift=None):
         x = _f32(x)

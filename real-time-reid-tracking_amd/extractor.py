@@ -34,7 +34,7 @@ def pack_checkpoint(state_dict):
 
 
 class Extractor(object):
-    def __init__(self, model_path, use_cuda=True, device=0, precision=None, size=None, hw_siblings=False):
+    def __init__(self, model_path, use_cuda=True, device=0, precision=None, size=None, hw_siblings=False, hw_ema=False):
         """``Extractor(model_path, use_cuda=True)`` as feature_extractor.py:15-29.  ``precision`` (keyword, not in the reference):
         "f16x3" (default; $REID_PRECISION overrides the default) / "f32" / "f16" - see precision.py; a checkpoint the fp32-class
         arithmetic cannot represent runs in exact fp32, with one log line.  ``size`` (keyword, (W, H) like ``self.size``): the size
@@ -44,13 +44,15 @@ class Extractor(object):
         reid_ctx_set_hw_precision 2 around every call) must be given - $REID_PRECISION is a default, not a name, and nothing is demoted
         behind the caller's back - and the object's log line names size and arithmetic.  ``hw_siblings=True`` (keyword) lets a cares18_ibn
         checkpoint take such a size too, under the same rule: Engine.set_hw_siblings(True) around every call (the TripletAttention tail
-        of libreid_hip_anysize_ca.so); emares18_ibn has no other size."""
+        of libreid_hip_anysize_ca.so); ``hw_ema=True`` (keyword) does the same for an emares18_ibn checkpoint: Engine.set_hw_ema(True)
+        around every call (the EMA tail of libreid_hip_anysize_ema.so); without it emares18_ibn has no other size."""
         if not use_cuda:
             raise RuntimeError("Extractor: the MI355X engine has no CPU path (use_cuda=False is not supported)")
         self.device = "cuda"
         self._mode = _precision.resolve(precision)
         from .engine import Engine as _Engine
         self._hw_siblings = bool(_Engine.hw_siblings_value(hw_siblings))      # a bad value raises here, before any device call
+        self._hw_ema = bool(_Engine.hw_ema_value(hw_ema))
         if isinstance(model_path, dict):
             state_dict = model_path            # already-loaded state_dict (tests, benchmarks)
         else:
@@ -61,6 +63,8 @@ class Extractor(object):
             state_dict = torch.load(model_path, map_location="cpu")   # {"state_dict": ...} / "module." prefixes: weights.pack_seres18
         from .engine import Engine, get_engine
         self._arch, blob, manifest, self.info = pack_checkpoint(state_dict)
+        if self._hw_ema and self.info.get("arch") != "emares18_ibn":
+            raise ValueError("Extractor: hw_ema belongs to emares18_ibn checkpoints, got %s" % (self.info.get("arch"),))
         if self._arch == "swin":
             self.size = tuple(int(v) for v in (size or (224, 224)))           # (W, H)
             Engine._swin_crop_args(self.size[::-1], None)
@@ -70,6 +74,8 @@ class Extractor(object):
                 from .engine import check_hw
                 h, w = check_hw(tuple(size)[::-1])
                 sized = ("seres18_ibn", "cares18_ibn") if self._hw_siblings else ("seres18_ibn",)
+                if self._hw_ema:
+                    sized = sized + ("emares18_ibn",)
                 if self.info.get("arch") not in sized or precision is None or self._mode == _precision.F16:
                     raise ValueError("Extractor: at a size other than (W, H) = (128, 256) the ResNet18-IBN family runs seres18_ibn "
                                      "checkpoints in exact fp32 (precision=\"f32\") or fp32-class (precision=\"f16x3\"), asked for by "
@@ -117,7 +123,9 @@ class Extractor(object):
             # a fall back (precision.run) the object is exact fp32 and the setting stays as the engine has it
             def scoped(eng):
                 sib = True if self._hw_siblings and self.info.get("arch") == "cares18_ibn" else None
-                with eng.hw_precision_scope(2 if self._mode == _precision.F32_CLASS else None), eng.hw_siblings_scope(sib):
+                ema = True if self._hw_ema and self.info.get("arch") == "emares18_ibn" else None
+                with eng.hw_precision_scope(2 if self._mode == _precision.F32_CLASS else None), eng.hw_siblings_scope(sib), \
+                        eng.hw_ema_scope(ema):
                     return fn(eng)
             return _precision.run(self, self.net, "Extractor", scoped)
         return _precision.run(self, self.net, "Extractor", fn)

@@ -18,7 +18,7 @@ def show_avai_models():
     print(list(__model_factory.keys()))
 
 
-def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True, precision=None, version=None, hw_precision=None, hw_siblings=None):
+def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True, precision=None, version=None, hw_precision=None, hw_siblings=None, hw_ema=None):
     """Same signature, same ``KeyError`` text as models/__init__.py:93-121; constructors are called with
     (num_classes, loss, pretrained, use_gpu).  ``precision`` (keyword, this engine's addition): the arithmetic the model runs
     in - None = $REID_PRECISION, else "f16x3", the mode bench.py reports (precision.py).  ``version`` (keyword): "v1" / "v2" of
@@ -26,7 +26,7 @@ def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True
     ``hw_precision`` (keyword): 'seres18_ibn' at inputs other than 256 x 128 - None = exact fp32 for such a call, "f16x3" = the fp32-class
     arithmetic (backbone.SERes18IBN); the Swin takes none.
     ``hw_siblings`` (keyword): True lets 'cares18_ibn' take inputs other than 256 x 128 too (backbone.CARes18IBN, Engine.set_hw_siblings);
-    every other name takes none."""
+    every other name takes none.  ``hw_ema`` (keyword): the same for 'emares18_ibn' (backbone.EMARes18IBN, Engine.set_hw_ema)."""
     avai_models = list(__model_factory.keys())
     if name not in avai_models:
         raise KeyError('Unknown model: {}. Must be one of {}'.format(name, avai_models))
@@ -43,4 +43,8 @@ def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True
         if name != 'cares18_ibn':
             raise ValueError("model '{}' has no hw_siblings argument".format(name))
         extra['hw_siblings'] = hw_siblings
+    if hw_ema is not None:
+        if name != 'emares18_ibn':
+            raise ValueError("model '{}' has no hw_ema argument".format(name))
+        extra['hw_ema'] = hw_ema
     return __model_factory[name](num_classes=num_classes, loss=loss, pretrained=pretrained, use_gpu=use_gpu, precision=precision, **extra)

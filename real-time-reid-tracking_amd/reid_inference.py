@@ -47,17 +47,31 @@ def dbscan_pseudo_labels(dists, eps=0.5, min_samples=5):
 
 
 ARCHS = ("seres18", "swin", "seres18_hw", "cares18_hw")
-HW_ARCHS = ("seres18_hw", "cares18_hw")
+EMA_ARCH = "emares18_hw"
+HW_ARCHS = ("seres18_hw", "cares18_hw", EMA_ARCH)
 # "seres18_hw": the ResNet path at the images' own size - the script's --dataset veri runs the ResNet family at
 # Resize((224, int(ratio * 224))), ratio the mean width / height of the dataset (data_transforms.py:121, image_reid_inference.py:169-180).
 # Float images carry the size, uint8 images are resized to ``size`` (required); seres18_ibn weights, exact fp32 (reid_*_hw).  The default
 # "seres18" stays fixed at 256 x 128, every architecture of the family and every precision mode.
 # "cares18_hw": the same with cares18_ibn weights (the script's --backbone cares18): Engine.set_hw_siblings(True) for the call, restored after it.
+# "emares18_hw": the same with emares18_ibn weights, accepted only together with the keyword hw_ema=True (_ema_gate): Engine.set_hw_ema(True)
+# for the call, restored after it.  Without the keyword the name is refused like any unknown one, so it is not in ARCHS.
+
+
+def _ema_gate(arch, hw_ema):
+    """arch="emares18_hw" and the keyword hw_ema=True come together or not at all (ValueError, before any device call)."""
+    from .engine import Engine
+    on = bool(Engine.hw_ema_value(hw_ema))
+    if arch == EMA_ARCH and not on:
+        raise ValueError("arch must be one of %s, got %r (the keyword hw_ema=True enables arch=%r)" % (ARCHS, arch, EMA_ARCH))
+    if on and arch != EMA_ARCH:
+        raise ValueError("hw_ema belongs to arch=%r; arch=%r takes none" % (EMA_ARCH, arch))
+    return on
 
 
 def _descriptor_width(engine, arch):
     """Width of a descriptor row of ``arch`` on this engine; ValueError for an unknown arch or weights without a classifier."""
-    if arch not in ARCHS:
+    if arch not in ARCHS and arch != EMA_ARCH:              # "emares18_hw" has passed _ema_gate where this is reached
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
     if arch == "swin":
         nc, dim = getattr(engine, "swin_num_class", 0), getattr(engine, "swin_dim", 0)
@@ -149,7 +163,7 @@ def _check_strong(arch, flip, strong_offsets, n, pad):
 
 
 def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None, hw_precision=None,
-                        strong_offsets=None, pad=10):
+                        strong_offsets=None, pad=10, hw_ema=False):
     """Descriptors of ``images`` (float32 [n,3,256,128], host) into the device rows ``d_out`` (pointer to [n, 512 + num_class]
     fp32): upload in batches of ``bs`` images, one ``reid_descriptor_f32_nchw_dev`` per batch.  Unlike the reference function
     (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253).
@@ -167,16 +181,19 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     exact fp32 (``reid_descriptor_f32_nchw_hw_dev`` / ``reid_descriptor_images_u8_hw``), or - ``hw_precision`` "f32" / "f16x3"
     (``Engine.set_hw_precision``) - in the arithmetic named, whatever the context's mode: set for this call and restored after it; None
     leaves the engine's setting alone.  ``arch="cares18_hw"``: the same entries on cares18_ibn weights (the script's --backbone cares18 with
-    --dataset veri), ``Engine.set_hw_siblings(True)`` for this call and restored after it.
+    --dataset veri), ``Engine.set_hw_siblings(True)`` for this call and restored after it.  ``arch="emares18_hw"`` with ``hw_ema=True`` (the
+    name alone is refused like an unknown one): the same entries on emares18_ibn weights, ``Engine.set_hw_ema(True)`` for this call and
+    restored after it.
 
     ``strong_offsets``: int [n, 2] of (top, left) per image with ``pad`` (data_transforms.strong_inference_offsets): the second view is the
     script's strong_inference one - the mirror shifted by (top - pad, left - pad) over a black border, black being (0 - mean) / std of the
     ImageNet values (``reid_descriptor_f32_nchw_shift_dev`` / ``reid_descriptor_images_u8_shift``).  ``arch="swin"`` takes none: the
     script gives the Swin the plain mirror.  None is today's call and bits."""
+    _ema_gate(arch, hw_ema)
     if hw_precision is not None:
         from .engine import Engine
         if arch not in HW_ARCHS:
-            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw'; arch=%r takes none" % (arch,))
+            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw' / 'emares18_hw'; arch=%r takes none" % (arch,))
         Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
     if strong_offsets is not None:
         strong_offsets, pad = _check_strong(arch, flip, strong_offsets, len(images), pad)
@@ -199,8 +216,9 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
         if view_index.shape[0] != n or (n and (view_index.min() < 0 or view_index.max() >= 2 ** 31)):
             raise ValueError("view_index must hold one non-negative index per image (%d), got %d" % (n, view_index.shape[0]))
         view_index = view_index.astype(np.int32)
-    if hw_precision is not None or arch == "cares18_hw":   # every argument is checked: the settings go on for the device work and off after it
-        with engine.hw_precision_scope(hw_precision), engine.hw_siblings_scope(True if arch == "cares18_hw" else None):
+    if hw_precision is not None or arch in ("cares18_hw", EMA_ARCH):   # every argument is checked: the settings go on for the device work and off after it
+        with engine.hw_precision_scope(hw_precision), engine.hw_siblings_scope(True if arch == "cares18_hw" else None), \
+                engine.hw_ema_scope(True if arch == EMA_ARCH else None):
             return inference_efficient(engine, images, d_out, flip, bs, "seres18_hw", view_index, size if u8 else None,
                                        strong_offsets=strong_offsets, pad=pad)
     if u8:
@@ -233,7 +251,7 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
 def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, query_images, query_labels, query_cams,
                   query_seqs, num_gallery_cams=None, eps=0.5, la=0.05, k1=20, k2=6, flip=True, cluster_fn=None, taps=None,
                   verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None, hw_precision=None,
-                  strong_inference=False, strong_offsets=None, attribute_dist=None, pad=10):
+                  strong_inference=False, strong_offsets=None, attribute_dist=None, pad=10, hw_ema=False):
     """(CMC float32 [ng], mAP float) of the script's chain for one gallery / query pair; weights must be loaded on the engine
     (``Engine.load_seres18`` / ``build_model``).  ``taps`` (a dict) receives host copies of the intermediates the
     reference-generated fixture holds: "desc", "debiased", "jaccard", "pseudo_labels", "smoothed".
@@ -245,7 +263,8 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     runs seres18_ibn weights in exact fp32 at the float images' own size or at ``size``: VeRi is ``size=(224, int(ratio * 224))``;
     ``hw_precision`` "f32" / "f16x3" names that forward's arithmetic for this call - ``Engine.set_hw_precision``, restored afterwards - and
     None leaves the engine's setting alone; ``arch="cares18_hw"`` is the same for cares18_ibn weights, with ``Engine.set_hw_siblings(True)``
-    for the call).
+    for the call, and ``arch="emares18_hw"`` together with ``hw_ema=True`` for emares18_ibn weights, with ``Engine.set_hw_ema(True)`` for the
+    call; without that keyword the name is refused).
     ``strong_inference`` / ``strong_offsets``: the script's second view for the ResNet family (--backbone seres18 / cares18,
     image_reid_inference.py:179-181) - the mirror shifted by up to +-``pad`` pixels on each axis over a black border.
     ``strong_offsets`` is int [ng + nq, 2] of (top, left) per image, gallery first; ``strong_inference=True`` without offsets draws them
@@ -255,6 +274,7 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     euclidean_dist(rows, rows) is added to the device Jaccard matrix (``reid_distmat_add_l2_dev``) before its download.
     ``taps["jaccard"]`` stays the matrix before the add; ``taps["dists"]`` is the one handed to DBSCAN / ``cluster_fn``.  With these
     keywords left out the call and its bits are what they were."""
+    _ema_gate(arch, hw_ema)
     if strong_inference or strong_offsets is not None:
         n_all = len(gallery_labels) + len(query_labels)
         if strong_offsets is None:
@@ -276,9 +296,9 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     if hw_precision is not None:
         from .engine import Engine
         if arch not in HW_ARCHS:
-            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw'; arch=%r takes none" % (arch,))
+            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw' / 'emares18_hw'; arch=%r takes none" % (arch,))
         Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
-    if arch not in ARCHS:
+    if arch not in ARCHS and arch != EMA_ARCH:
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
     if use_side and arch != "swin":
         raise ValueError("use_side is the Swin's side information (--sie); arch=%r takes none here" % (arch,))
@@ -299,9 +319,9 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     try:
         strong = {} if strong_offsets is None else {"pad": pad}
         inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None, size=size if u8[0] else None,
-                            hw_precision=hw_precision, **(strong and dict(strong, strong_offsets=strong_offsets[:ng])))
+                            hw_precision=hw_precision, hw_ema=hw_ema, **(strong and dict(strong, strong_offsets=strong_offsets[:ng])))
         inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None,
-                            size=size if u8[1] else None, hw_precision=hw_precision,
+                            size=size if u8[1] else None, hw_precision=hw_precision, hw_ema=hw_ema,
                             **(strong and dict(strong, strong_offsets=strong_offsets[ng:])))
         if taps is not None:
             taps["desc"] = merged.numpy()

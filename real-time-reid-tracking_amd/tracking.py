@@ -31,11 +31,19 @@ def _two_streams(stream, on):
     stream.eng.frame_match_stream(stream.match_stream)
 
 
-HW_ARCHS = ("seres18_hw", "cares18_hw")   # the any-size forward: seres18_ibn, and cares18_ibn with Engine.set_hw_siblings(True)
+EMA_ARCH = "emares18_hw"                  # accepted only together with the keyword hw_ema=True
+# the any-size forward: seres18_ibn, cares18_ibn with Engine.set_hw_siblings(True), emares18_ibn with Engine.set_hw_ema(True)
+HW_ARCHS = ("seres18_hw", "cares18_hw", EMA_ARCH)
 
 
-def _check_arch(arch, size, mean_std, hw_precision=None):
-    """`arch`, `size`, `mean_std`, `hw_precision` of the stream classes, checked before any device call (ValueError)."""
+def _check_arch(arch, size, mean_std, hw_precision=None, hw_ema=False):
+    """`arch`, `size`, `mean_std`, `hw_precision`, `hw_ema` of the stream classes, checked before any device call (ValueError)."""
+    on = bool(Engine.hw_ema_value(hw_ema))
+    if arch == EMA_ARCH and not on:
+        raise ValueError("arch must be 'seres18', 'seres18_hw', 'cares18_hw' or 'swin', got %r (the keyword hw_ema=True enables arch=%r)"
+                         % (arch, EMA_ARCH))
+    if on and arch != EMA_ARCH:
+        raise ValueError("hw_ema belongs to arch=%r, got arch %r" % (EMA_ARCH, arch))
     if arch == "swin":
         Engine._swin_crop_args(size, mean_std)
     elif arch in HW_ARCHS:
@@ -50,14 +58,15 @@ def _check_arch(arch, size, mean_std, hw_precision=None):
     Engine.hw_precision_value(hw_precision)
 
 
-def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_precision=None):
+def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_precision=None, hw_ema=False):
     """`arch` of the stream classes: "seres18" (default) loads a ResNet18-SE family checkpoint, frames are 512 wide; "swin" - the
     reference's swin_transformer tracker model, modification_tracking/models/__init__.py:80 - loads with `Engine.load_swin`, every crop
     is resized to ``size`` = (H, W) multiples of 224 and normalised with ``mean_std`` (None: ImageNet), and the embeddings, the bank
     and the cost stage are 96 wide; "seres18_hw" - a ResNet18-IBN-SE (seres18_ibn) tracker at another crop size, Extractor(size=) of
     feature_extractor.py:31-46 - resizes every crop to ``size`` = (H, W), sides 32 .. 512, normalises with ``mean_std`` (None: 0.5 / 0.5)
     and runs the any-size forward in the arithmetic ``hw_precision`` names (`Engine.set_hw_precision`); frames are 512 wide; "cares18_hw" - the same with a CARes18-IBN (cares18_ibn) checkpoint: the context's
-    `Engine.set_hw_siblings` is switched on, and stays on for the stream's life."""
+    `Engine.set_hw_siblings` is switched on, and stays on for the stream's life; "emares18_hw" with ``hw_ema=True`` - the same with an
+    EMARes18-IBN (emares18_ibn) checkpoint and `Engine.set_hw_ema`."""
     if arch == "swin":
         stream.eng.load_swin(weights_blob, manifest)
     else:
@@ -66,6 +75,8 @@ def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_prec
         stream.eng.set_hw_precision(hw_precision)
     if arch == "cares18_hw":
         stream.eng.set_hw_siblings(True)
+    if arch == EMA_ARCH:
+        stream.eng.set_hw_ema(True)
     stream.arch, stream.size, stream.mean_std = arch, size, mean_std
 
 
@@ -85,11 +96,11 @@ def _one_stream_again(stream):
 
 class CameraStream:
     def __init__(self, weights_blob, manifest, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0, own_context=True,
-                 max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_precision=None):
-        _check_arch(arch, size, mean_std, hw_precision)
+                 max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision, hw_ema)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -142,11 +153,11 @@ class MultiCameraStream:
     with one list entry per camera everywhere; one host thread, one wait per frame time."""
 
     def __init__(self, weights_blob, manifest, cameras, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_precision=None):
-        _check_arch(arch, size, mean_std, hw_precision)
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision, hw_ema)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -231,11 +242,11 @@ class LookaheadCameraStream:
     """
 
     def __init__(self, weights_blob, manifest, frames_per_pass=2, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_precision=None):
-        _check_arch(arch, size, mean_std, hw_precision)
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision, hw_ema)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
