@@ -387,6 +387,23 @@ int reid_ctx_set_hw_siblings(reid_ctx* ctx, int on);
  *                reid_ctx_set_hw_siblings 1.
  *   Any other value is REID_ERR_ARG and changes nothing.  (256, 128) is never affected. */
 int reid_ctx_set_hw_ema(reid_ctx* ctx, int on);
+/* reid_ctx_set_hw_f16(ctx, on): ResNet18-IBN-SE at input sizes other than 256 x 128 in the fp16-storage arithmetic (f16 activations and
+ * weights, fp32 accumulation on the matrix pipe, fp32 or wider statistics, gates, GeM and neck), a setting of its own because
+ * reid_ctx_set_hw_precision refuses 1 and callers of that refusal keep it.
+ *   0 (default)  as above: reid_ctx_set_hw_precision and the context's mode decide, every status and message unchanged.
+ *   1            a loaded seres18_ibn runs at another size (32 .. 512 per side, odd sizes allowed) through the kernels of
+ *                libreid_hip_anysize_f16.so (csrc/anysize_f16.h: stem on the matrix pipe, max-pool, implicit-GEMM trunk convolutions, IBN
+ *                finish, SE tail, GeM + neck), whatever the context's mode and whatever reid_ctx_set_hw_precision is set to; the stored
+ *                hw_precision keeps its value (its checkpoint rules too) and governs again once this setting is back at 0.  The library
+ *                must lie beside this one (REID_ERR_STATE naming it otherwise, before anything is queued and before a frame slot is
+ *                touched).  A loaded cares18_ibn / emares18_ibn at another size is REID_ERR_ARG whatever reid_ctx_set_hw_siblings /
+ *                reid_ctx_set_hw_ema are: the message names the architecture and says that the fp16-storage any-size forward serves
+ *                seres18_ibn only.  The size range, the pass sizes and the side indices are unchanged; every reid_*_hw entry, the _shift
+ *                entries, reid_embed_frame_u8_hw and reid_frame_submit_hw follow (the frame entries through resize + normalise and the
+ *                f16 stem: libreid_hip_anysize_front.so is not needed).  The camera bias and the classifier stay fp32;
+ *                reid_debug_stage returns the f16 taps widened to fp32, each at its own map size.
+ *   Any other value is REID_ERR_ARG and changes nothing.  (256, 128) is never affected. */
+int reid_ctx_set_hw_f16(reid_ctx* ctx, int on);
 int reid_embed_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits);
 int reid_embed_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits);
 int reid_embed_ragged_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,

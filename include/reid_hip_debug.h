@@ -149,6 +149,28 @@ int reid_debug_any_ema_tail(reid_ctx* ctx, int n, int h, int w, int c, const flo
 int reid_debug_any_conv(reid_ctx* ctx, int hw_precision, const float* x, int n, int h, int w, int cin, const float* wgt, int cout, int r,
                         int stride, int pad, const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out,
                         int* form_out);
+/* The kernels of libreid_hip_anysize_f16.so (csrc/anysize_f16.h; tests/test_gpu_anysize_f16.py) through the launchers the any-size forward
+ * calls under reid_ctx_set_hw_f16 1, on host operands.  f16 operands and results are handed over as their bits (uint16_t), NHWC.  Every
+ * output has ONE guard row behind its last pixel, preset to 0xff bytes with the rest (NaN in f16 and in fp32).
+ *   any_conv_f16     x [n][h][w][cin], wgt [cout][r][r][cin], out [n ho wo cout + cout]; geometry, epilogue and NULL rules of
+ *                    reid_debug_any_conv, residual f16; form_out (may be NULL) = the tile form launched, 1 = 128 x 64, 2 = 128 x 128.
+ *   any_stem_f16     x fp32 [n][h][w][3], w16 [64][192] (k = r 24 + s 3 + c, zero padded): conv 7x7 s2 p3 + BN -> stem_out
+ *                    [n H1 W1 64 + 64], then MaxPool(3, 2, 1) of that map -> pool_out [n H2 W2 64 + 64].
+ *   any_norm_f16     x -> out [n hw c + c] in place: channels < half InstanceNorm2d(affine) over the image's hw pixels + ReLU, the rest untouched.
+ *   any_se_tail_f16  out = relu(sigmoid(w2t^T relu(w1 mean_hw(y))) y + shortcut); alias != 0: the launch writes into y's buffer; gate
+ *                    [n c + c] fp32 may be NULL.
+ *   any_gem_f16      GeM (exponent p, clamp 1e-6) + BNNeck on f16 x, gem_out (may be NULL) / emb fp32 [n c + c]. */
+int reid_debug_any_conv_f16(reid_ctx* ctx, const uint16_t* x, int n, int h, int w, int cin, const uint16_t* wgt, int cout, int r, int stride,
+                            int pad, const float* scale, const float* shift, const uint16_t* residual, int relu, int relu_from, uint16_t* out,
+                            int* form_out);
+int reid_debug_any_stem_f16(reid_ctx* ctx, const float* x, int n, int h, int w, const uint16_t* w16, const float* scale, const float* shift,
+                            uint16_t* stem_out, uint16_t* pool_out);
+int reid_debug_any_norm_f16(reid_ctx* ctx, int n, int hw, int c, int half, const uint16_t* x, const float* in_gamma, const float* in_beta,
+                            uint16_t* out);
+int reid_debug_any_se_tail_f16(reid_ctx* ctx, int n, int hw, int c, int mid, const float* w1, const float* w2t, const uint16_t* y,
+                               const uint16_t* shortcut, int alias, uint16_t* out, float* gate);
+int reid_debug_any_gem_f16(reid_ctx* ctx, int n, int hw, int c, float p, const uint16_t* x, const float* scale, const float* shift,
+                           float* gem_out, float* emb);
 /* The front end of the any-size forward from uint8 windows (tests/test_gpu_anysize_front.py) through the launcher reid_frame_submit_hw and
  * reid_embed_frame_u8_hw call, on host operands: src [src_bytes] holds n windows, window i hw[2i] x hw[2i + 1] pixels at byte offsets[i],
  * its rows one after the other (pitch 0) or `pitch` pixels apart (windows of one frame); every window must lie inside src.  They are

@@ -80,14 +80,16 @@ class SERes18IBN:
     ``model(x)`` -> embedding [N,512] = BNNeck output; ``model(x, return_logits=True)`` ->
     (embedding, logits[N,num_classes]) like the reference's eval-mode tuple (SERes18_IBN.py:274-275).
     ``x``: float32/float16 [N,3,256,128] NCHW, normalised - numpy array or torch tensor; the result has the
-    type (and, for torch, the device) of the input.
+    type (and, for torch, the device) of the input.  Inputs [N,3,H,W] of another size (sides 32 .. 512) run the any-size forward in exact
+    fp32, with ``hw_precision="f16x3"`` in the fp32-class arithmetic, or with ``hw_f16=True`` in fp16 storage with fp32 accumulation
+    (libreid_hip_anysize_f16.so); the engine's settings come back after the call.
     """
 
     embed_dim = 512
     arch = "seres18_ibn"
 
     def __init__(self, num_classes=751, loss="triplet", pretrained=False, use_gpu=True, seed=0, num_cams=6, cam_factor=-1.0,
-                 precision=None, hw_precision=None, hw_siblings=False, hw_ema=False, **_):
+                 precision=None, hw_precision=None, hw_siblings=False, hw_ema=False, hw_f16=False, **_):
         if loss not in ("triplet", "softmax"):
             raise NotImplementedError                      # seres18_ibn(), SERes18_IBN.py:279-285
         self._mode = _precision.resolve(precision)         # "f16x3" unless the argument or $REID_PRECISION says otherwise (precision.py)
@@ -101,6 +103,13 @@ class SERes18IBN:
         self._hw_ema = bool(Engine.hw_ema_value(hw_ema))
         if self._hw_ema and self.arch != "emares18_ibn":
             raise ValueError("%s has no hw_ema argument (emares18_ibn only)" % self.arch)
+        # seres18_ibn only: True = inputs of another size run in fp16 storage with fp32 accumulation (Engine.set_hw_f16 around such a call)
+        self._hw_f16 = bool(Engine.hw_f16_value(hw_f16))
+        if self._hw_f16 and self.arch != "seres18_ibn":
+            raise ValueError("%s has no hw_f16 argument (seres18_ibn only)" % self.arch)
+        if self._hw_f16 and hw_precision is not None:
+            raise ValueError("hw_f16 and hw_precision both name the arithmetic of inputs of another size: give one of them, got hw_f16=%r "
+                             "and hw_precision=%r" % (hw_f16, hw_precision))
         self._hw_call = _HwClassCall(self) if hw == 2 else None
         self.num_classes = num_classes
         self.num_cams, self.cam_factor = num_cams, float(cam_factor)   # SERes18_IBN.py:193,198: cam_bias [num_cams,512] and its factor
@@ -233,6 +242,14 @@ class SERes18IBN:
                     with e.hw_ema_scope(True):
                         return fn(e)
                 return inner_ema(scoped)
+        if any_size and getattr(self, "_hw_f16", False):          # seres18_ibn in fp16 storage: likewise with the engine's hw_f16
+            inner_f16 = run
+
+            def run(fn):
+                def scoped(e):
+                    with e.hw_f16_scope(True):
+                        return fn(e)
+                return inner_f16(scoped)
         if is_torch and x.is_cuda:
             if x.device.index != self._device:
                 self.to(x.device.index)

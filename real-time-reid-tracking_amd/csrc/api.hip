@@ -4,6 +4,7 @@
 #include "siblings_f16.h"
 #include "anysize.h"
 #include "anysize_x3.h"
+#include "anysize_f16.h"
 #include "distmat_x3.h"
 #include "select_x3.h"
 #include "anysize_front.h"
@@ -231,6 +232,18 @@ extern "C" int reid_ctx_set_hw_ema(reid_ctx* ctx, int on) {
         return REID_ERR_ARG;
     }
     ctx->hw_ema = on;
+    return REID_OK;
+}
+
+extern "C" int reid_ctx_set_hw_f16(reid_ctx* ctx, int on) {
+    ARG_CHECK(ctx);
+    CTX_GUARD(ctx);
+    if (on != 0 && on != 1) {
+        reid_set_error("reid_ctx_set_hw_f16: the value must be 0 (other input sizes run in the arithmetic reid_ctx_set_hw_precision names) or "
+                       "1 (they run seres18_ibn in fp16 storage with fp32 accumulation)");
+        return REID_ERR_ARG;
+    }
+    ctx->hw_f16 = on;
     return REID_OK;
 }
 
@@ -1551,6 +1564,35 @@ static int anysize_x3_api(const AnysizeX3Api** out) {
     return REID_OK;
 }
 
+// ... and that forward in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16 1): anysize_f16.h
+struct AnysizeF16Api {
+    decltype(&anysize_f16_conv) conv = nullptr;
+    decltype(&anysize_f16_stem) stem = nullptr;
+    decltype(&anysize_f16_maxpool) maxpool = nullptr;
+    decltype(&anysize_f16_norm) norm = nullptr;
+    decltype(&anysize_f16_se_tail) se_tail = nullptr;
+    decltype(&anysize_f16_gem) gem = nullptr;
+};
+static int anysize_f16_api(const AnysizeF16Api** out) {
+    static std::mutex m;
+    static AnysizeF16Api api;
+    std::lock_guard<std::mutex> lk(m);
+    if (!api.conv) {
+        void* f[6];
+        REID_TRY(open_beside_self("libreid_hip_anysize_f16.so", "ResNet18-IBN-SE at another input size in the fp16-storage arithmetic needs",
+                                  {"anysize_f16_conv", "anysize_f16_stem", "anysize_f16_maxpool", "anysize_f16_norm", "anysize_f16_se_tail",
+                                   "anysize_f16_gem"}, f));
+        api.stem = (decltype(api.stem))f[1];
+        api.maxpool = (decltype(api.maxpool))f[2];
+        api.norm = (decltype(api.norm))f[3];
+        api.se_tail = (decltype(api.se_tail))f[4];
+        api.gem = (decltype(api.gem))f[5];
+        api.conv = (decltype(api.conv))f[0];
+    }
+    *out = &api;
+    return REID_OK;
+}
+
 // ... and its front end from uint8 windows in one kernel (reid_frame_submit_hw, reid_embed_frame_u8_hw): anysize_front.h
 static int anysize_front_api(decltype(&anysize_front)* out) {
     static std::mutex m;
@@ -1625,6 +1667,17 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
         return REID_ERR_STATE;
     }
     static const char* const kArch[3] = {"seres18_ibn", "cares18_ibn", "emares18_ibn"};
+    if (ctx->hw_f16) {   // the setting names the arithmetic itself: neither the mode nor hw_precision is looked at
+        if (wt.arch != 0) {
+            reid_set_error("%s: input size %d x %d with reid_ctx_set_hw_f16 1: loaded architecture %s; the fp16-storage any-size forward serves "
+                           "seres18_ibn only", who, h, w, kArch[wt.arch]);
+            return REID_ERR_ARG;
+        }
+        const AnysizeApi* api;
+        REID_TRY(anysize_api(&api));
+        const AnysizeF16Api* f16api;
+        return anysize_f16_api(&f16api);
+    }
     if (ctx->hw_siblings && wt.arch == 2 && !ctx->hw_ema) {
         reid_set_error("%s: input size %d x %d: loaded architecture %s has no any-size tail; with reid_ctx_set_hw_siblings 1 only cares18_ibn "
                        "runs at sizes other than 256 x 128 beside seres18_ibn", who, h, w, kArch[wt.arch]);
@@ -1665,6 +1718,7 @@ int se_any_front_ready(reid_ctx* ctx, int h, int w, const float** mean_std6, con
         }
         return REID_OK;
     }
+    if (ctx->hw_f16) return REID_OK;   // its passes go through resize + normalise and the f16 stem: the fused fp32 front end is not needed
     decltype(&anysize_front) front;
     return anysize_front_api(&front);
 }
@@ -1960,8 +2014,183 @@ static int seres18_trunk_any(reid_ctx* ctx, const AnyBufs& b, int n, float* d_em
     return REID_OK;
 }
 
+// ---- the same forward in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16 1): every kernel from libreid_hip_anysize_f16.so
+static int any_f16_launched(hipError_t e, const char* what) {
+    if (e != hipSuccess) {
+        reid_set_error("libreid_hip_anysize_f16.so %s -> %s", what, hipGetErrorString(e));
+        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
+    }
+    return REID_OK;
+}
+
+int launch_any_conv_f16(reid_ctx* ctx, const _Float16* x, int n, int H, int W, int Cin, const _Float16* w16, int Cout, int R, int stride, int pad,
+                        const float* scale, const float* shift, const _Float16* residual, int relu, int relu_from, _Float16* out) {
+    const AnysizeF16Api* api;
+    REID_TRY(anysize_f16_api(&api));
+    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - R) / stride + 1;
+    const double m = (double)n * Ho * Wo, ktrue = (double)R * R * Cin;
+    prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * Cout * ktrue, ((double)n * H * W * Cin + m * Cout * (residual ? 2.0 : 1.0) + (double)Cout * ktrue) * 2.0);
+    const hipError_t e = api->conv(ctx->stream, x, n, H, W, Cin, w16, Cout, R, stride, pad, scale, shift, residual, relu, relu_from, out,
+                                   &ctx->any_f16_form);
+    prof_end(ctx);
+    return any_f16_launched(e, "anysize_f16_conv");
+}
+
+int launch_any_stem_f16(reid_ctx* ctx, const float* x, int n, int h, int w, const _Float16* w16, const float* scale, const float* shift,
+                        _Float16* out) {
+    const AnysizeF16Api* api;
+    REID_TRY(anysize_f16_api(&api));
+    const double m = (double)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1);
+    prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * 64 * 147.0, (double)n * h * w * 12.0 + m * 128.0 + 64 * 192 * 2.0);
+    const hipError_t e = api->stem(ctx->stream, x, n, h, w, w16, scale, shift, out);
+    prof_end(ctx);
+    return any_f16_launched(e, "anysize_f16_stem");
+}
+
+int launch_any_maxpool_f16(reid_ctx* ctx, const _Float16* x, int n, int h, int w, int c, _Float16* out) {
+    const AnysizeF16Api* api;
+    REID_TRY(anysize_f16_api(&api));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, ((double)n * h * w * c + (double)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) * c) * 2.0);
+    const hipError_t e = api->maxpool(ctx->stream, x, n, h, w, c, out);
+    prof_end(ctx);
+    return any_f16_launched(e, "anysize_f16_maxpool");
+}
+
+int launch_any_norm_f16(reid_ctx* ctx, _Float16* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta) {
+    const AnysizeF16Api* api;
+    REID_TRY(anysize_f16_api(&api));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * half * 6.0);
+    const hipError_t e = api->norm(ctx->stream, x, n, hw, c, half, in_gamma, in_beta);
+    prof_end(ctx);
+    return any_f16_launched(e, "anysize_f16_norm");
+}
+
+int launch_any_se_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int hw, int c, int mid, const float* w1,
+                           const float* w2t, _Float16* out, float* gate_out) {
+    const AnysizeF16Api* api;
+    REID_TRY(anysize_f16_api(&api));
+    float* pooled;
+    REID_TRY(ctx_ws(ctx, "any.pooled", (size_t)n * c * 4, (void**)&pooled));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 8.0);
+    const hipError_t e = api->se_tail(ctx->stream, y, sc, n, hw, c, mid, w1, w2t, pooled, out, gate_out);
+    prof_end(ctx);
+    return any_f16_launched(e, "anysize_f16_se_tail");
+}
+
+int launch_any_gem_f16(reid_ctx* ctx, const _Float16* x, int n, int hw, int c, const float* p, const float* scale, const float* shift,
+                       float* gem_out, float* emb) {
+    const AnysizeF16Api* api;
+    REID_TRY(anysize_f16_api(&api));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 2.0);
+    const hipError_t e = api->gem(ctx->stream, x, n, hw, c, p, scale, shift, gem_out, emb);
+    prof_end(ctx);
+    return any_f16_launched(e, "anysize_f16_gem");
+}
+
+// x: fp32 NHWC [n][h][w][3] on the device.  The buffers are those of any_bufs in f16 (the same names as the fp16-storage forward at
+// 256 x 128, which sizes them in bytes too); the weights are the f16 image of the blob reid_seres18_load makes whatever the mode
+// (Se18Weights::h; the stem's [64][192] packed rows are in it), the fp32 folded-BN vectors, SE weights and neck are shared with the
+// fp32 forward.  The trunk is seres18_trunk_any's, launch for launch.
+static int seres18_forward_any_f16(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
+    typedef _Float16 f16;
+    Se18Weights& wt = ctx->se18;
+    ARG_CHECK(wt.arch == 0);
+    const bool keep = ctx->debug_keep != 0;
+    const int H1 = (h - 1) / 2 + 1, W1 = (w - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
+    ARG_CHECK((long long)n * H1 * W1 < (1ll << 31) - 256);
+    size_t elems[11];
+    elems[0] = (size_t)H1 * W1 * 64;
+    elems[1] = (size_t)H2 * W2 * 64;
+    size_t per = elems[1];
+    {
+        int H = H2, W = W2;
+        for (int i = 0; i < 8; ++i) {
+            const Se18Block& k = wt.blk[i];
+            H = (H + 2 - 3) / k.stride + 1;
+            W = (W + 2 - 3) / k.stride + 1;
+            elems[2 + i] = (size_t)H * W * k.c;
+            if (elems[2 + i] > per) per = elems[2 + i];
+        }
+    }
+    elems[10] = 512;
+    f16 *stem, *pool, *tbase;
+    float* gem;
+    REID_TRY(ctx_ws(ctx, "se18h.stem", (size_t)n * elems[0] * 2, (void**)&stem));
+    REID_TRY(ctx_ws(ctx, "se18h.pool", (size_t)n * per * 2, (void**)&pool));
+    REID_TRY(ctx_ws(ctx, "se18h.t", (size_t)n * per * 2 * (keep ? 4 * 8 : 4), (void**)&tbase));
+    REID_TRY(ctx_ws(ctx, "se18.gem", (size_t)n * 512 * 4, (void**)&gem));
+    REID_TRY(launch_any_stem_f16(ctx, x, n, h, w, wt.h(wt.stem_w), wt.stem_scale, wt.stem_shift, stem));
+    REID_TRY(launch_any_maxpool_f16(ctx, stem, n, H1, W1, 64, pool));
+    float* stage[11];
+    stage[0] = (float*)stem;
+    stage[1] = (float*)pool;
+    const f16* cur = pool;
+    int H = H2, W = W2;
+    for (int i = 0; i < 8; ++i) {
+        const Se18Block& k = wt.blk[i];
+        f16* free_[3];
+        int nf = 0;
+        for (int j = 0; j < 4 && nf < 3; ++j) {
+            f16* t = tbase + ((size_t)(keep ? i * 4 : 0) + j) * n * per;
+            if (t != cur) free_[nf++] = t;
+        }
+        f16 *c1 = free_[0], *y = free_[1], *sc = free_[2];
+        const int Ho = (H + 2 - 3) / k.stride + 1, Wo = (W + 2 - 3) / k.stride + 1, hw = Ho * Wo;
+        if (k.ibn) {   // BatchNorm half + ReLU in conv1's epilogue, InstanceNorm half (statistics of the whole image) by one pass in place
+            REID_TRY(launch_any_conv_f16(ctx, cur, n, H, W, k.cin, wt.h(k.conv1_w), k.c, 3, k.stride, 1, wt.ep + (size_t)i * 1024,
+                                         wt.ep + (size_t)i * 1024 + 512, nullptr, 1, k.c / 2, c1));
+            REID_TRY(launch_any_norm_f16(ctx, c1, n, hw, k.c, k.c / 2, k.in_gamma, k.in_beta));
+        } else {
+            REID_TRY(launch_any_conv_f16(ctx, cur, n, H, W, k.cin, wt.h(k.conv1_w), k.c, 3, k.stride, 1, k.bn1_scale, k.bn1_shift, nullptr, 1, 0,
+                                         c1));
+        }
+        REID_TRY(launch_any_conv_f16(ctx, c1, n, Ho, Wo, k.c, wt.h(k.conv2_w), k.c, 3, 1, 1, k.bn2_scale, k.bn2_shift, k.ds ? nullptr : cur,
+                                     k.ds ? 0 : 1, 0, y));
+        const f16* shortcut = cur;
+        if (k.ds) {
+            REID_TRY(launch_any_conv_f16(ctx, cur, n, H, W, k.cin, wt.h(k.ds_w), k.c, 1, k.stride, 0, k.ds_scale, k.ds_shift, nullptr, 0, 0, sc));
+            shortcut = sc;
+        }
+        f16* out = c1;   // conv1's output is dead after conv2
+        REID_TRY(launch_any_se_tail_f16(ctx, y, shortcut, n, hw, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr));
+        stage[2 + i] = (float*)out;
+        cur = out;
+        H = Ho;
+        W = Wo;
+    }
+    REID_TRY(launch_any_gem_f16(ctx, cur, n, H * W, 512, wt.gem_p, wt.neck_scale, wt.neck_shift, gem, d_emb));
+    {
+        const int32_t* d_cam;
+        REID_TRY(ctx_take_side(ctx, n, wt.num_cams, "reid_embed (camera bias)", &d_cam));
+        if (d_cam) REID_TRY(launch_add_indexed_rows(ctx, d_emb, n, 1, 512, wt.cam_bias, d_cam, wt.cam_factor));
+    }
+    stage[10] = gem;
+    if (d_logits) {
+        if (!wt.cls_w) {
+            reid_set_error("logits requested but the weight blob has no classifier (cls.w)");
+            return REID_ERR_STATE;
+        }
+        GemmParams p;
+        memset(&p, 0, sizeof(p));
+        p.A = d_emb; p.lda = 512;
+        p.B = wt.cls_w; p.ldb = 512;
+        p.M = n; p.N = wt.num_class; p.K = 512;
+        p.C = d_logits; p.ldc = wt.num_class;
+        REID_TRY(launch_gemm_f32(ctx, A_DENSE, E_BIAS, p, REID_K_CONV_GEMM, 2.0 * n * wt.num_class * 512,
+                                 ((double)n * 512 + (double)wt.num_class * 512 + (double)n * wt.num_class) * 4.0));
+    }
+    ctx->last_n = n;
+    ctx->last_f16 = true;
+    for (int s = 0; s < 11; ++s) {
+        ctx->stage_ptr[s] = stage[s];
+        ctx->stage_elems[s] = elems[s];
+    }
+    return REID_OK;
+}
+
 // x: fp32 NHWC [n][h][w][3] on the device
 static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
+    if (ctx->hw_f16) return seres18_forward_any_f16(ctx, x, n, h, w, d_emb, d_logits);
     const Se18Weights& wt = ctx->se18;
     AnyBufs b;
     REID_TRY(any_bufs(ctx, n, h, w, true, b));
@@ -1990,7 +2219,8 @@ constexpr long long ANY_FRONT_MAX_STEM_PIXELS = 65536;
 static int se_any_run_windows(reid_ctx* ctx, const RaggedSrc& src, int i, int m, int h, int w, const float* mean_std6, float* d_emb, float* d_log,
                               bool front = false) {
     const bool small = (long long)m * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) <= ANY_FRONT_MAX_STEM_PIXELS;
-    if (front && (ctx->any_front == 1 || (ctx->any_front == 2 && small)) && !ctx->debug_keep) {
+    // reid_ctx_set_hw_f16 1: the fused kernel's pooled map is fp32, so such a pass takes resize + normalise and the f16 stem
+    if (front && !ctx->hw_f16 && (ctx->any_front == 1 || (ctx->any_front == 2 && small)) && !ctx->debug_keep) {
         const Se18Weights& wt = ctx->se18;
         AnyBufs b;
         REID_TRY(any_bufs(ctx, m, h, w, false, b));

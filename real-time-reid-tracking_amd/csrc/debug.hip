@@ -830,6 +830,117 @@ extern "C" int reid_debug_any_conv(reid_ctx* ctx, int hw_precision, const float*
     return ctx_fault_status(ctx);
 }
 
+// ---- the kernels of libreid_hip_anysize_f16.so (anysize_f16.h; tests/test_gpu_anysize_f16.py) through the launchers the any-size forward
+// calls under reid_ctx_set_hw_f16 1.  f16 operands and results travel as their bits (uint16_t).  Every output buffer carries one guard row
+// behind the last pixel, set to 0xff bytes (NaN in f16 and fp32) with the rest and returned with it.
+extern "C" int reid_debug_any_conv_f16(reid_ctx* ctx, const uint16_t* x, int n, int h, int w, int cin, const uint16_t* wgt, int cout, int r,
+                                       int stride, int pad, const float* scale, const float* shift, const uint16_t* residual, int relu,
+                                       int relu_from, uint16_t* out, int* form_out) {
+    ARG_CHECK(ctx && x && wgt && out && n >= 1 && h >= 1 && w >= 1 && cin >= 32 && cin % 32 == 0 && cout >= 64 && cout % 64 == 0 &&
+              ((r == 3 && pad == 1) || (r == 1 && pad == 0)) && (stride == 1 || stride == 2) && (scale == nullptr) == (shift == nullptr) &&
+              relu_from >= 0 && relu_from <= cout);
+    CTX_ENTER(ctx);
+    const int ho = (h + 2 * pad - r) / stride + 1, wo = (w + 2 * pad - r) / stride + 1;
+    const size_t nx = (size_t)n * h * w * cin, nw = (size_t)cout * r * r * cin, ny = (size_t)n * ho * wo * cout;
+    uint16_t *dx, *dw, *dr, *dout;
+    float *ds, *dh;
+    REID_TRY(dbg_upload(ctx, "dbgh.x", x, nx, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgh.w", wgt, nw, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgc.scale", scale, (size_t)cout, &ds));
+    REID_TRY(dbg_upload(ctx, "dbgc.shift", shift, (size_t)cout, &dh));
+    REID_TRY(dbg_upload(ctx, "dbgh.res", residual, ny, &dr));
+    REID_TRY(dbg_output(ctx, "dbgh.out", ny + cout, &dout));
+    ctx->any_f16_form = 0;
+    REID_TRY(launch_any_conv_f16(ctx, (const _Float16*)dx, n, h, w, cin, (const _Float16*)dw, cout, r, stride, pad, ds, dh, (const _Float16*)dr,
+                                 relu, relu_from, (_Float16*)dout));
+    if (form_out) *form_out = ctx->any_f16_form;
+    REID_TRY(dbg_download(ctx, out, dout, ny + cout));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_any_stem_f16(reid_ctx* ctx, const float* x, int n, int h, int w, const uint16_t* w16, const float* scale,
+                                       const float* shift, uint16_t* stem_out, uint16_t* pool_out) {
+    ARG_CHECK(ctx && x && w16 && scale && shift && stem_out && pool_out && n >= 1 && h >= 1 && w >= 1);
+    CTX_ENTER(ctx);
+    const int H1 = (h - 1) / 2 + 1, W1 = (w - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
+    const size_t ns = (size_t)n * H1 * W1 * 64, np_ = (size_t)n * H2 * W2 * 64;
+    float *dx, *ds, *dh;
+    uint16_t *dw, *dstem, *dpool;
+    REID_TRY(dbg_upload(ctx, "dbgc.x", x, (size_t)n * h * w * 3, &dx));
+    REID_TRY(dbg_upload(ctx, "dbgh.w", w16, (size_t)64 * 192, &dw));
+    REID_TRY(dbg_upload(ctx, "dbgc.scale", scale, (size_t)64, &ds));
+    REID_TRY(dbg_upload(ctx, "dbgc.shift", shift, (size_t)64, &dh));
+    REID_TRY(dbg_output(ctx, "dbgh.out", ns + 64, &dstem));
+    REID_TRY(dbg_output(ctx, "dbgh.res", np_ + 64, &dpool));
+    REID_TRY(launch_any_stem_f16(ctx, dx, n, h, w, (const _Float16*)dw, ds, dh, (_Float16*)dstem));
+    REID_TRY(launch_any_maxpool_f16(ctx, (const _Float16*)dstem, n, H1, W1, 64, (_Float16*)dpool));
+    REID_TRY(dbg_download(ctx, stem_out, dstem, ns + 64));
+    REID_TRY(dbg_download(ctx, pool_out, dpool, np_ + 64));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_any_norm_f16(reid_ctx* ctx, int n, int hw, int c, int half, const uint16_t* x, const float* in_gamma,
+                                       const float* in_beta, uint16_t* out) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && half >= 32 && half <= c && x && in_gamma && in_beta && out);
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)n * hw * c;
+    uint16_t* dx;
+    float *dg, *db;
+    REID_TRY(dbg_output(ctx, "dbgh.x", nx + c, &dx));
+    HIP_TRY(hipMemcpyAsync(dx, x, nx * 2, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(dbg_upload(ctx, "dbgt.gamma", in_gamma, (size_t)half, &dg));
+    REID_TRY(dbg_upload(ctx, "dbgt.beta", in_beta, (size_t)half, &db));
+    REID_TRY(launch_any_norm_f16(ctx, (_Float16*)dx, n, hw, c, half, dg, db));
+    REID_TRY(dbg_download(ctx, out, dx, nx + c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+// alias != 0: out is y's buffer (the launch the forward could make in place); the guard row then lies behind y
+extern "C" int reid_debug_any_se_tail_f16(reid_ctx* ctx, int n, int hw, int c, int mid, const float* w1, const float* w2t, const uint16_t* y,
+                                          const uint16_t* shortcut, int alias, uint16_t* out, float* gate) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && mid >= 1 && w1 && w2t && y && shortcut && out);
+    CTX_ENTER(ctx);
+    const size_t ny = (size_t)n * hw * c;
+    float *dw1, *dw2, *dgate = nullptr;
+    uint16_t *dy, *dsc, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", w1, (size_t)mid * c, &dw1));
+    REID_TRY(dbg_upload(ctx, "dbgt.w2", w2t, (size_t)mid * c, &dw2));
+    REID_TRY(dbg_output(ctx, "dbgh.x", ny + c, &dy));
+    HIP_TRY(hipMemcpyAsync(dy, y, ny * 2, hipMemcpyHostToDevice, ctx->stream));
+    REID_TRY(dbg_upload(ctx, "dbgh.res", shortcut, ny, &dsc));
+    REID_TRY(dbg_output(ctx, "dbgh.out", ny + c, &dout));
+    if (alias) dout = dy;
+    if (gate) REID_TRY(dbg_output(ctx, "dbgt.a", (size_t)n * c + c, &dgate));
+    REID_TRY(launch_any_se_tail_f16(ctx, (const _Float16*)dy, (const _Float16*)dsc, n, hw, c, mid, dw1, dw2, (_Float16*)dout, dgate));
+    REID_TRY(dbg_download(ctx, out, dout, ny + c));
+    if (dgate) REID_TRY(dbg_download(ctx, gate, dgate, (size_t)n * c + c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_any_gem_f16(reid_ctx* ctx, int n, int hw, int c, float p, const uint16_t* x, const float* scale, const float* shift,
+                                      float* gem_out, float* emb) {
+    ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && x && scale && shift && emb);
+    CTX_ENTER(ctx);
+    const size_t nx = (size_t)n * hw * c, ne = (size_t)n * c + c;
+    uint16_t* dx;
+    float *dp, *dsc, *dsh, *dg = nullptr, *de;
+    REID_TRY(dbg_upload(ctx, "dbgt.p", &p, 1, &dp));
+    REID_TRY(dbg_upload(ctx, "dbgt.bns", scale, (size_t)c, &dsc));
+    REID_TRY(dbg_upload(ctx, "dbgt.bnh", shift, (size_t)c, &dsh));
+    REID_TRY(dbg_upload(ctx, "dbgh.x", x, nx, &dx));
+    if (gem_out) REID_TRY(dbg_output(ctx, "dbgt.a", ne, &dg));
+    REID_TRY(dbg_output(ctx, "dbgt.b", ne, &de));
+    REID_TRY(launch_any_gem_f16(ctx, (const _Float16*)dx, n, hw, c, dp, dsc, dsh, dg, de));
+    if (dg) REID_TRY(dbg_download(ctx, gem_out, dg, ne));
+    REID_TRY(dbg_download(ctx, emb, de, ne));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 // The front end of the any-size forward from uint8 windows through launch_any_front, the function reid_frame_submit_hw and
 // reid_embed_frame_u8_hw call: fused 1 = any_front_kernel (libreid_hip_anysize_front.so), 0 = resize, stem GEMM and max-pool in three launches.
 extern "C" int reid_debug_any_front(reid_ctx* ctx, int fused, const uint8_t* src, int64_t src_bytes, const int64_t* offsets, const int32_t* hw,

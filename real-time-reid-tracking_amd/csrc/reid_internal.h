@@ -515,6 +515,9 @@ struct reid_ctx {
                              // 0 = exact fp32 whatever the mode, 2 = fp32-class whatever the mode (libreid_hip_anysize_x3.so)
     int hw_siblings = 0;     // reid_ctx_set_hw_siblings: 1 = a loaded cares18_ibn runs at other sizes too (libreid_hip_anysize_ca.so)
     int hw_ema = 0;          // reid_ctx_set_hw_ema: 1 = a loaded emares18_ibn runs at other sizes too (libreid_hip_anysize_ema.so)
+    int hw_f16 = 0;          // reid_ctx_set_hw_f16: 1 = a loaded seres18_ibn runs at other sizes in fp16 storage with fp32 accumulation, whatever
+                             // the mode and hw_precision (libreid_hip_anysize_f16.so)
+    int any_f16_form = 0;    // the tile form the last fp16-storage any-size convolution launched (anysize_f16.h), written on the host only
     int any_ema = 1;         // libreid_hip_debug.so switch: the EMA tail of the any-size trunk: 1 = libreid_hip_anysize_ema.so, 0 =
                              // launch_ema_tail (attention_f32.hip; refuses a map whose slab does not fit LDS), for A/B timing in one process
     int any_ca = 1;          // libreid_hip_debug.so switch: the TripletAttention tail of the any-size trunk: 1 = libreid_hip_anysize_ca.so,
@@ -790,7 +793,9 @@ int open_beside_self(const char* file, const char* what, std::initializer_list<c
 // (or, with reid_ctx_set_hw_siblings 1, cares18_ibn, which then needs libreid_hip_anysize_ca.so: REID_ERR_STATE; with reid_ctx_set_hw_ema 1,
 // emares18_ibn, which then needs libreid_hip_anysize_ema.so: REID_ERR_STATE) or
 // a precision mode other than 0 while reid_ctx_set_hw_precision is -1 (REID_ERR_ARG naming both), libreid_hip_anysize.so and, at
-// hw_precision 2, libreid_hip_anysize_x3.so (REID_ERR_STATE).  se_any_pass: images per pass, the
+// hw_precision 2, libreid_hip_anysize_x3.so (REID_ERR_STATE).  With reid_ctx_set_hw_f16 1 instead: an architecture other than seres18_ibn
+// (REID_ERR_ARG naming it, whatever hw_siblings / hw_ema), libreid_hip_anysize.so and libreid_hip_anysize_f16.so (REID_ERR_STATE); the mode
+// and hw_precision are not looked at.  se_any_pass: images per pass, the
 // context's chunk scaled by 256 * 128 / (h * w) and clamped to 1 .. 4096.  se_any_run_nchw: one pass from fp32 NCHW [m][3][h][w] on the
 // device (mirror: the horizontally flipped view); se_any_run_windows: from uploaded uint8 windows through the cv2-style resize.
 struct RaggedSrc;
@@ -800,7 +805,8 @@ int se_any_pass(const reid_ctx* ctx, int h, int w);
 int se_any_run_nchw(reid_ctx* ctx, const float* d_x, int m, int h, int w, int mirror, float* d_emb, float* d_log);
 // The frame pipeline at out_h x out_w (reid_frame_submit_hw, reid_embed_frame_u8_hw).  se_any_front_ready: what such a call refuses, with
 // nothing queued - *mean_std6 NULL becomes 0.5 / 0.5, a value that is not finite or a std <= 0 is REID_ERR_ARG, then se_any_ready's rules,
-// at 256 x 128 another mean_std6 than 0.5 / 0.5 (REID_ERR_ARG), elsewhere libreid_hip_anysize_front.so (REID_ERR_STATE).
+// at 256 x 128 another mean_std6 than 0.5 / 0.5 (REID_ERR_ARG), elsewhere libreid_hip_anysize_front.so (REID_ERR_STATE; not with
+// reid_ctx_set_hw_f16 1, whose passes never take the fused front end).
 // any_ragged_enqueue: ragged_enqueue_begin + passes of se_any_pass crops, as embed_ragged_enqueue.  launch_any_front: the front end of
 // one pass on uploaded windows -> pool [n][H2][W2][64]; fused 1 = any_front_kernel, 0 = resize, stem GEMM (into stem [n][H1][W1][64]) and
 // max-pool, the same bits - the forward and reid_debug_any_front call this one function.
@@ -832,6 +838,19 @@ int launch_any_ema_tail(reid_ctx* ctx, const float* y, const float* sc, int n, i
 // R = 1 pad 0) on the cached split form of wgt.  The forward and reid_debug_any_conv call this one function.
 int launch_any_conv(reid_ctx* ctx, int arith, const float* x, int n, int H, int W, int Cin, const float* wgt, int Cout, int R, int stride, int pad,
                     const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out);
+// The any-size forward in fp16 storage (reid_ctx_set_hw_f16 1; kernels: anysize_f16.h) on device operands, NHWC f16 activations, with the
+// context's profiling slot.  The forward and the reid_debug_any_*_f16 harnesses call these functions.  launch_any_conv_f16: w16 f16
+// [Cout][R R][Cin]; the tile form lands in ctx->any_f16_form.  launch_any_stem_f16: x fp32 NHWC [n][h][w][3], w16 [64][192] f16.
+int launch_any_conv_f16(reid_ctx* ctx, const _Float16* x, int n, int H, int W, int Cin, const _Float16* w16, int Cout, int R, int stride, int pad,
+                        const float* scale, const float* shift, const _Float16* residual, int relu, int relu_from, _Float16* out);
+int launch_any_stem_f16(reid_ctx* ctx, const float* x, int n, int h, int w, const _Float16* w16, const float* scale, const float* shift,
+                        _Float16* out);
+int launch_any_maxpool_f16(reid_ctx* ctx, const _Float16* x, int n, int h, int w, int c, _Float16* out);
+int launch_any_norm_f16(reid_ctx* ctx, _Float16* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta);
+int launch_any_se_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int hw, int c, int mid, const float* w1,
+                           const float* w2t, _Float16* out, float* gate_out);
+int launch_any_gem_f16(reid_ctx* ctx, const _Float16* x, int n, int hw, int c, const float* p, const float* scale, const float* shift,
+                       float* gem_out, float* emb);
 void prof_begin(reid_ctx* ctx, int kind, double flops, double bytes);
 void prof_end(reid_ctx* ctx);
 

@@ -53,6 +53,10 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _f16(a):
+    return np.ascontiguousarray(a, dtype=np.float16)
+
+
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -167,7 +171,7 @@ class Engine:
     @staticmethod
     def hw_precision_value(v):
         """None / -1 -> -1, "f32" / 0 -> 0, "f16x3" / 2 -> 2 (the values of reid_ctx_set_hw_precision); ValueError otherwise, before any
-        device call - the fp16-storage mode and every other value have no any-size forward."""
+        device call - the fp16-storage arithmetic of the any-size forward is a setting of its own (set_hw_f16), every other value has none."""
         if v is None:
             return -1
         if isinstance(v, str):
@@ -287,6 +291,45 @@ class Engine:
             finally:
                 if self.hw_ema != prev:
                     self.set_hw_ema(prev)
+        return scope()
+
+    @staticmethod
+    def hw_f16_value(v):
+        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_f16); ValueError otherwise, before any device call."""
+        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+            return int(v)
+        raise ValueError("hw_f16 must be False / 0 (other input sizes run in the arithmetic hw_precision names) or True / 1 (they run "
+                         "seres18_ibn in fp16 storage), got %r" % (v,))
+
+    def set_hw_f16(self, on):
+        """seres18_ibn at input sizes other than 256 x 128 in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16): False (default) =
+        set_hw_precision and the mode decide, True = such inputs run through libreid_hip_anysize_f16.so whatever the mode and
+        hw_precision, which keeps its value.  cares18_ibn / emares18_ibn are refused there; 256 x 128 is not affected."""
+        v = Engine.hw_f16_value(on)
+        check(self.lib.reid_ctx_set_hw_f16(self.h, v))
+        self._hw_f16 = bool(v)
+
+    @property
+    def hw_f16(self):
+        """What set_hw_f16 set last (the library's default is False)."""
+        return getattr(self, "_hw_f16", False)
+
+    def hw_f16_scope(self, on):
+        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            if on is None:
+                yield self
+                return
+            prev = self.hw_f16
+            self.set_hw_f16(on)
+            try:
+                yield self
+            finally:
+                if self.hw_f16 != prev:
+                    self.set_hw_f16(prev)
         return scope()
 
     def set_side_index(self, index):
@@ -1586,6 +1629,64 @@ class Engine:
         check(_ffi.debug_lib().reid_debug_any_conv(self.h, int(hw_precision), _ptr(x), n, h, w, cin, _ptr(wt), cout, r, int(stride), pad, _ptr(sc),
                                                    _ptr(sh), _ptr(rr), int(bool(relu)), int(relu_from), _ptr(out), C.byref(form)))
         return out[:-cout].reshape(n, ho, wo, cout), out[-cout:], form.value
+
+    # ---- libreid_hip_anysize_f16.so (reid_debug_any_*_f16): f16 operands are np.float16 arrays, handed over as their bits
+    def debug_any_conv_f16(self, x, wt, stride, scale=None, shift=None, res=None, relu=False, relu_from=0):
+        """One trunk convolution of the fp16-storage any-size forward: x float16 [n, h, w, cin], wt float16 [cout, r, r, cin], r = 3 (pad 1)
+        or 1 (pad 0).  Returns (out float16 [n, ho, wo, cout], guard [cout] - NaN unless the kernel wrote out of bounds -, the tile form)."""
+        x, wt = _f16(x), _f16(wt)
+        n, h, w, cin = x.shape
+        cout, r = wt.shape[0], wt.shape[1]
+        pad = 1 if r == 3 else 0
+        ho, wo = (h + 2 * pad - r) // stride + 1, (w + 2 * pad - r) // stride + 1
+        sc, sh = (None, None) if scale is None else (_f32(scale), _f32(shift))
+        rr = None if res is None else _f16(res)
+        if rr is not None and rr.size != n * ho * wo * cout:
+            raise ValueError("debug_any_conv_f16: the residual must have the output's %d elements" % (n * ho * wo * cout))
+        out = np.empty(n * ho * wo * cout + cout, np.float16)
+        form = C.c_int(0)
+        check(_ffi.debug_lib().reid_debug_any_conv_f16(self.h, _ptr(x), n, h, w, cin, _ptr(wt), cout, r, int(stride), pad, _ptr(sc), _ptr(sh),
+                                                       _ptr(rr), int(bool(relu)), int(relu_from), _ptr(out), C.byref(form)))
+        return out[:-cout].reshape(n, ho, wo, cout), out[-cout:], form.value
+
+    def debug_any_stem_f16(self, x, w16, scale, shift):
+        """Stem + max-pool of that forward: x fp32 [n, h, w, 3], w16 float16 [64, 192].  Returns (stem float16 [n, H1, W1, 64], its guard
+        [64], pool float16 [n, H2, W2, 64], its guard [64])."""
+        x, w16, scale, shift = _f32(x), _f16(w16), _f32(scale), _f32(shift)
+        n, h, w, _ = x.shape
+        if w16.size != 64 * 192 or scale.size != 64 or shift.size != 64 or x.shape[3] != 3:
+            raise ValueError("debug_any_stem_f16: x [n, h, w, 3], w16 [64, 192], scale [64], shift [64]")
+        h1, w1 = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        h2, w2 = (h1 - 1) // 2 + 1, (w1 - 1) // 2 + 1
+        stem = np.empty(n * h1 * w1 * 64 + 64, np.float16)
+        pool = np.empty(n * h2 * w2 * 64 + 64, np.float16)
+        check(_ffi.debug_lib().reid_debug_any_stem_f16(self.h, _ptr(x), n, h, w, _ptr(w16), _ptr(scale), _ptr(shift), _ptr(stem), _ptr(pool)))
+        return stem[:-64].reshape(n, h1, w1, 64), stem[-64:], pool[:-64].reshape(n, h2, w2, 64), pool[-64:]
+
+    def debug_any_norm_f16(self, x, half, in_gamma, in_beta):
+        x = _f16(x)
+        n, hw, c = x.shape
+        out = np.empty(x.size + c, np.float16)
+        g, b = _f32(in_gamma), _f32(in_beta)
+        check(_ffi.debug_lib().reid_debug_any_norm_f16(self.h, n, hw, c, int(half), _ptr(x), _ptr(g), _ptr(b), _ptr(out)))
+        return out
+
+    def debug_any_se_tail_f16(self, y, shortcut, w1, w2t, alias=False):
+        y, shortcut, w1, w2t = _f16(y), _f16(shortcut), _f32(w1), _f32(w2t)
+        n, hw, c = y.shape
+        out = np.empty(y.size + c, np.float16)
+        gate = np.empty(n * c + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_se_tail_f16(self.h, n, hw, c, w1.shape[0], _ptr(w1), _ptr(w2t), _ptr(y), _ptr(shortcut),
+                                                          int(bool(alias)), _ptr(out), _ptr(gate)))
+        return out, gate
+
+    def debug_any_gem_f16(self, x, p, scale, shift):
+        x, scale, shift = _f16(x), _f32(scale), _f32(shift)
+        n, hw, c = x.shape
+        gem = np.empty(n * c + c, np.float32)
+        emb = np.empty(n * c + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_gem_f16(self.h, n, hw, c, C.c_float(p), _ptr(x), _ptr(scale), _ptr(shift), _ptr(gem), _ptr(emb)))
+        return gem, emb
 
     def debug_any_front(self, crops, size, stem_w, scale, shift, mean_std=None, fused=True, frame=None):
         """The front end of the any-size forward from uint8 windows (reid_debug_any_front): resize to ``size`` = (H, W) + normalise +

@@ -39,12 +39,13 @@ def smooth_tracklets(embeddings, seqs, indices_valid, device=0):
     return out
 
 
-def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=None, strong_offsets=None, pad=10):
+def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=None, strong_offsets=None, pad=10, hw_f16=False):
     """float [n,3,H,W] after the caller's transform ((256, 128), or sides in 32 .. 512 for seres18_ibn weights in exact fp32), or a list
     of uint8 [h,w,3] images of any sizes, which the device resizes as PIL does - to ``size`` = (H, W), default (256, 128); the script's
     VeRi geometry is (224, int(ratio * 224)) - and normalises with the ImageNet values (Engine.descriptor_images_u8).
     ``hw_precision``: the arithmetic of another size for this call (Engine.set_hw_precision: "f32" / "f16x3"), restored afterwards; None
-    leaves the engine's setting alone.
+    leaves the engine's setting alone.  ``hw_f16=True`` instead (both together are a ValueError naming them): another size runs
+    seres18_ibn in fp16 storage with fp32 accumulation for this call (Engine.set_hw_f16), restored afterwards.
     ``strong_offsets``: int [n, 2] of (top, left) per image (data_transforms.strong_inference_offsets) - the second view becomes the
     script's strong_inference one, the mirror shifted by (top - pad, left - pad) over a black border (reid/data_transforms.py:130-191;
     Engine.descriptor_f32_nchw_shift / descriptor_images_u8_shift; needs ``flip``).  None is today's call and bits."""
@@ -55,6 +56,13 @@ def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=Non
         if not flip:
             raise ValueError("strong_offsets shift the mirrored view: flip must be on")
         strong_offsets, pad = Engine.check_shift(strong_offsets, len(images), pad)   # a bad value raises here, before any device call
+    from .engine import Engine as _Engine
+    if _Engine.hw_f16_value(hw_f16):                 # a bad value raises here, before any device call
+        if hw_precision is not None:
+            raise ValueError("hw_f16 and hw_precision both name the arithmetic of another size: give one of them, got hw_f16=%r and "
+                             "hw_precision=%r" % (hw_f16, hw_precision))
+        with get_engine(device).hw_f16_scope(True):
+            return extract_descriptors(images, flip, device, size, strong_offsets=strong_offsets, pad=pad)
     if hw_precision is not None:
         from .engine import Engine
         Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call

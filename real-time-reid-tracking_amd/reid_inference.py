@@ -32,6 +32,7 @@ the second view of the ResNet family the shifted mirror of get_inference_transfo
 ``reid_descriptor_images_u8_shift``), and ``attribute_dist`` adds the attribute distance (:276-289, tricks.py) to the device Jaccard
 matrix before its one download (``reid_distmat_add_l2_dev``).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -56,6 +57,19 @@ HW_ARCHS = ("seres18_hw", "cares18_hw", EMA_ARCH)
 # "cares18_hw": the same with cares18_ibn weights (the script's --backbone cares18): Engine.set_hw_siblings(True) for the call, restored after it.
 # "emares18_hw": the same with emares18_ibn weights, accepted only together with the keyword hw_ema=True (_ema_gate): Engine.set_hw_ema(True)
 # for the call, restored after it.  Without the keyword the name is refused like any unknown one, so it is not in ARCHS.
+
+
+def _f16_gate(arch, hw_f16, hw_precision):
+    """The keyword hw_f16=True belongs to arch="seres18_hw" and replaces hw_precision (ValueError, before any device call).  Returns it as a bool."""
+    from .engine import Engine
+    on = bool(Engine.hw_f16_value(hw_f16))
+    if on and arch != "seres18_hw":
+        raise ValueError("hw_f16 belongs to arch='seres18_hw' (the fp16-storage any-size forward serves seres18_ibn only); arch=%r takes none"
+                         % (arch,))
+    if on and hw_precision is not None:
+        raise ValueError("hw_f16 and hw_precision both name the arithmetic of arch='seres18_hw': give one of them, got hw_f16=%r and "
+                         "hw_precision=%r" % (hw_f16, hw_precision))
+    return on
 
 
 def _ema_gate(arch, hw_ema):
@@ -163,7 +177,7 @@ def _check_strong(arch, flip, strong_offsets, n, pad):
 
 
 def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None, hw_precision=None,
-                        strong_offsets=None, pad=10, hw_ema=False):
+                        strong_offsets=None, pad=10, hw_ema=False, hw_f16=False):
     """Descriptors of ``images`` (float32 [n,3,256,128], host) into the device rows ``d_out`` (pointer to [n, 512 + num_class]
     fp32): upload in batches of ``bs`` images, one ``reid_descriptor_f32_nchw_dev`` per batch.  Unlike the reference function
     (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253).
@@ -188,8 +202,12 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     ``strong_offsets``: int [n, 2] of (top, left) per image with ``pad`` (data_transforms.strong_inference_offsets): the second view is the
     script's strong_inference one - the mirror shifted by (top - pad, left - pad) over a black border, black being (0 - mean) / std of the
     ImageNet values (``reid_descriptor_f32_nchw_shift_dev`` / ``reid_descriptor_images_u8_shift``).  ``arch="swin"`` takes none: the
-    script gives the Swin the plain mirror.  None is today's call and bits."""
+    script gives the Swin the plain mirror.  None is today's call and bits.
+
+    ``hw_f16=True`` (``arch="seres18_hw"`` only, and instead of ``hw_precision``: both together are a ValueError): the any-size forward runs
+    in fp16 storage with fp32 accumulation - ``Engine.set_hw_f16(True)`` for this call and restored after it."""
     _ema_gate(arch, hw_ema)
+    f16 = _f16_gate(arch, hw_f16, hw_precision)
     if hw_precision is not None:
         from .engine import Engine
         if arch not in HW_ARCHS:
@@ -216,9 +234,9 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
         if view_index.shape[0] != n or (n and (view_index.min() < 0 or view_index.max() >= 2 ** 31)):
             raise ValueError("view_index must hold one non-negative index per image (%d), got %d" % (n, view_index.shape[0]))
         view_index = view_index.astype(np.int32)
-    if hw_precision is not None or arch in ("cares18_hw", EMA_ARCH):   # every argument is checked: the settings go on for the device work and off after it
+    if hw_precision is not None or f16 or arch in ("cares18_hw", EMA_ARCH):   # every argument is checked: the settings go on for the device work and off after it
         with engine.hw_precision_scope(hw_precision), engine.hw_siblings_scope(True if arch == "cares18_hw" else None), \
-                engine.hw_ema_scope(True if arch == EMA_ARCH else None):
+                engine.hw_ema_scope(True if arch == EMA_ARCH else None), (engine.hw_f16_scope(True) if f16 else contextlib.nullcontext()):
             return inference_efficient(engine, images, d_out, flip, bs, "seres18_hw", view_index, size if u8 else None,
                                        strong_offsets=strong_offsets, pad=pad)
     if u8:
@@ -251,7 +269,7 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
 def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, query_images, query_labels, query_cams,
                   query_seqs, num_gallery_cams=None, eps=0.5, la=0.05, k1=20, k2=6, flip=True, cluster_fn=None, taps=None,
                   verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None, hw_precision=None,
-                  strong_inference=False, strong_offsets=None, attribute_dist=None, pad=10, hw_ema=False):
+                  strong_inference=False, strong_offsets=None, attribute_dist=None, pad=10, hw_ema=False, hw_f16=False):
     """(CMC float32 [ng], mAP float) of the script's chain for one gallery / query pair; weights must be loaded on the engine
     (``Engine.load_seres18`` / ``build_model``).  ``taps`` (a dict) receives host copies of the intermediates the
     reference-generated fixture holds: "desc", "debiased", "jaccard", "pseudo_labels", "smoothed".
@@ -273,8 +291,10 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     (gallery first), or a ``(labels, mat_path)`` pair for tricks.attribute_rows; the rows are normalised on the host, uploaded and
     euclidean_dist(rows, rows) is added to the device Jaccard matrix (``reid_distmat_add_l2_dev``) before its download.
     ``taps["jaccard"]`` stays the matrix before the add; ``taps["dists"]`` is the one handed to DBSCAN / ``cluster_fn``.  With these
-    keywords left out the call and its bits are what they were."""
+    keywords left out the call and its bits are what they were.  ``hw_f16=True`` (``arch="seres18_hw"`` only, instead of ``hw_precision``):
+    the descriptors come from the fp16-storage any-size forward, ``Engine.set_hw_f16(True)`` for the call."""
     _ema_gate(arch, hw_ema)
+    _f16_gate(arch, hw_f16, hw_precision)
     if strong_inference or strong_offsets is not None:
         n_all = len(gallery_labels) + len(query_labels)
         if strong_offsets is None:
@@ -319,9 +339,9 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     try:
         strong = {} if strong_offsets is None else {"pad": pad}
         inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None, size=size if u8[0] else None,
-                            hw_precision=hw_precision, hw_ema=hw_ema, **(strong and dict(strong, strong_offsets=strong_offsets[:ng])))
+                            hw_precision=hw_precision, hw_ema=hw_ema, hw_f16=hw_f16, **(strong and dict(strong, strong_offsets=strong_offsets[:ng])))
         inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None,
-                            size=size if u8[1] else None, hw_precision=hw_precision, hw_ema=hw_ema,
+                            size=size if u8[1] else None, hw_precision=hw_precision, hw_ema=hw_ema, hw_f16=hw_f16,
                             **(strong and dict(strong, strong_offsets=strong_offsets[ng:])))
         if taps is not None:
             taps["desc"] = merged.numpy()
