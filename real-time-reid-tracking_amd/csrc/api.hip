@@ -871,6 +871,29 @@ static int seres18_chain_layer4(reid_ctx* ctx, int n, const Se18Block& ka, const
 }
 #endif   // REID_EXPERIMENTS
 
+// The end of every ResNet18-SE forward, behind the GeM neck: the camera bias on d_emb [n][512], then the classifier when logits are wanted
+static int se18_head(reid_ctx* ctx, int n, float* d_emb, float* d_logits) {
+    const Se18Weights& w = ctx->se18;
+    {   // SERse18_IBN.forward(x, cam): + cam_factor * cam_bias[cam] on the BNNeck output, before the classifier (:269-271)
+        const int32_t* d_cam;
+        REID_TRY(ctx_take_side(ctx, n, w.num_cams, "reid_embed (camera bias)", &d_cam));
+        if (d_cam) REID_TRY(launch_add_indexed_rows(ctx, d_emb, n, 1, 512, w.cam_bias, d_cam, w.cam_factor));
+    }
+    if (!d_logits) return REID_OK;
+    if (!w.cls_w) {
+        reid_set_error("logits requested but the weight blob has no classifier (cls.w)");
+        return REID_ERR_STATE;
+    }
+    GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.A = d_emb; p.lda = 512;
+    p.B = w.cls_w; p.ldb = 512;
+    p.M = n; p.N = w.num_class; p.K = 512;
+    p.C = d_logits; p.ldc = w.num_class;
+    return launch_gemm_f32(ctx, A_DENSE, E_BIAS, p, REID_K_CONV_GEMM, 2.0 * n * w.num_class * 512,
+                           ((double)n * 512 + (double)w.num_class * 512 + (double)n * w.num_class) * 4.0);
+}
+
 struct Se18Bufs {
     float *stem, *pool, *t[4], *stats, *a_scale, *a_shift, *se, *gem;
     float* stage[11];
@@ -1037,26 +1060,8 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
         W = Wo;
     }
     if (!gem_done) REID_TRY(launch_gem_neck(ctx, cur, n, H * W, 512, w.gem_p, w.neck_scale, w.neck_shift, b.gem, d_emb));
-    {   // SERse18_IBN.forward(x, cam): + cam_factor * cam_bias[cam] on the BNNeck output, before the classifier (:269-271)
-        const int32_t* d_cam;
-        REID_TRY(ctx_take_side(ctx, n, w.num_cams, "reid_embed (camera bias)", &d_cam));
-        if (d_cam) REID_TRY(launch_add_indexed_rows(ctx, d_emb, n, 1, 512, w.cam_bias, d_cam, w.cam_factor));
-    }
+    REID_TRY(se18_head(ctx, n, d_emb, d_logits));
     b.stage[10] = b.gem;
-    if (d_logits) {
-        if (!w.cls_w) {
-            reid_set_error("logits requested but the weight blob has no classifier (cls.w)");
-            return REID_ERR_STATE;
-        }
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = d_emb; p.lda = 512;
-        p.B = w.cls_w; p.ldb = 512;
-        p.M = n; p.N = w.num_class; p.K = 512;
-        p.C = d_logits; p.ldc = w.num_class;
-        REID_TRY(launch_gemm_f32(ctx, A_DENSE, E_BIAS, p, REID_K_CONV_GEMM, 2.0 * n * w.num_class * 512,
-                                 ((double)n * 512 + (double)w.num_class * 512 + (double)n * w.num_class) * 4.0));
-    }
     ctx->last_n = n;
     ctx->last_f16 = false;
     for (int s = 0; s < 11; ++s) { ctx->stage_ptr[s] = b.stage[s]; ctx->stage_elems[s] = 0; }
@@ -1064,12 +1069,14 @@ static int seres18_forward(reid_ctx* ctx, const void* x, bool is_u8, int n, floa
 }
 
 // ------------------------------------------------------------------------------------------------ side libraries
-// The one loader of the libraries that lie beside this one and are opened on first use: libreid_hip_siblings_f16.so (below),
-// libreid_hip_swin_v2.so and libreid_hip_swin_crops.so (swin.hip), libreid_hip_bank96.so (bank.hip).  Contract: reid_internal.h.
-int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns) {
+// The one loader of the libraries that lie beside this one and are opened on first use.  Contract: reid_internal.h.
+int SideLib::open() {
+    std::lock_guard<std::mutex> lk(m);
+    if (loaded) return REID_OK;
+    static const char self_anchor = 0;   // an address inside this library, for dladdr
     Dl_info info;
     std::string path = file;
-    if (dladdr((const void*)&open_beside_self, &info) && info.dli_fname) {
+    if (dladdr(&self_anchor, &info) && info.dli_fname) {
         const std::string self = info.dli_fname;
         const size_t slash = self.rfind('/');
         if (slash != std::string::npos) path = self.substr(0, slash + 1) + path;
@@ -1081,55 +1088,49 @@ int open_beside_self(const char* file, const char* what, std::initializer_list<c
     }
     std::string listed;
     bool all = true;
-    for (const char* name : names) {
-        all = (*fns++ = dlsym(h, name)) != nullptr && all;
-        listed += listed.empty() ? name : std::string(" / ") + name;
+    for (SideSym* s : syms) {
+        all = (s->p = dlsym(h, s->name)) != nullptr && all;
+        listed += listed.empty() ? s->name : std::string(" / ") + s->name;
     }
     if (!all) {
         dlclose(h);
         reid_set_error("%s lacks %s", path.c_str(), listed.c_str());
         return REID_ERR_STATE;
     }
+    loaded = true;
     return REID_OK;
+}
+
+int SideLib::status(hipError_t e, const SideSym& fn) const {
+    if (e == hipSuccess) return REID_OK;
+    reid_set_error("%s %s -> %s", file, fn.name, hipGetErrorString(e));
+    return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
 }
 
 // ------------------------------------------------------------------------------------------------ fp16 forward
 // libreid_hip_siblings_f16.so (siblings_f16.h), opened from the directory this library lies in the first time a sibling backbone
 // (CARes18_IBN / EMARes18_IBN) runs in the fp16-storage mode: a process that never does never opens it.  Missing library or symbol:
 // REID_ERR_STATE naming the file - no other path runs a sibling in mode 1.
-struct SiblingsF16Api {
-    decltype(&siblings_f16_ta_workspace_bytes) ta_bytes = nullptr;
-    decltype(&siblings_f16_ta_tail) ta = nullptr;
-    decltype(&siblings_f16_ema_tail) ema = nullptr;
-};
-static int siblings_f16_api(const SiblingsF16Api** out) {
-    static std::mutex m;
-    static SiblingsF16Api api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.ta) {
-        void* f[3];
-        REID_TRY(open_beside_self("libreid_hip_siblings_f16.so", "CARes18-IBN / EMARes18-IBN in the fp16-storage mode need",
-                                  {"siblings_f16_ta_workspace_bytes", "siblings_f16_ta_tail", "siblings_f16_ema_tail"}, f));
-        api.ta_bytes = (decltype(api.ta_bytes))f[0];
-        api.ema = (decltype(api.ema))f[2];
-        api.ta = (decltype(api.ta))f[1];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct SiblingsF16Lib : SideLib {
+    SiblingsF16Lib() : SideLib("libreid_hip_siblings_f16.so", "CARes18-IBN / EMARes18-IBN in the fp16-storage mode need") {}
+    SIDE_FN(ta_bytes, siblings_f16_ta_workspace_bytes);
+    SIDE_FN(ta, siblings_f16_ta_tail);
+    SIDE_FN(ema, siblings_f16_ema_tail);
+} siblings_f16;
 
-// The two launches of that library with the context's workspace, argument checks and profiling slot.
-static int launch_sibling_tail_f16(reid_ctx* ctx, const SiblingsF16Api* api, int arch, const _Float16* y, const _Float16* sc, int n, int H,
-                                   int W, int C, const float* prm, _Float16* out) {
-    ARG_CHECK(api && y && sc && prm && out && out != y && out != sc);
+// The two launches of that library (opened by the caller) with the context's workspace, argument checks and profiling slot.
+static int launch_sibling_tail_f16(reid_ctx* ctx, int arch, const _Float16* y, const _Float16* sc, int n, int H, int W, int C, const float* prm,
+                                   _Float16* out) {
+    ARG_CHECK(y && sc && prm && out && out != y && out != sc);
     void* ws = nullptr;
     if (arch == 1) {
-        const size_t bytes = api->ta_bytes(n, H, W, C);
+        const size_t bytes = siblings_f16.ta_bytes(n, H, W, C);
         ARG_CHECK(bytes > 0);
         REID_TRY(ctx_ws(ctx, "ta16.ws", bytes, &ws));
     }
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * H * W * C * 2.0 * 4.0);
-    const hipError_t e = arch == 1 ? api->ta(ctx->stream, y, sc, n, H, W, C, prm, ws, out) : api->ema(ctx->stream, y, sc, n, H, W, C, prm, out);
+    const hipError_t e = arch == 1 ? siblings_f16.ta(ctx->stream, y, sc, n, H, W, C, prm, ws, out)
+                                   : siblings_f16.ema(ctx->stream, y, sc, n, H, W, C, prm, out);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;
@@ -1178,8 +1179,7 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
     // CARes18_IBN / EMARes18_IBN: the same convolutions, the block tail from libreid_hip_siblings_f16.so.  Everything that exists for
     // the SE tail only - the pooled statistics of conv2, the fused SE build of the layer-1 kernel, the f16_se_tail switch - is skipped.
     const bool sibling = w.arch != 0;
-    const SiblingsF16Api* sib = nullptr;
-    if (sibling) REID_TRY(siblings_f16_api(&sib));
+    if (sibling) REID_TRY(siblings_f16.open());
     f16 *pad_in, *stem, *pool, *tbase;
     float *stats, *a_scale, *a_shift, *se, *gem;
     REID_TRY(ctx_ws(ctx, "se18h.pad", (size_t)n * PAD_H * PAD_W * 4 * 2, (void**)&pad_in));
@@ -1275,7 +1275,7 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
         }
         f16* out = c1;
         if (sibling) {   // TripletAttention / EMA + shortcut + ReLU (CARes18.py:150-157, EMA_Res18.py:79-86)
-            REID_TRY(launch_sibling_tail_f16(ctx, sib, w.arch, y, shortcut, n, Ho, Wo, k.c, w.arch == 1 ? k.ta : k.ema, out));
+            REID_TRY(launch_sibling_tail_f16(ctx, w.arch, y, shortcut, n, Ho, Wo, k.c, w.arch == 1 ? k.ta : k.ema, out));
         } else if (ctx->f16_se_tail && ctx->debug_keep != 1) {   // gate + combine in one launch, sliced per image when there are few images
             REID_TRY(launch_se_tail_f16(ctx, stats, n, c64 ? 1 : tiles, k.c, k.mid, hw, k.se_w1, k.se_w2, y, shortcut, out));
         } else {
@@ -1288,26 +1288,8 @@ static int seres18_forward_f16(reid_ctx* ctx, const void* x, bool is_u8, int n, 
         W = Wo;
     }
     REID_TRY(launch_gem_neck_f16(ctx, cur, n, H * W, 512, w.gem_p, w.neck_scale, w.neck_shift, gem, d_emb));
-    {
-        const int32_t* d_cam;
-        REID_TRY(ctx_take_side(ctx, n, w.num_cams, "reid_embed (camera bias)", &d_cam));
-        if (d_cam) REID_TRY(launch_add_indexed_rows(ctx, d_emb, n, 1, 512, w.cam_bias, d_cam, w.cam_factor));
-    }
+    REID_TRY(se18_head(ctx, n, d_emb, d_logits));
     stage[10] = gem;
-    if (d_logits) {
-        if (!w.cls_w) {
-            reid_set_error("logits requested but the weight blob has no classifier (cls.w)");
-            return REID_ERR_STATE;
-        }
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = d_emb; p.lda = 512;
-        p.B = w.cls_w; p.ldb = 512;
-        p.M = n; p.N = w.num_class; p.K = 512;
-        p.C = d_logits; p.ldc = w.num_class;
-        REID_TRY(launch_gemm_f32(ctx, A_DENSE, E_BIAS, p, REID_K_CONV_GEMM, 2.0 * n * w.num_class * 512,
-                                 ((double)n * 512 + (double)w.num_class * 512 + (double)n * w.num_class) * 4.0));
-    }
     ctx->last_n = n;
     ctx->last_f16 = true;
     for (int s2 = 0; s2 < 11; ++s2) { ctx->stage_ptr[s2] = stage[s2]; ctx->stage_elems[s2] = 0; }
@@ -1521,132 +1503,51 @@ extern "C" int reid_embed_f32_nchw(reid_ctx* ctx, const float* x, int n, float* 
 // and an identity residual at once (conv_f32.hip wants hw % 128 == 0 and Wo | 32, its general form has no BN epilogue or ReLU) - and
 // the tails between them from libreid_hip_anysize.so (anysize.h).  A GEMM row is one output pixel summed in k order whatever tile it
 // falls into and no launch splits K, so the bits of an image do not depend on the pass it ran in.
-struct AnysizeApi {
-    decltype(&anysize_norm) norm = nullptr;
-    decltype(&anysize_se_tail) se_tail = nullptr;
-    decltype(&anysize_gem) gem = nullptr;
-    decltype(&anysize_nchw_to_nhwc3) to_nhwc = nullptr;
-    decltype(&anysize_resize_norm) resize = nullptr;
-};
-static int anysize_api(const AnysizeApi** out) {
-    static std::mutex m;
-    static AnysizeApi api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.norm) {
-        void* f[5];
-        REID_TRY(open_beside_self("libreid_hip_anysize.so", "ResNet18-IBN-SE at an input size other than 256 x 128 needs",
-                                  {"anysize_norm", "anysize_se_tail", "anysize_gem", "anysize_nchw_to_nhwc3", "anysize_resize_norm"}, f));
-        api.se_tail = (decltype(api.se_tail))f[1];
-        api.gem = (decltype(api.gem))f[2];
-        api.to_nhwc = (decltype(api.to_nhwc))f[3];
-        api.resize = (decltype(api.resize))f[4];
-        api.norm = (decltype(api.norm))f[0];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct AnysizeLib : SideLib {
+    AnysizeLib() : SideLib("libreid_hip_anysize.so", "ResNet18-IBN-SE at an input size other than 256 x 128 needs") {}
+    SIDE_FN(norm, anysize_norm);
+    SIDE_FN(se_tail, anysize_se_tail);
+    SIDE_FN(gem, anysize_gem);
+    SIDE_FN(to_nhwc, anysize_nchw_to_nhwc3);
+    SIDE_FN(resize, anysize_resize_norm);
+} anysize;
 
 // ... and the trunk convolutions of that forward in the fp32-class arithmetic (reid_ctx_set_hw_precision 2): anysize_x3.h
-struct AnysizeX3Api {
-    decltype(&anysize_x3_conv) conv = nullptr;
-};
-static int anysize_x3_api(const AnysizeX3Api** out) {
-    static std::mutex m;
-    static AnysizeX3Api api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.conv) {
-        void* f[1];
-        REID_TRY(open_beside_self("libreid_hip_anysize_x3.so", "ResNet18-IBN-SE at another input size in the fp32-class arithmetic needs",
-                                  {"anysize_x3_conv"}, f));
-        api.conv = (decltype(api.conv))f[0];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct AnysizeX3Lib : SideLib {
+    AnysizeX3Lib() : SideLib("libreid_hip_anysize_x3.so", "ResNet18-IBN-SE at another input size in the fp32-class arithmetic needs") {}
+    SIDE_FN(conv, anysize_x3_conv);
+} anysize_x3;
 
 // ... and that forward in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16 1): anysize_f16.h
-struct AnysizeF16Api {
-    decltype(&anysize_f16_conv) conv = nullptr;
-    decltype(&anysize_f16_stem) stem = nullptr;
-    decltype(&anysize_f16_maxpool) maxpool = nullptr;
-    decltype(&anysize_f16_norm) norm = nullptr;
-    decltype(&anysize_f16_se_tail) se_tail = nullptr;
-    decltype(&anysize_f16_gem) gem = nullptr;
-};
-static int anysize_f16_api(const AnysizeF16Api** out) {
-    static std::mutex m;
-    static AnysizeF16Api api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.conv) {
-        void* f[6];
-        REID_TRY(open_beside_self("libreid_hip_anysize_f16.so", "ResNet18-IBN-SE at another input size in the fp16-storage arithmetic needs",
-                                  {"anysize_f16_conv", "anysize_f16_stem", "anysize_f16_maxpool", "anysize_f16_norm", "anysize_f16_se_tail",
-                                   "anysize_f16_gem"}, f));
-        api.stem = (decltype(api.stem))f[1];
-        api.maxpool = (decltype(api.maxpool))f[2];
-        api.norm = (decltype(api.norm))f[3];
-        api.se_tail = (decltype(api.se_tail))f[4];
-        api.gem = (decltype(api.gem))f[5];
-        api.conv = (decltype(api.conv))f[0];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct AnysizeF16Lib : SideLib {
+    AnysizeF16Lib() : SideLib("libreid_hip_anysize_f16.so", "ResNet18-IBN-SE at another input size in the fp16-storage arithmetic needs") {}
+    SIDE_FN(conv, anysize_f16_conv);
+    SIDE_FN(stem, anysize_f16_stem);
+    SIDE_FN(maxpool, anysize_f16_maxpool);
+    SIDE_FN(norm, anysize_f16_norm);
+    SIDE_FN(se_tail, anysize_f16_se_tail);
+    SIDE_FN(gem, anysize_f16_gem);
+} anysize_f16;
 
 // ... and its front end from uint8 windows in one kernel (reid_frame_submit_hw, reid_embed_frame_u8_hw): anysize_front.h
-static int anysize_front_api(decltype(&anysize_front)* out) {
-    static std::mutex m;
-    static decltype(&anysize_front) front = nullptr;
-    std::lock_guard<std::mutex> lk(m);
-    if (!front) {
-        void* f[1];
-        REID_TRY(open_beside_self("libreid_hip_anysize_front.so", "the frame pipeline of ResNet18-IBN-SE at another input size needs",
-                                  {"anysize_front"}, f));
-        front = (decltype(front))f[0];
-    }
-    *out = front;
-    return REID_OK;
-}
+static struct AnysizeFrontLib : SideLib {
+    AnysizeFrontLib() : SideLib("libreid_hip_anysize_front.so", "the frame pipeline of ResNet18-IBN-SE at another input size needs") {}
+    SIDE_FN(front, anysize_front);
+} anysize_front_lib;
 
 // ... and the TripletAttention block tail of cares18_ibn (reid_ctx_set_hw_siblings 1): anysize_ca.h
-struct AnysizeCaApi {
-    decltype(&anysize_ca_workspace_bytes) ws_bytes = nullptr;
-    decltype(&anysize_ca_tail) tail = nullptr;
-};
-static int anysize_ca_api(const AnysizeCaApi** out) {
-    static std::mutex m;
-    static AnysizeCaApi api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.tail) {
-        void* f[2];
-        REID_TRY(open_beside_self("libreid_hip_anysize_ca.so", "CARes18-IBN at an input size other than 256 x 128 needs",
-                                  {"anysize_ca_workspace_bytes", "anysize_ca_tail"}, f));
-        api.ws_bytes = (decltype(api.ws_bytes))f[0];
-        api.tail = (decltype(api.tail))f[1];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct AnysizeCaLib : SideLib {
+    AnysizeCaLib() : SideLib("libreid_hip_anysize_ca.so", "CARes18-IBN at an input size other than 256 x 128 needs") {}
+    SIDE_FN(ws_bytes, anysize_ca_workspace_bytes);
+    SIDE_FN(tail, anysize_ca_tail);
+} anysize_ca;
 
 // ... and the EMA block tail of emares18_ibn (reid_ctx_set_hw_ema 1): anysize_ema.h
-struct AnysizeEmaApi {
-    decltype(&anysize_ema_workspace_bytes) ws_bytes = nullptr;
-    decltype(&anysize_ema_tail) tail = nullptr;
-};
-static int anysize_ema_api(const AnysizeEmaApi** out) {
-    static std::mutex m;
-    static AnysizeEmaApi api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.tail) {
-        void* f[2];
-        REID_TRY(open_beside_self("libreid_hip_anysize_ema.so", "EMARes18-IBN at an input size other than 256 x 128 needs",
-                                  {"anysize_ema_workspace_bytes", "anysize_ema_tail"}, f));
-        api.ws_bytes = (decltype(api.ws_bytes))f[0];
-        api.tail = (decltype(api.tail))f[1];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct AnysizeEmaLib : SideLib {
+    AnysizeEmaLib() : SideLib("libreid_hip_anysize_ema.so", "EMARes18-IBN at an input size other than 256 x 128 needs") {}
+    SIDE_FN(ws_bytes, anysize_ema_workspace_bytes);
+    SIDE_FN(tail, anysize_ema_tail);
+} anysize_ema;
 
 bool se_any_routes(const reid_ctx* ctx, int h, int w) { return h != IMG_H || w != IMG_W || ctx->anysize_force != 0; }
 
@@ -1673,10 +1574,8 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
                            "seres18_ibn only", who, h, w, kArch[wt.arch]);
             return REID_ERR_ARG;
         }
-        const AnysizeApi* api;
-        REID_TRY(anysize_api(&api));
-        const AnysizeF16Api* f16api;
-        return anysize_f16_api(&f16api);
+        REID_TRY(anysize.open());
+        return anysize_f16.open();
     }
     if (ctx->hw_siblings && wt.arch == 2 && !ctx->hw_ema) {
         reid_set_error("%s: input size %d x %d: loaded architecture %s has no any-size tail; with reid_ctx_set_hw_siblings 1 only cares18_ibn "
@@ -1689,20 +1588,10 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
                        "mode %d (256 x 128 runs every architecture and mode)", who, h, w, kArch[wt.arch], ctx->precision);
         return REID_ERR_ARG;
     }
-    const AnysizeApi* api;
-    REID_TRY(anysize_api(&api));
-    if (ctx->hw_precision == 2) {
-        const AnysizeX3Api* x3;
-        REID_TRY(anysize_x3_api(&x3));
-    }
-    if (wt.arch == 1 && ctx->any_ca != 0) {
-        const AnysizeCaApi* ca;
-        REID_TRY(anysize_ca_api(&ca));
-    }
-    if (wt.arch == 2 && ctx->any_ema != 0) {
-        const AnysizeEmaApi* ema;
-        REID_TRY(anysize_ema_api(&ema));
-    }
+    REID_TRY(anysize.open());
+    if (ctx->hw_precision == 2) REID_TRY(anysize_x3.open());
+    if (wt.arch == 1 && ctx->any_ca != 0) REID_TRY(anysize_ca.open());
+    if (wt.arch == 2 && ctx->any_ema != 0) REID_TRY(anysize_ema.open());
     return REID_OK;
 }
 
@@ -1719,59 +1608,43 @@ int se_any_front_ready(reid_ctx* ctx, int h, int w, const float** mean_std6, con
         return REID_OK;
     }
     if (ctx->hw_f16) return REID_OK;   // its passes go through resize + normalise and the f16 stem: the fused fp32 front end is not needed
-    decltype(&anysize_front) front;
-    return anysize_front_api(&front);
-}
-
-static int any_launched(hipError_t e, const char* what) {
-    if (e != hipSuccess) {
-        reid_set_error("libreid_hip_anysize.so %s -> %s", what, hipGetErrorString(e));
-        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-    }
-    return REID_OK;
+    return anysize_front_lib.open();
 }
 
 int launch_any_norm(reid_ctx* ctx, float* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta, const float* bn_scale,
                     const float* bn_shift) {
-    const AnysizeApi* api;
-    REID_TRY(anysize_api(&api));
+    REID_TRY(anysize.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * (bn_scale ? c : half) * 12.0);
-    const hipError_t e = api->norm(ctx->stream, x, n, hw, c, half, in_gamma, in_beta, bn_scale, bn_shift);
+    const hipError_t e = anysize.norm(ctx->stream, x, n, hw, c, half, in_gamma, in_beta, bn_scale, bn_shift);
     prof_end(ctx);
-    return any_launched(e, "anysize_norm");
+    return anysize.status(e, anysize.norm);
 }
 
 int launch_any_se_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int hw, int c, int mid, const float* w1, const float* w2t,
                        float* out, float* gate_out) {
-    const AnysizeApi* api;
-    REID_TRY(anysize_api(&api));
+    REID_TRY(anysize.open());
     float* pooled;
     REID_TRY(ctx_ws(ctx, "any.pooled", (size_t)n * c * 4, (void**)&pooled));
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 16.0);
-    const hipError_t e = api->se_tail(ctx->stream, y, sc, n, hw, c, mid, w1, w2t, pooled, out, gate_out);
+    const hipError_t e = anysize.se_tail(ctx->stream, y, sc, n, hw, c, mid, w1, w2t, pooled, out, gate_out);
     prof_end(ctx);
-    return any_launched(e, "anysize_se_tail");
+    return anysize.status(e, anysize.se_tail);
 }
 
 int launch_any_ca_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int H, int W, int C, const float* prm, float* out,
                        const float** maps_out, const float** gates_out) {
-    const AnysizeCaApi* api;
-    REID_TRY(anysize_ca_api(&api));
-    const size_t bytes = api->ws_bytes(n, H, W, C);
+    REID_TRY(anysize_ca.open());
+    const size_t bytes = anysize_ca.ws_bytes(n, H, W, C);
     if (!bytes) {
-        reid_set_error("libreid_hip_anysize_ca.so: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", H, W,
-                       C, n);
+        reid_set_error("%s: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", anysize_ca.file, H, W, C, n);
         return REID_ERR_ARG;
     }
     void* ws;
     REID_TRY(ctx_ws(ctx, "any.ca", bytes, &ws));
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * H * W * C * 20.0);
-    const hipError_t e = api->tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
+    const hipError_t e = anysize_ca.tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
     prof_end(ctx);
-    if (e != hipSuccess) {
-        reid_set_error("libreid_hip_anysize_ca.so anysize_ca_tail -> %s", hipGetErrorString(e));
-        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-    }
+    REID_TRY(anysize_ca.status(e, anysize_ca.tail));
     if (maps_out) *maps_out = (const float*)ws;
     if (gates_out) *gates_out = (const float*)ws + (size_t)n * 2 * ((size_t)H * W + (size_t)C * W + (size_t)H * C);
     return REID_OK;
@@ -1779,23 +1652,18 @@ int launch_any_ca_tail(reid_ctx* ctx, const float* y, const float* sc, int n, in
 
 int launch_any_ema_tail(reid_ctx* ctx, const float* y, const float* sc, int n, int H, int W, int C, const float* prm, float* out,
                         const float** sig_out, const float** small_out) {
-    const AnysizeEmaApi* api;
-    REID_TRY(anysize_ema_api(&api));
-    const size_t bytes = api->ws_bytes(n, H, W, C);
+    REID_TRY(anysize_ema.open());
+    const size_t bytes = anysize_ema.ws_bytes(n, H, W, C);
     if (!bytes) {
-        reid_set_error("libreid_hip_anysize_ema.so: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", H, W,
-                       C, n);
+        reid_set_error("%s: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", anysize_ema.file, H, W, C, n);
         return REID_ERR_ARG;
     }
     void* ws;
     REID_TRY(ctx_ws(ctx, "any.ema", bytes, &ws));
     prof_begin(ctx, REID_K_ELEMENTWISE, (double)n * H * W * C * C / 32.0 * 36.0, (double)n * H * W * C * 20.0);
-    const hipError_t e = api->tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
+    const hipError_t e = anysize_ema.tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
     prof_end(ctx);
-    if (e != hipSuccess) {
-        reid_set_error("libreid_hip_anysize_ema.so anysize_ema_tail -> %s", hipGetErrorString(e));
-        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-    }
+    REID_TRY(anysize_ema.status(e, anysize_ema.tail));
     const float* sig = (const float*)((const double*)ws + (size_t)n * anysize_ema_slabs(H, W, C) * 3 * C);
     if (sig_out) *sig_out = sig;
     if (small_out) *small_out = sig + (size_t)n * (H + W) * C;
@@ -1804,12 +1672,11 @@ int launch_any_ema_tail(reid_ctx* ctx, const float* y, const float* sc, int n, i
 
 int launch_any_gem(reid_ctx* ctx, const float* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out,
                    float* emb) {
-    const AnysizeApi* api;
-    REID_TRY(anysize_api(&api));
+    REID_TRY(anysize.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 4.0);
-    const hipError_t e = api->gem(ctx->stream, x, n, hw, c, p, scale, shift, gem_out, emb);
+    const hipError_t e = anysize.gem(ctx->stream, x, n, hw, c, p, scale, shift, gem_out, emb);
     prof_end(ctx);
-    return any_launched(e, "anysize_gem");
+    return anysize.status(e, anysize.gem);
 }
 
 // one convolution of the any-size forward: NHWC fp32 in / out, folded BN (+ identity residual) (+ ReLU from column relu_from on)
@@ -1838,38 +1705,186 @@ int launch_any_conv(reid_ctx* ctx, int arith, const float* x, int n, int H, int 
                     const float* scale, const float* shift, const float* residual, int relu, int relu_from, float* out) {
     if (arith == 0) return any_conv(ctx, A_IM2COL, x, n, H, W, Cin, wgt, Cout, R, stride, pad, scale, shift, residual, relu, relu_from, out);
     ARG_CHECK(arith == 2);
-    const AnysizeX3Api* api;
-    REID_TRY(anysize_x3_api(&api));
+    REID_TRY(anysize_x3.open());
     const _Float16* w16;
     REID_TRY(split_weights_of(ctx, wgt, Cout, R * R, Cin, &w16));
     const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - R) / stride + 1;
     const double m = (double)n * Ho * Wo, ktrue = (double)R * R * Cin;
     prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * Cout * ktrue,
                ((double)n * H * W * Cin + m * Cout * (residual ? 2.0 : 1.0)) * 4.0 + (double)Cout * ktrue * 6.0);
-    const hipError_t e = api->conv(ctx->stream, x, n, H, W, Cin, w16, ctx->split_terms, Cout, R, stride, pad, scale, shift, residual, relu,
-                                   relu_from, out, ctx->fault, &ctx->any_conv_form);
+    const hipError_t e = anysize_x3.conv(ctx->stream, x, n, H, W, Cin, w16, ctx->split_terms, Cout, R, stride, pad, scale, shift, residual, relu,
+                                         relu_from, out, ctx->fault, &ctx->any_conv_form);
     prof_end(ctx);
-    if (e != hipSuccess) {
-        reid_set_error("libreid_hip_anysize_x3.so anysize_x3_conv -> %s", hipGetErrorString(e));
-        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-    }
-    return REID_OK;
+    return anysize_x3.status(e, anysize_x3.conv);
 }
+
+// stem: conv7x7 s2 p3 + BN, no ReLU (SERes18_IBN.py:251-253), then MaxPool2d(3, 2, 1) with -inf padding (:254; maxpool3s2_kernel skips
+// the taps outside the map, at odd sizes too).  x: fp32 NHWC [n][h][w][3] on the device
+static int any_stem_pool(reid_ctx* ctx, const float* x, int n, int h, int w, const float* stem_w, const float* scale, const float* shift,
+                         float* stem, float* pool) {
+    REID_TRY(any_conv(ctx, A_STEM_F32, x, n, h, w, 3, stem_w, 64, 7, 2, 3, scale, shift, nullptr, 0, 0, stem));
+    return launch_maxpool3s2(ctx, stem, n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 64, pool);
+}
+
+// n uploaded uint8 windows through the cv2-style bilinear resize to h x w and (v - mean[c]) / std[c]: fp32 NHWC in the workspace se18.in_nhwc
+static int any_resize_norm(reid_ctx* ctx, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
+                           const float* mean_std6, float** nhwc) {
+    REID_TRY(anysize.open());
+    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)n * h * w * 3 * 4, (void**)nhwc));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * w * 15.0);
+    const hipError_t e = anysize.resize(ctx->stream, d_src, d_off, d_hw, n, h, w, pitch, mean_std6, *nhwc);
+    prof_end(ctx);
+    return anysize.status(e, anysize.resize);
+}
+
+// The front end of the any-size forward from uploaded uint8 windows, as the new entries and reid_debug_any_front launch it:
+// fused = any_front_kernel (libreid_hip_anysize_front.so), else the three launches of the other reid_*_hw entries - the same bits.
+// stem [n][H1][W1][64] is written by the three launches only (fused: may be NULL); pool [n][H2][W2][64].
+int launch_any_front(reid_ctx* ctx, int fused, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
+                     const float* mean_std6, const float* stem_w, const float* scale, const float* shift, float* stem, float* pool) {
+    if (fused) {
+        REID_TRY(anysize_front_lib.open());
+        const int H1 = (h - 1) / 2 + 1, W1 = (w - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
+        prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * n * H1 * W1 * 64 * 147.0, (double)n * h * w * 3.0 + (double)n * H2 * W2 * 64 * 4.0 + 64 * 147 * 4.0);
+        const hipError_t e = anysize_front_lib.front(ctx->stream, d_src, d_off, d_hw, n, h, w, pitch, mean_std6, stem_w, scale, shift, pool);
+        prof_end(ctx);
+        return anysize_front_lib.status(e, anysize_front_lib.front);
+    }
+    ARG_CHECK(stem != nullptr);
+    float* nhwc;
+    REID_TRY(any_resize_norm(ctx, d_src, d_off, d_hw, n, h, w, pitch, mean_std6, &nhwc));
+    return any_stem_pool(ctx, nhwc, n, h, w, stem_w, scale, shift, stem, pool);
+}
+
+// ---- the same forward in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16 1): every kernel from libreid_hip_anysize_f16.so
+int launch_any_conv_f16(reid_ctx* ctx, const _Float16* x, int n, int H, int W, int Cin, const _Float16* w16, int Cout, int R, int stride, int pad,
+                        const float* scale, const float* shift, const _Float16* residual, int relu, int relu_from, _Float16* out) {
+    REID_TRY(anysize_f16.open());
+    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - R) / stride + 1;
+    const double m = (double)n * Ho * Wo, ktrue = (double)R * R * Cin;
+    prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * Cout * ktrue, ((double)n * H * W * Cin + m * Cout * (residual ? 2.0 : 1.0) + (double)Cout * ktrue) * 2.0);
+    const hipError_t e = anysize_f16.conv(ctx->stream, x, n, H, W, Cin, w16, Cout, R, stride, pad, scale, shift, residual, relu, relu_from, out,
+                                          &ctx->any_f16_form);
+    prof_end(ctx);
+    return anysize_f16.status(e, anysize_f16.conv);
+}
+
+int launch_any_stem_f16(reid_ctx* ctx, const float* x, int n, int h, int w, const _Float16* w16, const float* scale, const float* shift,
+                        _Float16* out) {
+    REID_TRY(anysize_f16.open());
+    const double m = (double)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1);
+    prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * 64 * 147.0, (double)n * h * w * 12.0 + m * 128.0 + 64 * 192 * 2.0);
+    const hipError_t e = anysize_f16.stem(ctx->stream, x, n, h, w, w16, scale, shift, out);
+    prof_end(ctx);
+    return anysize_f16.status(e, anysize_f16.stem);
+}
+
+int launch_any_maxpool_f16(reid_ctx* ctx, const _Float16* x, int n, int h, int w, int c, _Float16* out) {
+    REID_TRY(anysize_f16.open());
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, ((double)n * h * w * c + (double)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) * c) * 2.0);
+    const hipError_t e = anysize_f16.maxpool(ctx->stream, x, n, h, w, c, out);
+    prof_end(ctx);
+    return anysize_f16.status(e, anysize_f16.maxpool);
+}
+
+int launch_any_norm_f16(reid_ctx* ctx, _Float16* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta) {
+    REID_TRY(anysize_f16.open());
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * half * 6.0);
+    const hipError_t e = anysize_f16.norm(ctx->stream, x, n, hw, c, half, in_gamma, in_beta);
+    prof_end(ctx);
+    return anysize_f16.status(e, anysize_f16.norm);
+}
+
+int launch_any_se_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int hw, int c, int mid, const float* w1,
+                           const float* w2t, _Float16* out, float* gate_out) {
+    REID_TRY(anysize_f16.open());
+    float* pooled;
+    REID_TRY(ctx_ws(ctx, "any.pooled", (size_t)n * c * 4, (void**)&pooled));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 8.0);
+    const hipError_t e = anysize_f16.se_tail(ctx->stream, y, sc, n, hw, c, mid, w1, w2t, pooled, out, gate_out);
+    prof_end(ctx);
+    return anysize_f16.status(e, anysize_f16.se_tail);
+}
+
+int launch_any_gem_f16(reid_ctx* ctx, const _Float16* x, int n, int hw, int c, const float* p, const float* scale, const float* shift,
+                       float* gem_out, float* emb) {
+    REID_TRY(anysize_f16.open());
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 2.0);
+    const hipError_t e = anysize_f16.gem(ctx->stream, x, n, hw, c, p, scale, shift, gem_out, emb);
+    prof_end(ctx);
+    return anysize_f16.status(e, anysize_f16.gem);
+}
+
+// ---- the trunk of the any-size forward, written once for its two arithmetics.  An arithmetic is the element type T of the activations, the
+// names of its workspaces (the 256 x 128 forward of the same storage shares these buffers by name), the bound on a pass's stem rows, and the
+// launches of the walk; weights are passed as they lie in the fp32 blob.
+struct AnyF32 {
+    typedef float T;
+    static constexpr const char *stem_ws = "se18.stem", *pool_ws = "se18.pool", *ring_ws = "se18.t";
+    static constexpr long long row_bound = 1ll << 31;   // the GEMM's row index is an int (element offsets are 64-bit)
+    int arith;                                          // launch_any_conv's: 0 exact fp32, 2 fp32-class
+    int conv(reid_ctx* ctx, const T* x, int n, int H, int W, int Cin, const float* wgt, int Cout, int R, int stride, int pad, const float* scale,
+             const float* shift, const T* residual, int relu, int relu_from, T* out) const {
+        return launch_any_conv(ctx, arith, x, n, H, W, Cin, wgt, Cout, R, stride, pad, scale, shift, residual, relu, relu_from, out);
+    }
+    int norm(reid_ctx* ctx, T* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta) const {
+        return launch_any_norm(ctx, x, n, hw, c, half, in_gamma, in_beta, nullptr, nullptr);
+    }
+    int tail(reid_ctx* ctx, const Se18Block& k, const T* y, const T* shortcut, int n, int Ho, int Wo, T* out) const {
+        const int arch = ctx->se18.arch;
+        if (arch == 1) {   // CARes18_IBN: TripletAttention + shortcut + ReLU (CARes18.py:150-157); any_ca 0: the 256 x 128 forward's kernels
+            if (ctx->any_ca) return launch_any_ca_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out);
+            return launch_ta_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out);
+        }
+        if (arch == 2) {   // EMARes18_IBN: EMA + shortcut + ReLU (EMA_Res18.py:79-86); any_ema 0: the 256 x 128 forward's kernel
+            if (ctx->any_ema) return launch_any_ema_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ema, out);
+            return launch_ema_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ema, out);
+        }
+        return launch_any_se_tail(ctx, y, shortcut, n, Ho * Wo, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr);
+    }
+    int gem(reid_ctx* ctx, const T* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out, float* emb) const {
+        return launch_any_gem(ctx, x, n, hw, c, p, scale, shift, gem_out, emb);
+    }
+};
+// fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16 1): the weights are the f16 image of the blob reid_seres18_load makes whatever the
+// mode (Se18Weights::h; the stem's [64][192] packed rows are in it); the fp32 folded-BN vectors, SE weights and neck are the fp32 forward's
+struct AnyF16 {
+    typedef _Float16 T;
+    static constexpr const char *stem_ws = "se18h.stem", *pool_ws = "se18h.pool", *ring_ws = "se18h.t";
+    static constexpr long long row_bound = (1ll << 31) - 256;
+    int conv(reid_ctx* ctx, const T* x, int n, int H, int W, int Cin, const float* wgt, int Cout, int R, int stride, int pad, const float* scale,
+             const float* shift, const T* residual, int relu, int relu_from, T* out) const {
+        return launch_any_conv_f16(ctx, x, n, H, W, Cin, ctx->se18.h(wgt), Cout, R, stride, pad, scale, shift, residual, relu, relu_from, out);
+    }
+    int norm(reid_ctx* ctx, T* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta) const {
+        return launch_any_norm_f16(ctx, x, n, hw, c, half, in_gamma, in_beta);
+    }
+    int tail(reid_ctx* ctx, const Se18Block& k, const T* y, const T* shortcut, int n, int Ho, int Wo, T* out) const {
+        return launch_any_se_tail_f16(ctx, y, shortcut, n, Ho * Wo, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr);
+    }
+    int gem(reid_ctx* ctx, const T* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out, float* emb) const {
+        return launch_any_gem_f16(ctx, x, n, hw, c, p, scale, shift, gem_out, emb);
+    }
+};
 
 // The buffers of one pass of n images at h x w: the stem map (want_stem; the fused front end never writes one), the pooled map, the
 // trunk's ring and the GeM output
+template <class T>
 struct AnyBufs {
     int H1, W1, H2, W2;
     size_t elems[11], per;
-    float *stem = nullptr, *pool, *tbase, *gem;
+    T *stem = nullptr, *pool, *tbase;
+    float* gem;
 };
-static int any_bufs(reid_ctx* ctx, int n, int h, int w, bool want_stem, AnyBufs& b) {
+template <class Ar>
+static int any_bufs(reid_ctx* ctx, int n, int h, int w, bool want_stem, AnyBufs<typename Ar::T>& b) {
     const Se18Weights& wt = ctx->se18;
     const bool keep = ctx->debug_keep != 0;
+    const size_t es = sizeof(typename Ar::T);
     b.H1 = (h + 6 - 7) / 2 + 1, b.W1 = (w + 6 - 7) / 2 + 1;              // conv 7x7 s2 p3
     b.H2 = (b.H1 + 2 - 3) / 2 + 1, b.W2 = (b.W1 + 2 - 3) / 2 + 1;        // MaxPool2d(3, 2, 1)
     const int H1 = b.H1, W1 = b.W1, H2 = b.H2, W2 = b.W2;
-    ARG_CHECK((long long)n * H1 * W1 < (1ll << 31));                     // the GEMM's row index is an int (element offsets are 64-bit)
+    ARG_CHECK((long long)n * H1 * W1 < Ar::row_bound);
     size_t* elems = b.elems;
     elems[0] = (size_t)H1 * W1 * 64;
     elems[1] = (size_t)H2 * W2 * 64;
@@ -1886,327 +1901,97 @@ static int any_bufs(reid_ctx* ctx, int n, int h, int w, bool want_stem, AnyBufs&
     }
     elems[10] = 512;
     b.per = per;
-    if (want_stem) REID_TRY(ctx_ws(ctx, "se18.stem", (size_t)n * elems[0] * 4, (void**)&b.stem));
-    REID_TRY(ctx_ws(ctx, "se18.pool", (size_t)n * per * 4, (void**)&b.pool));
-    REID_TRY(ctx_ws(ctx, "se18.t", (size_t)n * per * 4 * (keep ? 4 * 8 : 4), (void**)&b.tbase));
+    if (want_stem) REID_TRY(ctx_ws(ctx, Ar::stem_ws, (size_t)n * elems[0] * es, (void**)&b.stem));
+    REID_TRY(ctx_ws(ctx, Ar::pool_ws, (size_t)n * per * es, (void**)&b.pool));
+    REID_TRY(ctx_ws(ctx, Ar::ring_ws, (size_t)n * per * es * (keep ? 4 * 8 : 4), (void**)&b.tbase));
     REID_TRY(ctx_ws(ctx, "se18.gem", (size_t)n * 512 * 4, (void**)&b.gem));
     return REID_OK;
 }
 
-// stem: conv7x7 s2 p3 + BN, no ReLU (SERes18_IBN.py:251-253), then MaxPool2d(3, 2, 1) with -inf padding (:254; maxpool3s2_kernel skips
-// the taps outside the map, at odd sizes too).  x: fp32 NHWC [n][h][w][3] on the device
-static int any_stem_pool(reid_ctx* ctx, const float* x, int n, int h, int w, const float* stem_w, const float* scale, const float* shift,
-                         float* stem, float* pool) {
-    REID_TRY(any_conv(ctx, A_STEM_F32, x, n, h, w, 3, stem_w, 64, 7, 2, 3, scale, shift, nullptr, 0, 0, stem));
-    return launch_maxpool3s2(ctx, stem, n, (h - 1) / 2 + 1, (w - 1) / 2 + 1, 64, pool);
-}
-
-// The front end of the any-size forward from uploaded uint8 windows, as the new entries and reid_debug_any_front launch it:
-// fused = any_front_kernel (libreid_hip_anysize_front.so), else the three launches of the other reid_*_hw entries - the same bits.
-// stem [n][H1][W1][64] is written by the three launches only (fused: may be NULL); pool [n][H2][W2][64].
-int launch_any_front(reid_ctx* ctx, int fused, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
-                     const float* mean_std6, const float* stem_w, const float* scale, const float* shift, float* stem, float* pool) {
-    if (fused) {
-        decltype(&anysize_front) front;
-        REID_TRY(anysize_front_api(&front));
-        const int H1 = (h - 1) / 2 + 1, W1 = (w - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
-        prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * n * H1 * W1 * 64 * 147.0, (double)n * h * w * 3.0 + (double)n * H2 * W2 * 64 * 4.0 + 64 * 147 * 4.0);
-        const hipError_t e = front(ctx->stream, d_src, d_off, d_hw, n, h, w, pitch, mean_std6, stem_w, scale, shift, pool);
-        prof_end(ctx);
-        if (e != hipSuccess) {
-            reid_set_error("libreid_hip_anysize_front.so anysize_front -> %s", hipGetErrorString(e));
-            return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-        }
-        return REID_OK;
-    }
-    ARG_CHECK(stem != nullptr);
-    const AnysizeApi* api;
-    REID_TRY(anysize_api(&api));
-    float* nhwc;
-    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)n * h * w * 3 * 4, (void**)&nhwc));
-    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * w * 15.0);
-    const hipError_t e = api->resize(ctx->stream, d_src, d_off, d_hw, n, h, w, pitch, mean_std6, nhwc);
-    prof_end(ctx);
-    REID_TRY(any_launched(e, "anysize_resize_norm"));
-    return any_stem_pool(ctx, nhwc, n, h, w, stem_w, scale, shift, stem, pool);
-}
-
 // the forward behind the pooled map b.pool [n][H2][W2][64] (b.stem: stage 0, or NULL when nothing wrote one)
-static int seres18_trunk_any(reid_ctx* ctx, const AnyBufs& b, int n, float* d_emb, float* d_logits) {
-    Se18Weights& wt = ctx->se18;
+template <class Ar>
+static int seres18_trunk_any(reid_ctx* ctx, const Ar& ar, const AnyBufs<typename Ar::T>& b, int n, float* d_emb, float* d_logits) {
+    typedef typename Ar::T T;
+    const Se18Weights& wt = ctx->se18;
     const bool keep = ctx->debug_keep != 0;
-    const int arith = ctx->hw_precision == 2 ? 2 : 0;   // the setting and nothing else picks the trunk's convolution launcher
-    const size_t per = b.per;
-    const size_t* elems = b.elems;
-    float *stem = b.stem, *pool = b.pool, *tbase = b.tbase, *gem = b.gem;
     float* stage[11];
-    stage[0] = stem;
-    stage[1] = pool;
-    const float* cur = pool;
+    stage[0] = (float*)b.stem;
+    stage[1] = (float*)b.pool;
+    const T* cur = b.pool;
     int H = b.H2, W = b.W2;
     for (int i = 0; i < 8; ++i) {
         const Se18Block& k = wt.blk[i];
-        float* free_[3];
+        T* free_[3];
         int nf = 0;
         for (int j = 0; j < 4 && nf < 3; ++j) {
-            float* t = tbase + ((size_t)(keep ? i * 4 : 0) + j) * n * per;
+            T* t = b.tbase + ((size_t)(keep ? i * 4 : 0) + j) * n * b.per;
             if (t != cur) free_[nf++] = t;
         }
-        float *c1 = free_[0], *y = free_[1], *sc = free_[2];
-        const int Ho = (H + 2 - 3) / k.stride + 1, Wo = (W + 2 - 3) / k.stride + 1, hw = Ho * Wo;
+        T *c1 = free_[0], *y = free_[1], *sc = free_[2];
+        const int Ho = (H + 2 - 3) / k.stride + 1, Wo = (W + 2 - 3) / k.stride + 1;
         if (k.ibn) {   // BatchNorm half + ReLU in conv1's epilogue, InstanceNorm half (statistics of the whole image) by one pass in place
-            REID_TRY(launch_any_conv(ctx, arith, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, wt.ep + (size_t)i * 1024,
-                              wt.ep + (size_t)i * 1024 + 512, nullptr, 1, k.c / 2, c1));
-            REID_TRY(launch_any_norm(ctx, c1, n, hw, k.c, k.c / 2, k.in_gamma, k.in_beta, nullptr, nullptr));
+            REID_TRY(ar.conv(ctx, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, wt.ep + (size_t)i * 1024, wt.ep + (size_t)i * 1024 + 512,
+                             nullptr, 1, k.c / 2, c1));
+            REID_TRY(ar.norm(ctx, c1, n, Ho * Wo, k.c, k.c / 2, k.in_gamma, k.in_beta));
         } else {
-            REID_TRY(launch_any_conv(ctx, arith, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, k.bn1_scale, k.bn1_shift, nullptr, 1, 0, c1));
+            REID_TRY(ar.conv(ctx, cur, n, H, W, k.cin, k.conv1_w, k.c, 3, k.stride, 1, k.bn1_scale, k.bn1_shift, nullptr, 1, 0, c1));
         }
         // a block without a downsample is the whole BasicBlock_IBN: residual + ReLU before the SE scale, the input added again after
-        REID_TRY(launch_any_conv(ctx, arith, c1, n, Ho, Wo, k.c, k.conv2_w, k.c, 3, 1, 1, k.bn2_scale, k.bn2_shift, k.ds ? nullptr : cur,
-                          k.ds ? 0 : 1, 0, y));
-        const float* shortcut = cur;
+        REID_TRY(ar.conv(ctx, c1, n, Ho, Wo, k.c, k.conv2_w, k.c, 3, 1, 1, k.bn2_scale, k.bn2_shift, k.ds ? nullptr : cur, k.ds ? 0 : 1, 0, y));
+        const T* shortcut = cur;
         if (k.ds) {
-            REID_TRY(launch_any_conv(ctx, arith, cur, n, H, W, k.cin, k.ds_w, k.c, 1, k.stride, 0, k.ds_scale, k.ds_shift, nullptr, 0, 0, sc));
+            REID_TRY(ar.conv(ctx, cur, n, H, W, k.cin, k.ds_w, k.c, 1, k.stride, 0, k.ds_scale, k.ds_shift, nullptr, 0, 0, sc));
             shortcut = sc;
         }
-        float* out = c1;   // conv1's output is dead after conv2
-        if (wt.arch == 1) {   // CARes18_IBN: TripletAttention + shortcut + ReLU (CARes18.py:150-157); any_ca 0: the 256 x 128 forward's kernels
-            if (ctx->any_ca) REID_TRY(launch_any_ca_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out));
-            else REID_TRY(launch_ta_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out));
-        } else if (wt.arch == 2) {   // EMARes18_IBN: EMA + shortcut + ReLU (EMA_Res18.py:79-86); any_ema 0: the 256 x 128 forward's kernel
-            if (ctx->any_ema) REID_TRY(launch_any_ema_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ema, out));
-            else REID_TRY(launch_ema_tail(ctx, y, shortcut, n, Ho, Wo, k.c, k.ema, out));
-        } else {
-            REID_TRY(launch_any_se_tail(ctx, y, shortcut, n, hw, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr));
-        }
-        stage[2 + i] = out;
-        cur = out;
-        H = Ho;
-        W = Wo;
-    }
-    REID_TRY(launch_any_gem(ctx, cur, n, H * W, 512, wt.gem_p, wt.neck_scale, wt.neck_shift, gem, d_emb));
-    {   // SERse18_IBN.forward(x, cam): + cam_factor * cam_bias[cam] on the BNNeck output, before the classifier (:269-271)
-        const int32_t* d_cam;
-        REID_TRY(ctx_take_side(ctx, n, wt.num_cams, "reid_embed (camera bias)", &d_cam));
-        if (d_cam) REID_TRY(launch_add_indexed_rows(ctx, d_emb, n, 1, 512, wt.cam_bias, d_cam, wt.cam_factor));
-    }
-    stage[10] = gem;
-    if (d_logits) {
-        if (!wt.cls_w) {
-            reid_set_error("logits requested but the weight blob has no classifier (cls.w)");
-            return REID_ERR_STATE;
-        }
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = d_emb; p.lda = 512;
-        p.B = wt.cls_w; p.ldb = 512;
-        p.M = n; p.N = wt.num_class; p.K = 512;
-        p.C = d_logits; p.ldc = wt.num_class;
-        REID_TRY(launch_gemm_f32(ctx, A_DENSE, E_BIAS, p, REID_K_CONV_GEMM, 2.0 * n * wt.num_class * 512,
-                                 ((double)n * 512 + (double)wt.num_class * 512 + (double)n * wt.num_class) * 4.0));
-    }
-    ctx->last_n = n;
-    ctx->last_f16 = false;
-    for (int s = 0; s < 11; ++s) {
-        ctx->stage_ptr[s] = stage[s];
-        ctx->stage_elems[s] = elems[s];
-    }
-    return REID_OK;
-}
-
-// ---- the same forward in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16 1): every kernel from libreid_hip_anysize_f16.so
-static int any_f16_launched(hipError_t e, const char* what) {
-    if (e != hipSuccess) {
-        reid_set_error("libreid_hip_anysize_f16.so %s -> %s", what, hipGetErrorString(e));
-        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-    }
-    return REID_OK;
-}
-
-int launch_any_conv_f16(reid_ctx* ctx, const _Float16* x, int n, int H, int W, int Cin, const _Float16* w16, int Cout, int R, int stride, int pad,
-                        const float* scale, const float* shift, const _Float16* residual, int relu, int relu_from, _Float16* out) {
-    const AnysizeF16Api* api;
-    REID_TRY(anysize_f16_api(&api));
-    const int Ho = (H + 2 * pad - R) / stride + 1, Wo = (W + 2 * pad - R) / stride + 1;
-    const double m = (double)n * Ho * Wo, ktrue = (double)R * R * Cin;
-    prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * Cout * ktrue, ((double)n * H * W * Cin + m * Cout * (residual ? 2.0 : 1.0) + (double)Cout * ktrue) * 2.0);
-    const hipError_t e = api->conv(ctx->stream, x, n, H, W, Cin, w16, Cout, R, stride, pad, scale, shift, residual, relu, relu_from, out,
-                                   &ctx->any_f16_form);
-    prof_end(ctx);
-    return any_f16_launched(e, "anysize_f16_conv");
-}
-
-int launch_any_stem_f16(reid_ctx* ctx, const float* x, int n, int h, int w, const _Float16* w16, const float* scale, const float* shift,
-                        _Float16* out) {
-    const AnysizeF16Api* api;
-    REID_TRY(anysize_f16_api(&api));
-    const double m = (double)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1);
-    prof_begin(ctx, REID_K_CONV_GEMM, 2.0 * m * 64 * 147.0, (double)n * h * w * 12.0 + m * 128.0 + 64 * 192 * 2.0);
-    const hipError_t e = api->stem(ctx->stream, x, n, h, w, w16, scale, shift, out);
-    prof_end(ctx);
-    return any_f16_launched(e, "anysize_f16_stem");
-}
-
-int launch_any_maxpool_f16(reid_ctx* ctx, const _Float16* x, int n, int h, int w, int c, _Float16* out) {
-    const AnysizeF16Api* api;
-    REID_TRY(anysize_f16_api(&api));
-    prof_begin(ctx, REID_K_ELEMENTWISE, 0, ((double)n * h * w * c + (double)n * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) * c) * 2.0);
-    const hipError_t e = api->maxpool(ctx->stream, x, n, h, w, c, out);
-    prof_end(ctx);
-    return any_f16_launched(e, "anysize_f16_maxpool");
-}
-
-int launch_any_norm_f16(reid_ctx* ctx, _Float16* x, int n, int hw, int c, int half, const float* in_gamma, const float* in_beta) {
-    const AnysizeF16Api* api;
-    REID_TRY(anysize_f16_api(&api));
-    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * half * 6.0);
-    const hipError_t e = api->norm(ctx->stream, x, n, hw, c, half, in_gamma, in_beta);
-    prof_end(ctx);
-    return any_f16_launched(e, "anysize_f16_norm");
-}
-
-int launch_any_se_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int hw, int c, int mid, const float* w1,
-                           const float* w2t, _Float16* out, float* gate_out) {
-    const AnysizeF16Api* api;
-    REID_TRY(anysize_f16_api(&api));
-    float* pooled;
-    REID_TRY(ctx_ws(ctx, "any.pooled", (size_t)n * c * 4, (void**)&pooled));
-    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 8.0);
-    const hipError_t e = api->se_tail(ctx->stream, y, sc, n, hw, c, mid, w1, w2t, pooled, out, gate_out);
-    prof_end(ctx);
-    return any_f16_launched(e, "anysize_f16_se_tail");
-}
-
-int launch_any_gem_f16(reid_ctx* ctx, const _Float16* x, int n, int hw, int c, const float* p, const float* scale, const float* shift,
-                       float* gem_out, float* emb) {
-    const AnysizeF16Api* api;
-    REID_TRY(anysize_f16_api(&api));
-    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * hw * c * 2.0);
-    const hipError_t e = api->gem(ctx->stream, x, n, hw, c, p, scale, shift, gem_out, emb);
-    prof_end(ctx);
-    return any_f16_launched(e, "anysize_f16_gem");
-}
-
-// x: fp32 NHWC [n][h][w][3] on the device.  The buffers are those of any_bufs in f16 (the same names as the fp16-storage forward at
-// 256 x 128, which sizes them in bytes too); the weights are the f16 image of the blob reid_seres18_load makes whatever the mode
-// (Se18Weights::h; the stem's [64][192] packed rows are in it), the fp32 folded-BN vectors, SE weights and neck are shared with the
-// fp32 forward.  The trunk is seres18_trunk_any's, launch for launch.
-static int seres18_forward_any_f16(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
-    typedef _Float16 f16;
-    Se18Weights& wt = ctx->se18;
-    ARG_CHECK(wt.arch == 0);
-    const bool keep = ctx->debug_keep != 0;
-    const int H1 = (h - 1) / 2 + 1, W1 = (w - 1) / 2 + 1, H2 = (H1 - 1) / 2 + 1, W2 = (W1 - 1) / 2 + 1;
-    ARG_CHECK((long long)n * H1 * W1 < (1ll << 31) - 256);
-    size_t elems[11];
-    elems[0] = (size_t)H1 * W1 * 64;
-    elems[1] = (size_t)H2 * W2 * 64;
-    size_t per = elems[1];
-    {
-        int H = H2, W = W2;
-        for (int i = 0; i < 8; ++i) {
-            const Se18Block& k = wt.blk[i];
-            H = (H + 2 - 3) / k.stride + 1;
-            W = (W + 2 - 3) / k.stride + 1;
-            elems[2 + i] = (size_t)H * W * k.c;
-            if (elems[2 + i] > per) per = elems[2 + i];
-        }
-    }
-    elems[10] = 512;
-    f16 *stem, *pool, *tbase;
-    float* gem;
-    REID_TRY(ctx_ws(ctx, "se18h.stem", (size_t)n * elems[0] * 2, (void**)&stem));
-    REID_TRY(ctx_ws(ctx, "se18h.pool", (size_t)n * per * 2, (void**)&pool));
-    REID_TRY(ctx_ws(ctx, "se18h.t", (size_t)n * per * 2 * (keep ? 4 * 8 : 4), (void**)&tbase));
-    REID_TRY(ctx_ws(ctx, "se18.gem", (size_t)n * 512 * 4, (void**)&gem));
-    REID_TRY(launch_any_stem_f16(ctx, x, n, h, w, wt.h(wt.stem_w), wt.stem_scale, wt.stem_shift, stem));
-    REID_TRY(launch_any_maxpool_f16(ctx, stem, n, H1, W1, 64, pool));
-    float* stage[11];
-    stage[0] = (float*)stem;
-    stage[1] = (float*)pool;
-    const f16* cur = pool;
-    int H = H2, W = W2;
-    for (int i = 0; i < 8; ++i) {
-        const Se18Block& k = wt.blk[i];
-        f16* free_[3];
-        int nf = 0;
-        for (int j = 0; j < 4 && nf < 3; ++j) {
-            f16* t = tbase + ((size_t)(keep ? i * 4 : 0) + j) * n * per;
-            if (t != cur) free_[nf++] = t;
-        }
-        f16 *c1 = free_[0], *y = free_[1], *sc = free_[2];
-        const int Ho = (H + 2 - 3) / k.stride + 1, Wo = (W + 2 - 3) / k.stride + 1, hw = Ho * Wo;
-        if (k.ibn) {   // BatchNorm half + ReLU in conv1's epilogue, InstanceNorm half (statistics of the whole image) by one pass in place
-            REID_TRY(launch_any_conv_f16(ctx, cur, n, H, W, k.cin, wt.h(k.conv1_w), k.c, 3, k.stride, 1, wt.ep + (size_t)i * 1024,
-                                         wt.ep + (size_t)i * 1024 + 512, nullptr, 1, k.c / 2, c1));
-            REID_TRY(launch_any_norm_f16(ctx, c1, n, hw, k.c, k.c / 2, k.in_gamma, k.in_beta));
-        } else {
-            REID_TRY(launch_any_conv_f16(ctx, cur, n, H, W, k.cin, wt.h(k.conv1_w), k.c, 3, k.stride, 1, k.bn1_scale, k.bn1_shift, nullptr, 1, 0,
-                                         c1));
-        }
-        REID_TRY(launch_any_conv_f16(ctx, c1, n, Ho, Wo, k.c, wt.h(k.conv2_w), k.c, 3, 1, 1, k.bn2_scale, k.bn2_shift, k.ds ? nullptr : cur,
-                                     k.ds ? 0 : 1, 0, y));
-        const f16* shortcut = cur;
-        if (k.ds) {
-            REID_TRY(launch_any_conv_f16(ctx, cur, n, H, W, k.cin, wt.h(k.ds_w), k.c, 1, k.stride, 0, k.ds_scale, k.ds_shift, nullptr, 0, 0, sc));
-            shortcut = sc;
-        }
-        f16* out = c1;   // conv1's output is dead after conv2
-        REID_TRY(launch_any_se_tail_f16(ctx, y, shortcut, n, hw, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr));
+        T* out = c1;   // conv1's output is dead after conv2
+        REID_TRY(ar.tail(ctx, k, y, shortcut, n, Ho, Wo, out));
         stage[2 + i] = (float*)out;
         cur = out;
         H = Ho;
         W = Wo;
     }
-    REID_TRY(launch_any_gem_f16(ctx, cur, n, H * W, 512, wt.gem_p, wt.neck_scale, wt.neck_shift, gem, d_emb));
-    {
-        const int32_t* d_cam;
-        REID_TRY(ctx_take_side(ctx, n, wt.num_cams, "reid_embed (camera bias)", &d_cam));
-        if (d_cam) REID_TRY(launch_add_indexed_rows(ctx, d_emb, n, 1, 512, wt.cam_bias, d_cam, wt.cam_factor));
-    }
-    stage[10] = gem;
-    if (d_logits) {
-        if (!wt.cls_w) {
-            reid_set_error("logits requested but the weight blob has no classifier (cls.w)");
-            return REID_ERR_STATE;
-        }
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = d_emb; p.lda = 512;
-        p.B = wt.cls_w; p.ldb = 512;
-        p.M = n; p.N = wt.num_class; p.K = 512;
-        p.C = d_logits; p.ldc = wt.num_class;
-        REID_TRY(launch_gemm_f32(ctx, A_DENSE, E_BIAS, p, REID_K_CONV_GEMM, 2.0 * n * wt.num_class * 512,
-                                 ((double)n * 512 + (double)wt.num_class * 512 + (double)n * wt.num_class) * 4.0));
-    }
+    REID_TRY(ar.gem(ctx, cur, n, H * W, 512, wt.gem_p, wt.neck_scale, wt.neck_shift, b.gem, d_emb));
+    REID_TRY(se18_head(ctx, n, d_emb, d_logits));
+    stage[10] = b.gem;
     ctx->last_n = n;
-    ctx->last_f16 = true;
+    ctx->last_f16 = sizeof(T) == 2;
     for (int s = 0; s < 11; ++s) {
         ctx->stage_ptr[s] = stage[s];
-        ctx->stage_elems[s] = elems[s];
+        ctx->stage_elems[s] = b.elems[s];
     }
     return REID_OK;
 }
 
+// the fp32 arithmetics: the setting hw_precision and nothing else picks the trunk's convolution launcher
+static int seres18_trunk_any(reid_ctx* ctx, const AnyBufs<float>& b, int n, float* d_emb, float* d_logits) {
+    return seres18_trunk_any(ctx, AnyF32{ctx->hw_precision == 2 ? 2 : 0}, b, n, d_emb, d_logits);
+}
+
 // x: fp32 NHWC [n][h][w][3] on the device
 static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
-    if (ctx->hw_f16) return seres18_forward_any_f16(ctx, x, n, h, w, d_emb, d_logits);
     const Se18Weights& wt = ctx->se18;
-    AnyBufs b;
-    REID_TRY(any_bufs(ctx, n, h, w, true, b));
+    if (ctx->hw_f16) {   // stem and max-pool from libreid_hip_anysize_f16.so too, then the walk of seres18_trunk_any
+        ARG_CHECK(wt.arch == 0);
+        AnyBufs<_Float16> b;
+        REID_TRY(any_bufs<AnyF16>(ctx, n, h, w, true, b));
+        REID_TRY(launch_any_stem_f16(ctx, x, n, h, w, wt.h(wt.stem_w), wt.stem_scale, wt.stem_shift, b.stem));
+        REID_TRY(launch_any_maxpool_f16(ctx, b.stem, n, b.H1, b.W1, 64, b.pool));
+        return seres18_trunk_any(ctx, AnyF16{}, b, n, d_emb, d_logits);
+    }
+    AnyBufs<float> b;
+    REID_TRY(any_bufs<AnyF32>(ctx, n, h, w, true, b));
     REID_TRY(any_stem_pool(ctx, x, n, h, w, wt.stem_w, wt.stem_scale, wt.stem_shift, b.stem, b.pool));
     return seres18_trunk_any(ctx, b, n, d_emb, d_logits);
 }
 
 int se_any_run_nchw(reid_ctx* ctx, const float* d_x, int m, int h, int w, int mirror, float* d_emb, float* d_log) {
-    const AnysizeApi* api;
-    REID_TRY(anysize_api(&api));
+    REID_TRY(anysize.open());
     float* nhwc;
     REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * h * w * 3 * 4, (void**)&nhwc));
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)m * h * w * 24.0);
-    const hipError_t e = api->to_nhwc(ctx->stream, d_x, m, h, w, mirror, nhwc);
+    const hipError_t e = anysize.to_nhwc(ctx->stream, d_x, m, h, w, mirror, nhwc);
     prof_end(ctx);
-    REID_TRY(any_launched(e, "anysize_nchw_to_nhwc3"));
+    REID_TRY(anysize.status(e, anysize.to_nhwc));
     return seres18_forward_any(ctx, nhwc, m, h, w, d_emb, d_log);
 }
 
@@ -2222,20 +2007,14 @@ static int se_any_run_windows(reid_ctx* ctx, const RaggedSrc& src, int i, int m,
     // reid_ctx_set_hw_f16 1: the fused kernel's pooled map is fp32, so such a pass takes resize + normalise and the f16 stem
     if (front && !ctx->hw_f16 && (ctx->any_front == 1 || (ctx->any_front == 2 && small)) && !ctx->debug_keep) {
         const Se18Weights& wt = ctx->se18;
-        AnyBufs b;
-        REID_TRY(any_bufs(ctx, m, h, w, false, b));
+        AnyBufs<float> b;
+        REID_TRY(any_bufs<AnyF32>(ctx, m, h, w, false, b));
         REID_TRY(launch_any_front(ctx, 1, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, h, w, src.pitch, mean_std6, wt.stem_w, wt.stem_scale,
                                   wt.stem_shift, nullptr, b.pool));
         return seres18_trunk_any(ctx, b, m, d_emb, d_log);
     }
-    const AnysizeApi* api;
-    REID_TRY(anysize_api(&api));
     float* nhwc;
-    REID_TRY(ctx_ws(ctx, "se18.in_nhwc", (size_t)m * h * w * 3 * 4, (void**)&nhwc));
-    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)m * h * w * 15.0);
-    const hipError_t e = api->resize(ctx->stream, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, h, w, src.pitch, mean_std6, nhwc);
-    prof_end(ctx);
-    REID_TRY(any_launched(e, "anysize_resize_norm"));
+    REID_TRY(any_resize_norm(ctx, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, h, w, src.pitch, mean_std6, &nhwc));
     return seres18_forward_any(ctx, nhwc, m, h, w, d_emb, d_log);
 }
 
@@ -2481,27 +2260,17 @@ static int pad_rows_to(reid_ctx* ctx, const char* name, const float* d_x, int m,
 // distmat_x3.h).  Entry points of their own: no setting moves an existing call, and nothing else calls them.  The squared norms come from
 // the launch the exact entry uses, on the same rows padded further with zeros (which add nothing to a sum of squares): only the dot
 // product differs between the two entries.  Workspace names of their own (distx3.*): interleaved exact calls keep their buffers.
-static int distmat_x3_api(decltype(&distmat_x3)* out) {
-    static std::mutex m;
-    static decltype(&distmat_x3) fn = nullptr;
-    std::lock_guard<std::mutex> lk(m);
-    if (!fn) {
-        void* f[1];
-        REID_TRY(open_beside_self("libreid_hip_distmat_x3.so", "the distance matrix in the fp32-class arithmetic (reid_distmat_x3) needs",
-                                  {"distmat_x3"}, f));
-        fn = (decltype(fn))f[0];
-    }
-    *out = fn;
-    return REID_OK;
-}
+static struct DistmatX3Lib : SideLib {
+    DistmatX3Lib() : SideLib("libreid_hip_distmat_x3.so", "the distance matrix in the fp32-class arithmetic (reid_distmat_x3) needs") {}
+    SIDE_FN(run, distmat_x3);
+} distmat_x3_lib;
 
 extern "C" int reid_distmat_x3_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, float* d_out) {
     ARG_CHECK(ctx && d_x && d_y && d_out && m >= 0 && n >= 0 && d >= 1);
     CTX_ENTER(ctx);
     ARG_CHECK(metric >= REID_METRIC_L2 && metric <= REID_METRIC_DOT);
     if (m == 0 || n == 0) return REID_OK;
-    decltype(&distmat_x3) fn;
-    REID_TRY(distmat_x3_api(&fn));
+    REID_TRY(distmat_x3_lib.open());
     const float *xp, *yp;
     int ldx, ldy;
     REID_TRY(pad_rows_to(ctx, "distx3.xpad", d_x, m, d, 32, &xp, &ldx));   // whole K steps, 16-byte rows, zero columns
@@ -2514,13 +2283,9 @@ extern "C" int reid_distmat_x3_dev(reid_ctx* ctx, const float* d_x, int m, const
         REID_TRY(launch_row_sqnorm(ctx, yp, n, ldy, ldy, yy));
     }
     prof_begin(ctx, REID_K_DIST_GEMM, 2.0 * m * n * d, 4.0 * ((double)m * d + (double)n * d + (double)m * n));
-    const hipError_t e = fn(ctx->stream, xp, m, yp, n, ldx, xx, yy, metric, d_out, ctx->fault, nullptr);
+    const hipError_t e = distmat_x3_lib.run(ctx->stream, xp, m, yp, n, ldx, xx, yy, metric, d_out, ctx->fault, nullptr);
     prof_end(ctx);
-    if (e != hipSuccess) {
-        reid_set_error("libreid_hip_distmat_x3.so distmat_x3 -> %s", hipGetErrorString(e));
-        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-    }
-    return REID_OK;
+    return distmat_x3_lib.status(e, distmat_x3_lib.run);
 }
 
 extern "C" int reid_distmat_x3(reid_ctx* ctx, const float* x, int m, const float* y, int n, int d, int metric, float* out) {
@@ -2545,32 +2310,17 @@ extern "C" int reid_distmat_x3(reid_ctx* ctx, const float* x, int m, const float
 // arithmetic (libreid_hip_select_x3.so, select_x3.h: candidate lists from the epilogue of the x3 kernel, exact-fp32 refinement, a proof
 // per row, the exact-row kernel where the proof fails).  Entry points of their own: no setting moves an existing call, nothing else calls
 // them.  Norms and padding as in reid_distmat_x3*; workspace names of their own (selx3.*).
-struct SelectX3Api {
-    decltype(&select_x3_ws_bytes) bytes = nullptr;
-    decltype(&select_x3) run = nullptr;
-};
-static int select_x3_api(SelectX3Api** out) {
-    static std::mutex m;
-    static SelectX3Api api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.run) {
-        void* f[2];
-        REID_TRY(open_beside_self("libreid_hip_select_x3.so",
-                                  "arg-min and k-NN with fp32-class candidates (reid_argmin_rows_x3, reid_knn_x3) need", {"select_x3_ws_bytes", "select_x3"},
-                                  f));
-        api.bytes = (decltype(api.bytes))f[0];
-        api.run = (decltype(api.run))f[1];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct SelectX3Lib : SideLib {
+    SelectX3Lib() : SideLib("libreid_hip_select_x3.so", "arg-min and k-NN with fp32-class candidates (reid_argmin_rows_x3, reid_knn_x3) need") {}
+    SIDE_FN(bytes, select_x3_ws_bytes);
+    SIDE_FN(run, select_x3);
+} select_x3_lib;
 
 // The launcher of both entries (and of reid_debug_select_x3).  d_D [m][k] may be NULL.  stats (host, may be NULL): waits for the stream and
 // returns {rows proven, rows recomputed, tile form, candidates per row}.
 int select_x3_launch(reid_ctx* ctx, const float* d_x, int m, const float* d_y, int n, int d, int metric, int k, float* d_D, int32_t* d_I,
                      int force_every, int32_t* stats) {
-    SelectX3Api* api;
-    REID_TRY(select_x3_api(&api));
+    REID_TRY(select_x3_lib.open());
     const float *xp, *yp;
     int ldx, ldy;
     REID_TRY(pad_rows_to(ctx, "selx3.xpad", d_x, m, d, 32, &xp, &ldx));   // whole K steps, 16-byte rows, zero columns
@@ -2581,18 +2331,16 @@ int select_x3_launch(reid_ctx* ctx, const float* d_x, int m, const float* d_y, i
     REID_TRY(ctx_ws(ctx, "selx3.xx", (size_t)m * 4, (void**)&xx));
     REID_TRY(ctx_ws(ctx, "selx3.yy", (size_t)n * 4, (void**)&yy));
     REID_TRY(ctx_ws(ctx, "selx3.flags", (size_t)m * 4, (void**)&flags));
-    const size_t bytes = api->bytes(m, n);
+    const size_t bytes = select_x3_lib.bytes(m, n);
     REID_TRY(ctx_ws(ctx, "selx3.ws", bytes, &ws));
     REID_TRY(launch_row_sqnorm(ctx, xp, m, ldx, ldx, xx));   // the launch of the exact entries: zero columns add nothing to a sum of squares
     REID_TRY(launch_row_sqnorm(ctx, yp, n, ldy, ldy, yy));
     int form = 0;
     prof_begin(ctx, REID_K_SELECT, 2.0 * m * n * d, 4.0 * ((double)m * d + (double)n * d));
-    const hipError_t e = api->run(ctx->stream, xp, m, yp, n, ldx, xx, yy, metric, k, d_D, d_I, ws, bytes, ctx->fault, force_every, flags, &form);
+    const hipError_t e =
+        select_x3_lib.run(ctx->stream, xp, m, yp, n, ldx, xx, yy, metric, k, d_D, d_I, ws, bytes, ctx->fault, force_every, flags, &form);
     prof_end(ctx);
-    if (e != hipSuccess) {
-        reid_set_error("libreid_hip_select_x3.so select_x3 -> %s", hipGetErrorString(e));
-        return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-    }
+    REID_TRY(select_x3_lib.status(e, select_x3_lib.run));
     if (stats) {
         std::vector<int> h((size_t)m);
         HIP_TRY(hipMemcpyAsync(h.data(), flags, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));

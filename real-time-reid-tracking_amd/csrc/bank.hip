@@ -14,7 +14,6 @@
 #include "reid_internal.h"
 #include "bank96.h"
 #include <string.h>
-#include <mutex>
 #include <utility>
 
 struct reid_bank {
@@ -418,28 +417,19 @@ extern "C" int reid_bank_clear(reid_ctx* ctx, reid_bank* b, const int32_t* slots
 
 // libreid_hip_bank96.so (bank96.h), opened from the directory this library lies in on the first reid_frame_submit_swin (or by the
 // kernel's harness): a process that never tracks with a Swin never opens it.  Missing library or symbol: REID_ERR_STATE naming the file.
-static int bank96_api(decltype(&bank96_cost)* out) {
-    static std::mutex mu;
-    static decltype(&bank96_cost) cost = nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    if (!cost) {
-        void* f;
-        REID_TRY(open_beside_self("libreid_hip_bank96.so", "the frame pipeline of a Swin tracker needs", {"bank96_cost"}, &f));
-        cost = (decltype(cost))f;
-    }
-    *out = cost;
-    return REID_OK;
-}
+static struct Bank96Lib : SideLib {
+    Bank96Lib() : SideLib("libreid_hip_bank96.so", "the frame pipeline of a Swin tracker needs") {}
+    SIDE_FN(cost, bank96_cost);
+} bank96;
 
 // frame96: the caller is the frame pipeline's cost stage, which takes bank_cost96_kernel for a 96-wide bank; reid_bank_cost / _dev
 // keep bank_cost_kernel there, as before
 static int bank_cost_launch(reid_ctx* ctx, reid_bank* b, const int32_t* d_slots, int t, const float* d_dets, int m, int metric,
                             float max_dist, float* d_out, bool frame96 = false) {
     if (frame96 && b->d == 96 && ctx->bank_fast) {
-        decltype(&bank96_cost) cost96;
-        REID_TRY(bank96_api(&cost96));
+        REID_TRY(bank96.open());
         prof_begin(ctx, REID_K_SELECT, 2.0 * t * m * b->budget * b->d, 4.0 * ((double)t * b->budget * b->d + (double)m * b->d));
-        const hipError_t e = cost96(ctx->stream, b->feat, b->sq, b->count, b->budget, d_slots, t, d_dets, m, metric, max_dist, d_out);
+        const hipError_t e = bank96.cost(ctx->stream, b->feat, b->sq, b->count, b->budget, d_slots, t, d_dets, m, metric, max_dist, d_out);
         prof_end(ctx);
         HIP_TRY(e);
         return REID_OK;
@@ -609,8 +599,7 @@ extern "C" int reid_frame_submit_swin(reid_ctx* ctx, int slot, const uint8_t* pa
     CTX_ENTER(ctx);
     int d = 0;
     REID_TRY(swin_ragged_ready(ctx, out_h, out_w, &mean_std6, &d));
-    decltype(&bank96_cost) cost96;
-    REID_TRY(bank96_api(&cost96));
+    REID_TRY(bank96.open());
     return frame_submit_impl(ctx, slot, offsets, hw, m, d, [&](const char* tag, const int64_t* off, const int32_t* hw_, float** d_emb) -> int {
         return swin_ragged_enqueue(ctx, tag, packed, off, hw_, m, out_h, out_w, mean_std6, d_emb, ctx->side_copy != 0 && ctx->stream != nullptr);
     });

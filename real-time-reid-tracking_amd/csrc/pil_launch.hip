@@ -2,37 +2,19 @@
 // kernels (pil_resize.h).  No kernel lives here: the product library's kernel list stays what it was.
 #include "pil_launch.h"
 #include <map>
-#include <mutex>
 #include <cmath>
 
 namespace {
-struct PilApi {
-    decltype(&pil_resize_max_side) max_side = nullptr;
-    decltype(&pil_resize_max_out) max_out = nullptr;
-    decltype(&pil_resize_coeffs) coeffs = nullptr;
-    decltype(&pil_resize_norm_table) norm_table = nullptr;
-    decltype(&pil_resize_launch) launch = nullptr;
-};
-
 // libreid_hip_pil_resize.so, opened beside this library on the first *_images_u8 call (or reid_debug_pil_resize): a process that never
 // hands over uint8 images for the evaluation chain never opens it.  Missing library or symbol: REID_ERR_STATE naming the file.
-int pil_api(const PilApi** out) {
-    static std::mutex m;
-    static PilApi api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.launch) {
-        void* f[5];
-        REID_TRY(open_beside_self("libreid_hip_pil_resize.so", "the *_images_u8 entry points need",
-                                  {"pil_resize_max_side", "pil_resize_max_out", "pil_resize_coeffs", "pil_resize_norm_table", "pil_resize_launch"}, f));
-        api.max_side = (decltype(api.max_side))f[0];
-        api.max_out = (decltype(api.max_out))f[1];
-        api.coeffs = (decltype(api.coeffs))f[2];
-        api.norm_table = (decltype(api.norm_table))f[3];
-        api.launch = (decltype(api.launch))f[4];
-    }
-    *out = &api;
-    return REID_OK;
-}
+struct PilLib : SideLib {
+    PilLib() : SideLib("libreid_hip_pil_resize.so", "the *_images_u8 entry points need") {}
+    SIDE_FN(max_side, pil_resize_max_side);
+    SIDE_FN(max_out, pil_resize_max_out);
+    SIDE_FN(coeffs, pil_resize_coeffs);
+    SIDE_FN(norm_table, pil_resize_norm_table);
+    SIDE_FN(launch, pil_resize_launch);
+} pil;
 
 const float kImagenet[6] = {0.485f, 0.456f, 0.406f, 0.229f, 0.224f, 0.225f};
 }  // namespace
@@ -49,9 +31,8 @@ int pil_mean_std(const float** mean_std6) {
 }
 
 int PilPlan::build(const RaggedSrc& src, int oh, int ow, const float* mean_std6, int pass_) {
-    const PilApi* api;
-    REID_TRY(pil_api(&api));
-    const int lim = api->max_side(), lim_out = api->max_out();
+    REID_TRY(pil.open());
+    const int lim = pil.max_side(), lim_out = pil.max_out();
     if (oh < 1 || ow < 1 || oh > lim_out || ow > lim_out) {
         reid_set_error("PIL resize: output size %d x %d, each side must be in [1, %d]", oh, ow, lim_out);
         return REID_ERR_ARG;
@@ -69,7 +50,7 @@ int PilPlan::build(const RaggedSrc& src, int oh, int ow, const float* mean_std6,
     out_w = ow;
     n = src.n;
     pass = pass_;
-    api->norm_table(mean_std6, table);
+    pil.norm_table(mean_std6, table);
     tables.clear();
     images.resize(n);
     mid_bytes = 0;
@@ -78,10 +59,10 @@ int PilPlan::build(const RaggedSrc& src, int oh, int ow, const float* mean_std6,
         auto it = seen.find({in, out});
         if (it == seen.end()) {
             int ks = 0;
-            if (api->coeffs(in, out, nullptr, nullptr, &ks) != 0) return REID_ERR_ARG;
+            if (pil.coeffs(in, out, nullptr, nullptr, &ks) != 0) return REID_ERR_ARG;
             const size_t at = tables.size();
             tables.resize(at + (size_t)out * (2 + ks));
-            if (api->coeffs(in, out, tables.data() + at + 2 * (size_t)out, tables.data() + at, &ks) != 0) {
+            if (pil.coeffs(in, out, tables.data() + at + 2 * (size_t)out, tables.data() + at, &ks) != 0) {
                 reid_set_error("PIL resize: no coefficients for %d -> %d", in, out);
                 return REID_ERR_ARG;
             }
@@ -123,8 +104,7 @@ int PilPlan::up(hipStream_t s) const {
 }
 
 int PilPlan::launch(reid_ctx* ctx, const RaggedSrc& src, int i, int m, uint8_t* d_u8, float* d_out) const {
-    const PilApi* api;
-    REID_TRY(pil_api(&api));
+    REID_TRY(pil.open());
     if (i < 0 || m < 1 || m > pass || i % pass || i + m > n || src.n != n || !src.d_src || !d_tables || !d_mid || !d_out) {
         reid_set_error("PIL resize: bad launch (images [%d, %d) of %d, passes of %d)", i, i + m, n, pass);
         return REID_ERR_ARG;
@@ -137,7 +117,7 @@ int PilPlan::launch(reid_ctx* ctx, const RaggedSrc& src, int i, int m, uint8_t* 
     }
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, bytes);
     const hipError_t e =
-        api->launch(ctx->stream, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, max_h, out_h, out_w, d_tables, d_images + i, d_table, d_mid, d_u8, d_out);
+        pil.launch(ctx->stream, src.d_src, src.d_off + i, src.d_hw + 2 * i, m, max_h, out_h, out_w, d_tables, d_images + i, d_table, d_mid, d_u8, d_out);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;

@@ -12,7 +12,6 @@
 #include "reid_internal.h"
 #include "pil_launch.h"
 #include "eval_links.h"
-#include <mutex>
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -207,51 +206,28 @@ int launch_flip_w_nchw(reid_ctx* ctx, const float* x, long long rows, int w, flo
 
 // ---- libreid_hip_eval_links.so (eval_links.h), opened on the first call that needs it: the shifted mirrored view of the
 // reid_descriptor_*_shift entries and reid_distmat_add_l2*.
-struct EvalLinksApi {
-    decltype(&eval_links_shift_mirror) shift_mirror = nullptr;
-    decltype(&eval_links_dist_add_l2) dist_add_l2 = nullptr;
-};
-static int eval_links_api(const EvalLinksApi** out) {
-    static std::mutex m;
-    static EvalLinksApi api;
-    static bool ready = false;
-    std::lock_guard<std::mutex> lk(m);
-    if (!ready) {
-        void* f[2];
-        REID_TRY(open_beside_self("libreid_hip_eval_links.so",
-                                  "the shifted mirrored view (reid_descriptor_*_shift) and reid_distmat_add_l2 need",
-                                  {"eval_links_shift_mirror", "eval_links_dist_add_l2"}, f));
-        api.shift_mirror = (decltype(api.shift_mirror))f[0];
-        api.dist_add_l2 = (decltype(api.dist_add_l2))f[1];
-        ready = true;
-    }
-    *out = &api;
-    return REID_OK;
-}
-static int eval_links_status(const char* what, hipError_t e) {
-    if (e == hipSuccess) return REID_OK;
-    reid_set_error("libreid_hip_eval_links.so %s -> %s", what, hipGetErrorString(e));
-    return e == hipErrorInvalidValue ? REID_ERR_ARG : REID_ERR_HIP;
-}
+static struct EvalLinksLib : SideLib {
+    EvalLinksLib() : SideLib("libreid_hip_eval_links.so", "the shifted mirrored view (reid_descriptor_*_shift) and reid_distmat_add_l2 need") {}
+    SIDE_FN(shift_mirror, eval_links_shift_mirror);
+    SIDE_FN(dist_add_l2, eval_links_dist_add_l2);
+} eval_links;
 
 // shift_mirror_nchw_kernel: y = crop(pad(mirror(x))) of x [m][3][h][w], (top, left) per image from d_shift_tl (device int32 [m][2])
 int launch_shift_mirror(reid_ctx* ctx, const float* x, int m, int h, int w, const int32_t* d_shift_tl, int pad, const float* fill3, float* y) {
-    const EvalLinksApi* ev;
-    REID_TRY(eval_links_api(&ev));
+    REID_TRY(eval_links.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, 8.0 * m * 3 * h * w);
-    const hipError_t e = ev->shift_mirror(ctx->stream, x, m, h, w, d_shift_tl, pad, fill3, y);
+    const hipError_t e = eval_links.shift_mirror(ctx->stream, x, m, h, w, d_shift_tl, pad, fill3, y);
     prof_end(ctx);
-    return eval_links_status("eval_links_shift_mirror", e);
+    return eval_links.status(e, eval_links.shift_mirror);
 }
 
 // dist_add_l2_kernel: d_inout [n][n] += euclidean_dist(a, a), a [n][d]
 int launch_dist_add_l2(reid_ctx* ctx, const float* a, int n, int d, float* d_inout) {
-    const EvalLinksApi* ev;
-    REID_TRY(eval_links_api(&ev));
+    REID_TRY(eval_links.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 2.0 * n * n * d, 8.0 * n * n);
-    const hipError_t e = ev->dist_add_l2(ctx->stream, a, n, d, d_inout);
+    const hipError_t e = eval_links.dist_add_l2(ctx->stream, a, n, d, d_inout);
     prof_end(ctx);
-    return eval_links_status("eval_links_dist_add_l2", e);
+    return eval_links.status(e, eval_links.dist_add_l2);
 }
 
 // The second view of the reid_descriptor_*_shift entries (strong_inference, reid/data_transforms.py:130-191): the mirror shifted by
@@ -395,8 +371,7 @@ static int shift_entry_ready(reid_ctx* ctx, const char* who, int n, int h, int w
     }
     REID_TRY(shift_check(who, shift_tl, n, pad));
     REID_TRY(se_any_ready(ctx, h, w, who));
-    const EvalLinksApi* ev;
-    return eval_links_api(&ev);
+    return eval_links.open();
 }
 
 extern "C" int reid_descriptor_f32_nchw_shift_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, const int32_t* shift_tl, int pad,
@@ -455,10 +430,7 @@ static int descriptor_images_u8(reid_ctx* ctx, const char* who, const uint8_t* p
     REID_TRY(src.check());
     if (shift_tl) REID_TRY(shift_check(who, shift_tl, n, pad));
     REID_TRY(se_any_ready(ctx, out_h, out_w, who));
-    if (shift_tl) {
-        const EvalLinksApi* ev;
-        REID_TRY(eval_links_api(&ev));
-    }
+    if (shift_tl) REID_TRY(eval_links.open());
     CTX_ENTER(ctx);
     if (n == 0) return REID_OK;
     int de = 0, nc = 0;
@@ -533,8 +505,7 @@ extern "C" int reid_distmat_add_l2_dev(reid_ctx* ctx, const float* d_a, int n, i
     }
     if (n == 0) return REID_OK;
     ARG_CHECK(d_a && d_inout && ((uintptr_t)d_inout & 15) == 0);
-    const EvalLinksApi* ev;
-    REID_TRY(eval_links_api(&ev));
+    REID_TRY(eval_links.open());
     CTX_ENTER(ctx);
     return launch_dist_add_l2(ctx, d_a, n, d, d_inout);
 }
@@ -547,8 +518,7 @@ extern "C" int reid_distmat_add_l2(reid_ctx* ctx, const float* a, int n, int d, 
     }
     if (n == 0) return REID_OK;
     ARG_CHECK(a && inout);
-    const EvalLinksApi* ev;
-    REID_TRY(eval_links_api(&ev));
+    REID_TRY(eval_links.open());
     CTX_ENTER(ctx);
     float *da, *dio;
     REID_TRY(ctx_ws(ctx, "addl2.a", (size_t)n * d * 4, (void**)&da));

@@ -7,6 +7,7 @@
 #include <initializer_list>
 #include <string>
 #include <map>
+#include <mutex>
 #include <tuple>
 #include <vector>
 #include "../../include/reid_hip.h"
@@ -784,9 +785,41 @@ int swin_ragged_enqueue(reid_ctx* ctx, const char* tag, const uint8_t* packed, c
 int bank_frame_cost_launch(reid_ctx* ctx, reid_bank* b, const int32_t* d_slots, int t, const float* d_dets, int m, int metric, float max_dist,
                            float* d_out);
 int bank_geometry(const reid_bank* b, int* max_tracks, int* budget, int* d);
-// The library `file` in the directory this library lies in: opened (RTLD_NOW | RTLD_LOCAL), fns[k] = its symbol names[k].  A missing file
-// ("<what> <path> beside libreid_hip.so: <dlerror>") or symbol ("<path> lacks a / b", the handle closed again) is REID_ERR_STATE.
-int open_beside_self(const char* file, const char* what, std::initializer_list<const char*> names, void** fns);
+// ---- The loader of the libraries that lie beside this one and are opened on first use (api.hip).  A library is described once, as a
+// struct derived from SideLib: its file, its "<what> needs" text, and one SIDE_FN member per function it exports, in the order a missing
+// symbol is reported in.  SIDE_FN takes the pointer type from the side header's declaration (decltype: unevaluated, so no reference to the
+// side library reaches this one's symbol table) and the symbol name from the same token; the member is then called like the function.
+//   open(): under the library's mutex, once: dlopen (RTLD_NOW | RTLD_LOCAL) from the directory this library lies in, then every symbol.
+//     A missing file ("<what> <path> beside libreid_hip.so: <dlerror>") or symbol ("<path> lacks a / b", the handle closed again) is
+//     REID_ERR_STATE and leaves the library unloaded: the next call tries again and reports again.
+//   status(e, fn): the hipError_t of a launch function of the library as a status: hipSuccess REID_OK; otherwise
+//     "<file> <fn> -> <hip error>", hipErrorInvalidValue REID_ERR_ARG, anything else REID_ERR_HIP.
+struct SideSym {
+    const char* name;
+    void* p = nullptr;
+};
+struct SideLib {
+    SideLib(const char* file, const char* what) : file(file), what(what) {}
+    SideLib(const SideLib&) = delete;
+    int open();
+    int status(hipError_t e, const SideSym& fn) const;
+    void add(SideSym* s) { syms.push_back(s); }
+    const char* const file;
+    const char* const what;
+
+private:
+    std::mutex m;
+    std::vector<SideSym*> syms;
+    bool loaded = false;
+};
+template <class F>
+struct SideFn;
+template <class R, class... A>
+struct SideFn<R (*)(A...)> : SideSym {
+    SideFn(SideLib* lib, const char* name) : SideSym{name} { lib->add(this); }
+    R operator()(A... a) const { return ((R(*)(A...))p)(a...); }
+};
+#define SIDE_FN(member, fn) SideFn<decltype(&fn)> member{this, #fn}
 // ---- ResNet18-IBN-SE at input sizes other than 256 x 128 (api.hip; kernels: anysize.h).  The reid_*_hw entries hand 256 x 128 to the
 // existing entries unless the debug switch anysize_force is set (se_any_routes).  se_any_ready: everything such a call would refuse, with
 // nothing queued - a side outside 32 .. 512 (REID_ERR_ARG), weights not loaded (REID_ERR_STATE), an architecture other than seres18_ibn

@@ -1215,65 +1215,30 @@ int launch_swin_tail(reid_ctx* ctx, const float* x, int n, int ntok, const float
 
 // libreid_hip_swin_v2.so, opened from the directory this library lies in when the first v2 checkpoint is loaded (or a v2 harness runs):
 // a process that never loads v2 weights never opens it.  Missing library or symbol: REID_ERR_STATE naming the file - no other path runs v2.
-struct SwinV2Api {
-    decltype(&swin_v2_window_attn_cos) attn = nullptr;
-    decltype(&swin_v2_post_norm) post_norm = nullptr;
-};
-static int swin_v2_api(const SwinV2Api** out) {
-    static std::mutex m;
-    static SwinV2Api api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.attn) {
-        void* f[2];
-        REID_TRY(open_beside_self("libreid_hip_swin_v2.so", "Swin v2 needs", {"swin_v2_window_attn_cos", "swin_v2_post_norm"}, f));
-        api.post_norm = (decltype(api.post_norm))f[1];
-        api.attn = (decltype(api.attn))f[0];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct SwinV2Lib : SideLib {
+    SwinV2Lib() : SideLib("libreid_hip_swin_v2.so", "Swin v2 needs") {}
+    SIDE_FN(attn, swin_v2_window_attn_cos);
+    SIDE_FN(post_norm, swin_v2_post_norm);
+} swin_v2;
 
 // libreid_hip_swin_crops.so (swin_crops.h), opened the same way on the first crops call (reid_swin_embed_ragged_u8 / _frame_u8, or their
 // harness): a process that only embeds float images never opens it.  Missing library or symbol: REID_ERR_STATE naming the file - there
 // is no other path from uint8 crops to the Swin stem.
-static int swin_crops_api(decltype(&swin_crops_front)* out) {
-    static std::mutex m;
-    static decltype(&swin_crops_front) front = nullptr;
-    std::lock_guard<std::mutex> lk(m);
-    if (!front) {
-        void* f;
-        REID_TRY(open_beside_self("libreid_hip_swin_crops.so", "Swin from uint8 crops needs", {"swin_crops_front"}, &f));
-        front = (decltype(front))f;
-    }
-    *out = front;
-    return REID_OK;
-}
+static struct SwinCropsLib : SideLib {
+    SwinCropsLib() : SideLib("libreid_hip_swin_crops.so", "Swin from uint8 crops needs") {}
+    SIDE_FN(front, swin_crops_front);
+} swin_crops;
 
 // libreid_hip_swin_eval.so (swin_eval.h), opened the same way on the first descriptor call (reid_swin_descriptor_*, or a harness of its
 // kernels): a process that only embeds never opens it.  Missing library or symbol: REID_ERR_STATE naming the file - there is no other path
 // to a Swin descriptor.
-struct SwinEvalApi {
-    decltype(&swin_eval_conv1_mirror) conv1_mirror = nullptr;
-    decltype(&swin_eval_crop_front_mirror) crop_front_mirror = nullptr;
-    decltype(&swin_eval_descriptor) descriptor = nullptr;
-    decltype(&swin_eval_max_classes) max_classes = nullptr;
-};
-static int swin_eval_api(const SwinEvalApi** out) {
-    static std::mutex m;
-    static SwinEvalApi api;
-    std::lock_guard<std::mutex> lk(m);
-    if (!api.descriptor) {
-        void* f[4];
-        REID_TRY(open_beside_self("libreid_hip_swin_eval.so", "Swin descriptors need",
-                                  {"swin_eval_conv1_mirror", "swin_eval_crop_front_mirror", "swin_eval_max_classes", "swin_eval_descriptor"}, f));
-        api.conv1_mirror = (decltype(api.conv1_mirror))f[0];
-        api.crop_front_mirror = (decltype(api.crop_front_mirror))f[1];
-        api.max_classes = (decltype(api.max_classes))f[2];
-        api.descriptor = (decltype(api.descriptor))f[3];
-    }
-    *out = &api;
-    return REID_OK;
-}
+static struct SwinEvalLib : SideLib {
+    SwinEvalLib() : SideLib("libreid_hip_swin_eval.so", "Swin descriptors need") {}
+    SIDE_FN(conv1_mirror, swin_eval_conv1_mirror);
+    SIDE_FN(crop_front_mirror, swin_eval_crop_front_mirror);
+    SIDE_FN(max_classes, swin_eval_max_classes);
+    SIDE_FN(descriptor, swin_eval_descriptor);
+} swin_eval;
 
 // ------------------------------------------------------------------------------------------------ weights
 struct SwinBlockW {
@@ -1390,8 +1355,7 @@ extern "C" int reid_swin_load(reid_ctx* ctx, const float* blob, size_t n_floats,
             }
             w.version = (int)v;
             if (w.version == 2) {   // the v2 kernels' library: absent -> refuse the checkpoint here, not in the middle of a forward
-                const SwinV2Api* v2;
-                const int rc = swin_v2_api(&v2);
+                const int rc = swin_v2.open();
                 if (rc != REID_OK) {
                     (void)hipFree(w.blob);
                     return rc;
@@ -1616,10 +1580,9 @@ int launch_window_attn_cos(reid_ctx* ctx, int mode, const void* qkv, int ldq, in
         reid_set_error("launch_window_attn_cos: bad arguments (mode %d, %d x %d tokens, %d heads, ldq %d)", mode, H, W, heads, ldq);
         return REID_ERR_ARG;
     }
-    const SwinV2Api* v2;
-    REID_TRY(swin_v2_api(&v2));
+    REID_TRY(swin_v2.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n_img * H * W * heads * 32 * (mode == 1 ? 8 : 16));
-    const hipError_t e = v2->attn(ctx->stream, mode, qkv, ldq, n_img, H, W, heads, shifted, bias_t, scale, out, ctx->fault);
+    const hipError_t e = swin_v2.attn(ctx->stream, mode, qkv, ldq, n_img, H, W, heads, shifted, bias_t, scale, out, ctx->fault);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;
@@ -1631,10 +1594,9 @@ int launch_post_norm(reid_ctx* ctx, int side_mode, const float* x, const float* 
         reid_set_error("launch_post_norm: bad arguments (side %d, %lld rows of %d)", side_mode, T, C);
         return REID_ERR_ARG;
     }
-    const SwinV2Api* v2;
-    REID_TRY(swin_v2_api(&v2));
+    REID_TRY(swin_v2.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)T * C * (12 + 2 * side_mode));
-    const hipError_t e = v2->post_norm(ctx->stream, side_mode, x, y, T, C, g, b, out, side, ctx->fault);
+    const hipError_t e = swin_v2.post_norm(ctx->stream, side_mode, x, y, T, C, g, b, out, side, ctx->fault);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;
@@ -1732,10 +1694,9 @@ int launch_swin_crop_front(reid_ctx* ctx, const uint8_t* d_src, const long long*
         reid_set_error("launch_swin_crop_front: bad arguments (%d windows to %d x %d, pitch %d)", n, h, wd, pitch);
         return REID_ERR_ARG;
     }
-    decltype(&swin_crops_front) front;
-    REID_TRY(swin_crops_api(&front));
+    REID_TRY(swin_crops.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * wd * 12);
-    const hipError_t e = front(ctx->stream, d_src, d_off, d_hw, n, h, wd, pitch, mean_std6, c1_w, c1_b, c1);
+    const hipError_t e = swin_crops.front(ctx->stream, d_src, d_off, d_hw, n, h, wd, pitch, mean_std6, c1_w, c1_b, c1);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;
@@ -1749,10 +1710,9 @@ int launch_sfe_conv1_mirror(reid_ctx* ctx, const float* x, int n, int h, int wd,
         reid_set_error("launch_sfe_conv1_mirror: bad arguments (%d images of %d x %d)", n, h, wd);
         return REID_ERR_ARG;
     }
-    const SwinEvalApi* ev;
-    REID_TRY(swin_eval_api(&ev));
+    REID_TRY(swin_eval.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * wd * (12 + 12));
-    const hipError_t e = ev->conv1_mirror(ctx->stream, x, n, h, wd, c1_w, c1_b, c1);
+    const hipError_t e = swin_eval.conv1_mirror(ctx->stream, x, n, h, wd, c1_w, c1_b, c1);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;
@@ -1764,10 +1724,9 @@ int launch_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* d_src, const lon
         reid_set_error("launch_swin_crop_front_mirror: bad arguments (%d windows to %d x %d, pitch %d)", n, h, wd, pitch);
         return REID_ERR_ARG;
     }
-    const SwinEvalApi* ev;
-    REID_TRY(swin_eval_api(&ev));
+    REID_TRY(swin_eval.open());
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * h * wd * 12);
-    const hipError_t e = ev->crop_front_mirror(ctx->stream, d_src, d_off, d_hw, n, h, wd, pitch, mean_std6, c1_w, c1_b, c1);
+    const hipError_t e = swin_eval.crop_front_mirror(ctx->stream, d_src, d_off, d_hw, n, h, wd, pitch, mean_std6, c1_w, c1_b, c1);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;
@@ -1775,19 +1734,18 @@ int launch_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* d_src, const lon
 
 // e1 / e2 (or nullptr) [n][96], cls_w [num_class][96] -> out rows of num_class + 96 floats, ld floats apart; all on the device
 int launch_swin_descriptor(reid_ctx* ctx, const float* e1, const float* e2, const float* cls_w, int n, int num_class, long long ld, float* out) {
-    const SwinEvalApi* ev;
-    REID_TRY(swin_eval_api(&ev));
+    REID_TRY(swin_eval.open());
     if (!e1 || !cls_w || !out || n < 1 || num_class < 1 || ld < (long long)num_class + 96 || (((uintptr_t)e1 | (uintptr_t)e2 | (uintptr_t)cls_w) & 15)) {
         reid_set_error("launch_swin_descriptor: bad arguments (%d rows, %d classes, row pitch %lld; operands 16-byte aligned)", n, num_class, ld);
         return REID_ERR_ARG;
     }
-    if (num_class > ev->max_classes()) {
+    if (num_class > swin_eval.max_classes()) {
         reid_set_error("Swin descriptor: %d classes, the descriptor kernel holds at most %d (both views' logits stay in LDS)", num_class,
-                       ev->max_classes());
+                       swin_eval.max_classes());
         return REID_ERR_ARG;
     }
     prof_begin(ctx, REID_K_ELEMENTWISE, 2.0 * n * num_class * 96 * (e2 ? 2 : 1), (double)n * ((double)num_class * 96 + num_class + 96 * 3) * 4);
-    const hipError_t e = ev->descriptor(ctx->stream, e1, e2, cls_w, n, num_class, ld, out);
+    const hipError_t e = swin_eval.descriptor(ctx->stream, e1, e2, cls_w, n, num_class, ld, out);
     prof_end(ctx);
     HIP_TRY(e);
     return REID_OK;
@@ -2169,8 +2127,7 @@ int swin_ragged_ready(reid_ctx* ctx, int out_h, int out_w, const float** mean_st
     REID_TRY(swin_crops_args(out_h, out_w, mean_std6));
     const SwinWeights* sw;
     REID_TRY(swin_loaded(ctx, &sw));
-    decltype(&swin_crops_front) front;
-    REID_TRY(swin_crops_api(&front));
+    REID_TRY(swin_crops.open());
     *dim_out = 96;
     return REID_OK;
 }
@@ -2247,15 +2204,11 @@ static int swin_descriptor_ready(reid_ctx* ctx, int n, bool crops, SwinDescPlan*
         return REID_ERR_STATE;
     }
     p->nc = p->sw->num_class;
-    const SwinEvalApi* ev;
-    REID_TRY(swin_eval_api(&ev));
-    if (crops) {
-        decltype(&swin_crops_front) front;
-        REID_TRY(swin_crops_api(&front));
-    }
-    if (p->nc > ev->max_classes()) {
+    REID_TRY(swin_eval.open());
+    if (crops) REID_TRY(swin_crops.open());
+    if (p->nc > swin_eval.max_classes()) {
         reid_set_error("reid_swin_descriptor_*: %d classes, the descriptor kernel holds at most %d (both views' logits stay in LDS)", p->nc,
-                       ev->max_classes());
+                       swin_eval.max_classes());
         return REID_ERR_ARG;
     }
     if ((uintptr_t)p->sw->cls_w & 15) {

@@ -193,11 +193,119 @@ def child():
     eng.close()
 
 
+# ---- the reid_*_hw entries (ResNet18-IBN-SE and its siblings at any input size) through Engine
+HW_SIZES = ((128, 64), (75, 53), (256, 128))             # the last one runs the any-size forward under the switch anysize_force
+
+
+def hw_entry_hashes(eng, tag):
+    """Every _hw entry at HW_SIZES with the loaded weights and the settings the caller made: n = 1 and several passes with a ragged last one
+    (chunk 2: passes of 8 at 128 x 64, of 16 at 75 x 53, of 2 at 256 x 128)."""
+    rag = synth.ragged_crops_u8(19, 4)
+    frame = np.random.default_rng(5).integers(0, 256, (FH, FW, 3), dtype=np.uint8)
+    nc = eng.num_class
+    eng.set_chunk(2)
+    for h, w in HW_SIZES:
+        forced = (h, w) == (256, 128)
+        eng.debug_switch("anysize_force", int(forced))
+        x = np.random.default_rng(h * w).uniform(-1, 1, (19, 3, h, w)).astype(np.float32)
+        for n in (1, 5) if forced else (1, 19):
+            t = "%s %dx%d n %2d" % (tag, h, w, n)
+            if not forced:                               # Engine hands 256 x 128 host images to the entry without a size
+                print(t, "f32_nchw    ", sha(*eng.embed_f32_nchw(x[:n], logits=True)))
+            print(t, "f32_nchw_dev", sha(*dev_call(eng, lambda a, e, l: eng.embed_f32_nchw_dev(a, n, e, l, size=(h, w)), x[:n], n, 512, nc)))
+            print(t, "ragged_u8   ", sha(*eng.embed_ragged_u8(rag[:n], logits=True, size=(h, w))))
+            print(t, "frame_u8    ", sha(*eng.embed_frame_u8(frame, boxes_for(n, n), logits=True, size=(h, w))))
+    eng.debug_switch("anysize_force", 0)
+
+
+def hw_stage_hashes(eng, tag):
+    """The eleven taps of one pass of 3 images at 75 x 53 under debug_keep."""
+    x = np.random.default_rng(7).uniform(-1, 1, (3, 3, 75, 53)).astype(np.float32)
+    eng.set_chunk(1024)
+    eng.debug_keep(1)
+    eng.embed_f32_nchw(x, logits=True)
+    for s in range(11):
+        print("%s stage %2d" % (tag, s), sha(eng.debug_stage(s, 3, size=(75, 53))))
+    eng.debug_keep(0)
+
+
+def hw_refusal(eng, what, h=128, w=64):
+    x, emb = np.zeros((1, 3, h, w), np.float32), np.zeros((1, 512), np.float32)
+    st = eng.lib.reid_embed_f32_nchw_hw(eng.h, p(x), 1, h, w, p(emb), None)
+    msg = eng.lib.reid_last_error().decode() if st else ""
+    print("STATUS hw %-45s %d   fault %d  %s" % (what, st, eng.fault_bits(), msg.split(";")[0]))
+
+
+def hw_entries():
+    eng = Engine(0)
+    load = lambda sd: eng.load_seres18(*weights.pack_seres18(sd)[:2])
+    load(synth.seres18_state_dict(0))
+    hw_entry_hashes(eng, "hw seres18 default   ")
+    hw_stage_hashes(eng, "hw seres18 default   ")
+    hw_refusal(eng, "a side of 31", 31, 64)
+    eng.set_precision(1)
+    hw_refusal(eng, "precision mode 1 without hw_precision")
+    eng.set_precision(0)
+    eng.set_hw_precision(2)
+    hw_entry_hashes(eng, "hw seres18 precision2")
+    eng.set_hw_precision(None)
+    eng.set_hw_f16(True)
+    hw_entry_hashes(eng, "hw seres18 f16       ")
+    hw_stage_hashes(eng, "hw seres18 f16       ")
+    eng.set_hw_f16(False)
+    load(synth.cares18_state_dict(0))
+    hw_refusal(eng, "cares18_ibn without hw_siblings")
+    eng.set_hw_f16(True)
+    hw_refusal(eng, "hw_f16 with cares18_ibn loaded")
+    eng.set_hw_f16(False)
+    eng.set_hw_siblings(True)
+    hw_entry_hashes(eng, "hw cares18 siblings  ")
+    eng.set_hw_siblings(False)
+    load(synth.emares18_state_dict(0))
+    hw_refusal(eng, "emares18_ibn without hw_ema")
+    eng.set_hw_ema(True)
+    hw_entry_hashes(eng, "hw emares18 ema      ")
+    eng.close()
+
+
+def missing_anysize_f16_library():
+    """The hw_f16 forward in a child process whose product library lies in a directory without libreid_hip_anysize_f16.so."""
+    src = os.path.dirname(os.path.abspath(_ffi.LIB_PATH))
+    with tempfile.TemporaryDirectory() as tmp:
+        for f in os.listdir(src):
+            if f.startswith("libreid_hip") and f.endswith(".so") and "anysize_f16" not in f:
+                shutil.copy(os.path.join(src, f), tmp)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-hw"], env=dict(os.environ, REID_HIP_LIB=os.path.join(tmp, "libreid_hip.so")),
+                           capture_output=True, text=True, timeout=300)
+        sys.stdout.write(r.stdout.replace(tmp, "<dir>"))
+        if r.returncode:
+            sys.stdout.write("child exit %d\n%s" % (r.returncode, r.stderr[-2000:]))
+
+
+def child_hw():
+    eng = Engine(0)
+    eng.load_seres18(*weights.pack_seres18(synth.seres18_state_dict(0))[:2])
+    eng.set_hw_f16(True)
+    x, emb = np.zeros((1, 3, 128, 64), np.float32), np.zeros((1, 512), np.float32)
+    for n in (0, 1, 1):                                  # twice: a failed open is tried, and reported, again
+        st = eng.lib.reid_embed_f32_nchw_hw(eng.h, p(x), n, 128, 64, p(emb), None)
+        msg = eng.lib.reid_last_error().decode() if st else ""
+        print("STATUS %-12s %-30s %-30s %d   fault %d  %s" % ("no f16 lib", "n = %d" % n, "reid_embed_f32_nchw_hw", st, eng.fault_bits(), msg.split(":")[0]))
+    eng.set_hw_f16(False)
+    st = eng.lib.reid_embed_f32_nchw_hw(eng.h, p(x), 1, 128, 64, p(emb), None)
+    print("STATUS %-12s %-30s %-30s %d   fault %d  %s" % ("no f16 lib", "n = 1, hw_f16 off", "reid_embed_f32_nchw_hw", st, eng.fault_bits(), sha(emb)))
+    eng.close()
+
+
 if __name__ == "__main__":
     if "--child" in sys.argv:
         child()
+    elif "--child-hw" in sys.argv:
+        child_hw()
     else:
         e = hashes()
         statuses(e)
         e.close()
         missing_crops_library()
+        hw_entries()
+        missing_anysize_f16_library()
