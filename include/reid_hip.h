@@ -257,7 +257,9 @@ int reid_argmin_rows_dev(reid_ctx* ctx, const float* d_x, int m, const float* d_
  * distance + selection (no nq x nb matrix), otherwise distance matrix tiles + a top-k pass.
  * A NaN distance is not a candidate (the rule at reid_argmin_rows): a row with fewer than k non-NaN distances - k > nb, or NaN in the
  * operands - is padded with (I = -1, D = +inf).  reid_rerank_jaccard skips such an index (csrc/rerank.hip checks 0 <= index < n).
- * (Tested for the two-pass and the fused fp32 path; the wide path of large searches, csrc/knn_wide.hip, expects finite operands.)
+ * The rule holds on every path, the wide one of large searches (csrc/knn_wide.hip) included: when a squared row norm is NaN or +inf - a
+ * non-finite component, or finite ones whose square overflows fp32 - that path answers the whole call from exact fp32 distances (slow,
+ * and the fused search's bits); no reid_knn* path raises the context's fault word.
  * search_raw_array_pytorch / IndexFlatL2.search, reid/faiss_utils.py:56-139 */
 int reid_knn(reid_ctx* ctx, const float* xq, int nq, const float* xb, int nb, int d, int k, float* D, int32_t* I);
 int reid_knn_dev(reid_ctx* ctx, const float* d_xq, int nq, const float* d_xb, int nb, int d, int k,

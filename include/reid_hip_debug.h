@@ -332,6 +332,20 @@ int reid_debug_select_exp(reid_ctx* ctx, int mode);
 /* Test switch of the large k-NN path (candidates on the f16 matrix pipe + exact fp32 refinement): enable = 0 -> fused fp32 search
  * for every size; force > 0 -> rows whose index is a multiple of it take the exact-row fallback. */
 int reid_debug_knn_wide(reid_ctx* ctx, int enable, int force);
+/* knn_wide_eligible (csrc/knn_wide.hip): 1 when reid_knn_dev sends this shape through the large k-NN path under the context's switches. */
+int reid_debug_knn_wide_eligible(reid_ctx* ctx, int nq, int nb, int d, int k);
+/* The large k-NN path itself on host operands xq [nq][d], xb [nb][d], 1 <= k <= 24, whatever reid_debug_knn_wide_eligible says: rows
+ * zero-padded to a multiple of 64 floats and squared norms as reid_knn_dev makes them, then knn_wide_dev.  D / I are [nq + 1][k]: the
+ * device outputs carry one guard row preset to 0xff bytes, which is returned with them.  tile_rows > 0 (a multiple of 256) replaces the
+ * rule that bounds the scratch matrix to 1 GiB by query tiles, for this call only.  For a call of ONE tile the stages come back too
+ * (each pointer may be NULL; with several tiles they must be):
+ *   mat   fp32 [nq][ceil256(nb)]  the candidate matrix sx sy (|y|^2 - 2 x.y) as selection and proof read it (padding columns: whatever the GEMM left);
+ *   keys  uint64 [nq][32]         the 32 smallest of each row, (order-preserving key of the value << 32) | column, ascending, ~0 = none;
+ *   flags int32 [nq]              rows sent through the exact-row fallback (forced, more than 1024 survivors, proof failed);
+ *   sc    fp32 [4]                sx, sy, sx sy, max |y|^2;
+ * nflagged: the rows the fallback kernel recomputed, counted on the device.  Waits for the stream. */
+int reid_debug_knn_wide_run(reid_ctx* ctx, const float* xq, int nq, const float* xb, int nb, int d, int k, int tile_rows, float* D,
+                            int32_t* I, float* mat, unsigned long long* keys, int32_t* flags, float* sc, int32_t* nflagged);
 /* reid_argmin_rows_x3_dev (k = 1, any metric) / reid_knn_x3_dev (metric = REID_METRIC_L2SQR) through the launcher those entries call, on
  * device operands (d_D [m][k] may be NULL, d_I [m][k]), with the test hook and the statistics they do not expose:
  * force_fallback_every = f > 0 sends every row whose index is a multiple of f through the exact-row kernel (the hook reid_debug_knn_wide

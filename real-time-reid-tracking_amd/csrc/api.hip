@@ -2239,7 +2239,7 @@ extern "C" int reid_distmat(reid_ctx* ctx, const float* x, int m, const float* y
 }
 
 // zero-padded copy with rows of a multiple of `mult` floats (mult = 4: 16-byte rows; 32: whole K-tiles of the LDS-DMA loops)
-static int pad_rows_to(reid_ctx* ctx, const char* name, const float* d_x, int m, int d, int mult, const float** out, int* ld) {
+int pad_rows_to(reid_ctx* ctx, const char* name, const float* d_x, int m, int d, int mult, const float** out, int* ld) {
     if (d % mult == 0 && ((uintptr_t)d_x % 16) == 0) {
         *out = d_x;
         *ld = d;

@@ -982,11 +982,11 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
 }
 }  // namespace
 
-int launch_split_pack(reid_ctx* ctx, const float* x, long long rows, int C, _Float16* out, const float* d_scale) {
+int launch_split_pack(reid_ctx* ctx, const float* x, long long rows, int C, _Float16* out, const float* d_scale, bool range_fault) {
     ARG_CHECK(C % 8 == 0);
     prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)rows * C * 8.0);
     hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)((rows * (C / 8) + 255) / 256)), dim3(256), 0, ctx->stream, x, rows, C, out,
-                       ctx->fault, d_scale);
+                       range_fault ? ctx->fault : nullptr, d_scale);
     prof_end(ctx);
     LAUNCH_CHECK();
     return REID_OK;

@@ -394,6 +394,65 @@ extern "C" int reid_debug_knn_wide(reid_ctx* ctx, int enable, int force) {
     return REID_OK;
 }
 
+extern "C" int reid_debug_knn_wide_eligible(reid_ctx* ctx, int nq, int nb, int d, int k) {
+    return ctx && knn_wide_eligible(ctx, nq, nb, d, k) ? 1 : 0;
+}
+
+// knn_wide_dev on host operands, called as reid_knn_dev calls it (rows zero-padded to a multiple of 64 floats, squared norms from
+// launch_row_sqnorm) whatever knn_wide_eligible says, with the stages the product entry does not expose (include/reid_hip_debug.h).
+// D / I [nq + 1][k]: the device outputs carry one guard row preset to 0xff bytes, which comes back with them.  tile_rows > 0 (a multiple
+// of 256) replaces the query-tile rule for this call.  mat [nq][ceil256(nb)], keys [nq][32], flags [nq], sc [4] (each may be null) are
+// filled for a call of ONE tile only (with several, keys belong to the last tile: REID_ERR_ARG); nflagged: the rows exact_row_kernel redid.
+extern "C" int reid_debug_knn_wide_run(reid_ctx* ctx, const float* xq, int nq, const float* xb, int nb, int d, int k, int tile_rows, float* D,
+                                       int32_t* I, float* mat, unsigned long long* keys, int32_t* flags, float* sc, int32_t* nflagged) {
+    ARG_CHECK(ctx && xq && xb && D && I && nflagged && nq >= 1 && nb >= 1 && d >= 1 && k >= 1 && k <= 24 && tile_rows >= 0 && tile_rows % 256 == 0);
+    const size_t nbpad = ((size_t)nb + 255) / 256 * 256;
+    const bool one_tile = (tile_rows == 0 || nq <= tile_rows) && (size_t)nq * nbpad <= ((size_t)1 << 28);
+    ARG_CHECK(one_tile || (!mat && !keys && !flags && !sc));
+    CTX_ENTER(ctx);
+    float *dx, *dy, *xx, *yy, *dD, *dmat = nullptr;
+    int32_t* dI;
+    REID_TRY(ctx_ws(ctx, "dbgk.x", (size_t)nq * d * 4, (void**)&dx));
+    REID_TRY(ctx_ws(ctx, "dbgk.y", (size_t)nb * d * 4, (void**)&dy));
+    REID_TRY(ctx_ws(ctx, "dbgk.D", (size_t)(nq + 1) * k * 4, (void**)&dD));
+    REID_TRY(ctx_ws(ctx, "dbgk.I", (size_t)(nq + 1) * k * 4, (void**)&dI));
+    if (mat) REID_TRY(ctx_ws(ctx, "dbgk.mat", (size_t)nq * nbpad * 4, (void**)&dmat));
+    HIP_TRY(hipMemcpyAsync(dx, xq, (size_t)nq * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dy, xb, (size_t)nb * d * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(dD, 0xff, (size_t)(nq + 1) * k * 4, ctx->stream));
+    HIP_TRY(hipMemsetAsync(dI, 0xff, (size_t)(nq + 1) * k * 4, ctx->stream));
+    if (dmat) HIP_TRY(hipMemsetAsync(dmat, 0xff, (size_t)nq * nbpad * 4, ctx->stream));
+    const float *xp, *yp;
+    int ldx, ldy;
+    REID_TRY(pad_rows_to(ctx, "sel.xpad", dx, nq, d, 64, &xp, &ldx));
+    REID_TRY(pad_rows_to(ctx, "sel.ypad", dy, nb, d, 64, &yp, &ldy));
+    REID_TRY(ctx_ws(ctx, "dist.xx", (size_t)nq * 4, (void**)&xx));
+    REID_TRY(ctx_ws(ctx, "dist.yy", (size_t)nb * 4, (void**)&yy));
+    REID_TRY(launch_row_sqnorm(ctx, xp, nq, ldx, ldx, xx));
+    REID_TRY(launch_row_sqnorm(ctx, yp, nb, ldy, ldy, yy));
+    const int t0 = ctx->knn_wide_tile_rows;
+    ctx->knn_wide_tile_rows = tile_rows;
+    const int st = knn_wide_dev(ctx, xp, nq, yp, nb, ldx, xx, yy, k, dD, dI, dmat);
+    ctx->knn_wide_tile_rows = t0;
+    REID_TRY(st);
+    // the stage buffers, by the names and sizes knn_wide_dev asked for (ctx_ws hands an existing buffer back)
+    unsigned long long* dkeys = nullptr;
+    int32_t* dflags;
+    float* dsc;
+    if (keys) REID_TRY(ctx_ws(ctx, "knnw.keys", (size_t)nq * 32 * 8, (void**)&dkeys));
+    REID_TRY(ctx_ws(ctx, "knnw.flags", (size_t)nq * 4 + 16, (void**)&dflags));
+    REID_TRY(ctx_ws(ctx, "knnw.sc", 16, (void**)&dsc));
+    HIP_TRY(hipMemcpyAsync(D, dD, (size_t)(nq + 1) * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(I, dI, (size_t)(nq + 1) * k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(nflagged, dflags + nq, 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (mat) HIP_TRY(hipMemcpyAsync(mat, dmat, (size_t)nq * nbpad * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (keys) HIP_TRY(hipMemcpyAsync(keys, dkeys, (size_t)nq * 32 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (flags) HIP_TRY(hipMemcpyAsync(flags, dflags, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (sc) HIP_TRY(hipMemcpyAsync(sc, dsc, 16, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return REID_OK;
+}
+
 // The selection with fp32-class candidates (libreid_hip_select_x3.so) through the launcher reid_argmin_rows_x3_dev / reid_knn_x3_dev call,
 // on device operands, with the test hook and the statistics those entries do not expose: force_fallback_every > 0 sends every row whose
 // index is a multiple of it through the exact-row kernel; stats = {rows proven, rows recomputed, tile form, candidates per row}.

@@ -13,6 +13,8 @@
 //   4. proof per row that no non-candidate can belong to the answer: every non-candidate's approximate value is >= the 32nd
 //      candidate's, so its exact value is >= that minus the error bound of step 1; if the k-th exact value does not stay below
 //      that, the row is flagged and exact_row_kernel redoes it from all n columns (rare: the margin is 32 - k candidates wide).
+// reid_knn's rule for NaN distances (include/reid_hip.h) holds here as on the other paths: a row with a NaN among its candidates' distances
+// is flagged, and when a squared norm is NaN or +inf every row of the call is - exact_row_kernel ranks with the rule's empty key.
 #include "reid_internal.h"
 #include <math.h>
 #include <string.h>
@@ -29,6 +31,8 @@ __device__ __forceinline__ unsigned long long pack_key(float v, int idx) {
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
     return ((unsigned long long)u << 32) | (unsigned int)idx;
 }
+// A NaN distance, of either sign bit, is no candidate (include/reid_hip.h, reid_argmin_rows / reid_knn; select.hip's cand_key): the empty key ~0
+__device__ __forceinline__ unsigned long long cand_key(float v, int idx) { return v == v ? pack_key(v, idx) : ~0ull; }
 __device__ __forceinline__ float unpack_val(unsigned long long k) {
     unsigned int u = (unsigned int)(k >> 32);
     u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
@@ -114,7 +118,7 @@ __global__ __launch_bounds__(256) void rowsel_kernel(const float* __restrict__ m
 __global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ x, long long ldx, const float* __restrict__ y, long long ldy, int K,
                                                      const float* __restrict__ rs, const float* __restrict__ cq, const float* __restrict__ sc,
                                                      const unsigned long long* __restrict__ keys, int rows, int n, int k, float err_scale,
-                                                     float* __restrict__ D, int32_t* __restrict__ I, int* __restrict__ flags) {
+                                                     float err_abs, float* __restrict__ D, int32_t* __restrict__ I, int* __restrict__ flags) {
     const int lane = threadIdx.x & 63, half = lane >> 5, c = lane & 31;
     const int row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + half;
     const bool live = row < rows;
@@ -129,7 +133,7 @@ __global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ x
     }
     const float r2 = live ? rs[row] : 0.f;
     const float e = valid ? l2sqr_of(dot, r2, cq[idx]) : INFINITY;
-    const unsigned long long ek = valid ? pack_key(e, idx) : ~0ull;
+    const unsigned long long ek = valid ? cand_key(e, idx) : ~0ull;       // (finite operands whose norms overflow against each other: inf - inf)
     // rank among the 32 candidates of this row (keys are unique: they carry the column)
     int rank = 0;
 #pragma unroll
@@ -137,10 +141,13 @@ __global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ x
         const unsigned long long other = __shfl(ek, half * 32 + o);
         rank += other < ek;
     }
+    const bool cand = ek != ~0ull;
     if (live && rank < k) {
-        D[(long long)row * k + rank] = valid ? e : INFINITY;
-        I[(long long)row * k + rank] = valid ? idx : -1;
+        D[(long long)row * k + rank] = cand ? e : INFINITY;
+        I[(long long)row * k + rank] = cand ? idx : -1;
     }
+    // a NaN among the candidates' distances: empty keys share a rank, and columns outside the candidates may be the row's answer
+    const unsigned nan_c = (unsigned)(__ballot(valid && !cand) >> (half * 32));
     // proof: the k-th exact value, in the matrix's units (without |x|^2), stays below the 32nd approximate value minus the error
     // of the approximate arithmetic
     const int kth = k < 32 ? k - 1 : 31;
@@ -153,9 +160,10 @@ __global__ __launch_bounds__(256) void refine_kernel(const float* __restrict__ x
         a_last = fmaxf(a_last, __shfl_xor(a_last, o));
     }
     if (live && c == 0) {
-        const float err = err_scale * (r2 + sc[3]) * ss;
+        const float err = err_scale * (r2 + sc[3]) * ss + err_abs;
         const bool enough = n <= KK;                               // every column is a candidate
-        if (!enough && !(ek_val + err < a_last - err)) flags[row] = 1;
+        // sc[4]: a non-finite squared norm somewhere in the call - the candidate stage has nothing to say, every row is answered exactly
+        if (sc[4] != 0.f || nan_c || (!enough && !(ek_val + err < a_last - err))) flags[row] = 1;
     }
 }
 
@@ -184,7 +192,7 @@ __global__ __launch_bounds__(256) void exact_row_kernel(const float* __restrict_
     for (int r = 0; r < k; ++r) {
         unsigned long long best = ~0ull;
         for (int j = tid; j < n; j += 256) {
-            const unsigned long long key = pack_key(out[j], j);
+            const unsigned long long key = cand_key(out[j], j);   // best == ~0: the row has run out of candidates, (+inf, -1) from here on
             if ((r == 0 || key > last) && key < best) best = key;
         }
 #pragma unroll
@@ -208,12 +216,19 @@ __global__ __launch_bounds__(256) void exact_row_kernel(const float* __restrict_
 // The candidate stage works on NORMALISED operands (the k-NN entry point takes any features; the split needs |value| 2^11 inside
 // f16): sc[0] = sx, sc[1] = sy powers of two with max |x| sx <= 1 and max |y| sy <= 1, sc[2] = sx sy, sc[3] = max |y|^2.  Scaling by
 // a power of two is exact and a positive factor keeps every row's order, so the candidate matrix holds sx sy (|y|^2 - 2 x.y).
+// sc[4] = 1 when a squared norm is NaN or +inf (a non-finite component, or finite ones beyond fp32's square root): the candidate stage
+// has nothing to say about such operands: refine_kernel flags every row, and exact_row_kernel answers them under the NaN rule - the fused fp32
+// search's answer, at the speed of a fallback.  Finite operands pay nothing for it: the norms are read here anyway.
 __global__ __launch_bounds__(256) void scale_prep_kernel(const float* __restrict__ rs, int nq, const float* __restrict__ cq, int nb,
                                                          float* __restrict__ sc) {
     __shared__ float sh[2][4];
-    float mx = 0.f, my = 0.f;
-    for (int i = threadIdx.x; i < nq; i += 256) mx = fmaxf(mx, rs[i]);
-    for (int i = threadIdx.x; i < nb; i += 256) my = fmaxf(my, cq[i]);
+    // the maxima on the bit patterns: a squared norm is >= 0 or NaN, so unsigned order is the values' order with +inf and every NaN
+    // (either sign, after the mask) on top - one max per element, as fmaxf was, and the non-finite norms are not skipped
+    unsigned ux = 0u, uy = 0u;
+    for (int i = threadIdx.x; i < nq; i += 256) { const unsigned b = __float_as_uint(rs[i]) & 0x7fffffffu; ux = b > ux ? b : ux; }
+    for (int i = threadIdx.x; i < nb; i += 256) { const unsigned b = __float_as_uint(cq[i]) & 0x7fffffffu; uy = b > uy ? b : uy; }
+    const int bad = __syncthreads_or(ux >= 0x7f800000u || uy >= 0x7f800000u);
+    float mx = ux < 0x7f800000u ? __uint_as_float(ux) : 0.f, my = uy < 0x7f800000u ? __uint_as_float(uy) : 0.f;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         mx = fmaxf(mx, __shfl_xor(mx, o));
@@ -232,7 +247,7 @@ __global__ __launch_bounds__(256) void scale_prep_kernel(const float* __restrict
             return ldexpf(1.0f, -e);
         };
         const float sx = pow2_inv(mx), sy = pow2_inv(my);
-        sc[0] = sx; sc[1] = sy; sc[2] = sx * sy; sc[3] = my;
+        sc[0] = sx; sc[1] = sy; sc[2] = sx * sy; sc[3] = my; sc[4] = bad ? 1.0f : 0.0f;
     }
 }
 __global__ __launch_bounds__(256) void scaled_bias_kernel(const float* __restrict__ cq, int nb, const float* __restrict__ sc, float* __restrict__ out) {
@@ -249,8 +264,8 @@ bool knn_wide_eligible(reid_ctx* ctx, int nq, int nb, int d, int k) {
 // xp [nq][ld] / yp [nb][ld]: the zero-padded operands of the fused fp32 search (ld % 64 == 0), rs / cq their squared norms.
 // force_flags != 0 (tests): every row whose index is a multiple of it takes the exact fallback.
 int knn_wide_dev(reid_ctx* ctx, const float* xp, int nq, const float* yp, int nb, int ld, const float* rs, const float* cq, int k, float* d_D,
-                 int32_t* d_I) {
-    ARG_CHECK(ld % 64 == 0 && k <= 24);
+                 int32_t* d_I, float* cand_out) {
+    ARG_CHECK(ld % 64 == 0 && k <= 24 && ctx->knn_wide_tile_rows >= 0 && ctx->knn_wide_tile_rows % 256 == 0);
     const int nbpad = (nb + 255) / 256 * 256;       // whole 256-column GEMM tiles; the matrix rows have this pitch (16-byte aligned)
     f16 *a16, *w16;
     float *mat, *sc, *biasv;
@@ -258,7 +273,7 @@ int knn_wide_dev(reid_ctx* ctx, const float* xp, int nq, const float* yp, int nb
     int *flags, *nflag;
     REID_TRY(ctx_ws(ctx, "knnw.a16", (size_t)nq * 2 * ld * 2, (void**)&a16));
     REID_TRY(ctx_ws(ctx, "knnw.w16", (size_t)nbpad * 3 * ld * 2, (void**)&w16));
-    REID_TRY(ctx_ws(ctx, "knnw.sc", 16, (void**)&sc));
+    REID_TRY(ctx_ws(ctx, "knnw.sc", 32, (void**)&sc));
     REID_TRY(ctx_ws(ctx, "knnw.bias", (size_t)nb * 4, (void**)&biasv));
     REID_TRY(ctx_ws(ctx, "knnw.flags", (size_t)nq * 4 + 16, (void**)&flags));
     nflag = flags + nq;
@@ -272,12 +287,14 @@ int knn_wide_dev(reid_ctx* ctx, const float* xp, int nq, const float* yp, int nb
     hipLaunchKernelGGL(scale_prep_kernel, dim3(1), dim3(256), 0, ctx->stream, rs, nq, cq, nb, sc);
     hipLaunchKernelGGL(scaled_bias_kernel, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, cq, nb, sc, biasv);
     LAUNCH_CHECK();
-    REID_TRY(launch_split_pack(ctx, xp, nq, ld, a16, sc));
+    // no range fault from here: every finite scaled value lies in [-1, 1], and reid_knn answers the others in exact fp32 (sc[4])
+    REID_TRY(launch_split_pack(ctx, xp, nq, ld, a16, sc, false));
     if (nbpad > nb) HIP_TRY(hipMemsetAsync(w16 + (size_t)nb * 3 * ld, 0, (size_t)(nbpad - nb) * 3 * ld * 2, ctx->stream));
     REID_TRY(launch_split_weights(ctx, yp, nb, 1, ld, 3, w16, sc + 1));
     // query tiles bound the scratch matrix to 1 GiB; whole 256-row GEMM tiles
     long long rows_per = ((long long)1 << 28) / nbpad / 256 * 256;
     if (rows_per < 256) rows_per = 256;
+    if (ctx->knn_wide_tile_rows > 0) rows_per = ctx->knn_wide_tile_rows;     // tests: several tiles at a small nq
     const int tile = nq < rows_per ? nq : (int)rows_per;
     REID_TRY(ctx_ws(ctx, "knnw.mat", (size_t)tile * nbpad * 4, (void**)&mat));
     REID_TRY(ctx_ws(ctx, "knnw.keys", (size_t)tile * KK * 8, (void**)&keys));
@@ -285,6 +302,12 @@ int knn_wide_dev(reid_ctx* ctx, const float* xp, int nq, const float* yp, int nb
     // |x||y|), and the fp32 accumulator is rounded once or twice per MFMA over a chain of 3 ld / 16 of them (each at most 2^-24 of the
     // running sum <= 2^11 sum |x_k y_k|); times two for the factor -2, and |x||y| <= (|x|^2 + |y|^2) / 2
     const float err_scale = (6.0f * (float)ld / 16.0f + 16.0f) / 16777216.0f;
+    // ... and what f16's smallest step, 2^-24, adds to that in absolute terms: a scaled component v in [-1, 1] splits with
+    // |v - vh| <= 2^-11 |v| + 2^-25 and |v - vh - vl| <= 2^-11 |v - vh| + 2^-36; in xl.yl + ex y + x ey the parts that are not a 2^-22
+    // share of |x_k y_k| sum to less than 3 x 2^-35 + 2^-50 < 2^-33 per multiply; ld multiplies, times two.  Nothing next to the
+    // relative term unless one row sets the scale and others lie 2^14 and more below it - their parts are f16 subnormals then, and the
+    // matrix was found 219 times the relative term off (tests/test_gpu_knn_wide.py, the outlier_q24 family)
+    const float err_abs = (float)ld / 4294967296.0f;
     for (int i = 0; i < nq; i += tile) {
         const int m = nq - i < tile ? nq - i : tile;
         Gemm16Params q;
@@ -306,7 +329,9 @@ int knn_wide_dev(reid_ctx* ctx, const float* xp, int nq, const float* yp, int nb
         prof_begin(ctx, REID_K_SELECT, 0, (double)m * nb * 8.0);
         hipLaunchKernelGGL(rowsel_kernel, dim3(m), dim3(256), 0, ctx->stream, mat, nb, (long long)nbpad, keys, flags + i);
         hipLaunchKernelGGL(refine_kernel, dim3((m + 7) / 8), dim3(256), 0, ctx->stream, xp + (size_t)i * ld, (long long)ld, yp, (long long)ld, ld,
-                           rs + i, cq, sc, keys, m, nb, k, err_scale, d_D + (size_t)i * k, d_I + (size_t)i * k, flags + i);
+                           rs + i, cq, sc, keys, m, nb, k, err_scale, err_abs, d_D + (size_t)i * k, d_I + (size_t)i * k, flags + i);
+        if (cand_out)      // tests: the matrix before exact_row_kernel reuses the flagged rows' slots
+            HIP_TRY(hipMemcpyAsync(cand_out + (size_t)i * nbpad, mat, (size_t)m * nbpad * 4, hipMemcpyDeviceToDevice, ctx->stream));
         hipLaunchKernelGGL(exact_row_kernel, dim3(m), dim3(256), 0, ctx->stream, xp + (size_t)i * ld, (long long)ld, yp, (long long)ld, ld, rs + i, cq,
                            mat, (long long)nbpad, nb, k, d_D + (size_t)i * k, d_I + (size_t)i * k, flags + i, nflag);
         prof_end(ctx);

@@ -251,7 +251,7 @@ int launch_sfe_conv1_mirror(reid_ctx* ctx, const float* x, int n, int h, int w, 
 int launch_swin_crop_front_mirror(reid_ctx* ctx, const uint8_t* d_src, const long long* d_off, const int* d_hw, int n, int h, int w, int pitch,
                                   const float* mean_std6, const float* c1_w, const float* c1_b, float* c1);
 int launch_swin_descriptor(reid_ctx* ctx, const float* e1, const float* e2, const float* cls_w, int n, int num_class, long long ld, float* out);
-int launch_split_pack(reid_ctx* ctx, const float* x, long long rows, int C, _Float16* out, const float* d_scale = nullptr);           // fp32 [rows][C] -> f16 [rows][2C] = [xh | xl']
+int launch_split_pack(reid_ctx* ctx, const float* x, long long rows, int C, _Float16* out, const float* d_scale = nullptr, bool range_fault = true);  // fp32 [rows][C] -> f16 [rows][2C] = [xh | xl']; range_fault = false: a value outside f16 leaves the fault word alone (knn_wide.hip answers such a call in exact fp32)
 int launch_split_weights(reid_ctx* ctx, const float* w, int cout, int taps, int cin, int terms, _Float16* out, const float* d_scale = nullptr);  // fp32 [cout][taps][cin] -> f16 [cout][taps][terms * cin]
 // fp16 elementwise kernels (elementwise_f16.hip)
 int launch_prep_u8_pad_f16(reid_ctx*, const uint8_t* crops, int n, int h, int w, int hp, int wp, _Float16* out);
@@ -468,6 +468,7 @@ struct reid_ctx {
                              // the fused fp32 search for every size)
     long long knn_wide_min = 1ll << 25;   // query x gallery pairs from which the wide path is taken (REID_KNN_WIDE_MIN): Market-size (3368 x 15913) 0.68 -> 0.41 ms
     int knn_wide_force = 0;  // tests (reid_debug_knn_wide): every row whose index is a multiple of it takes the exact-row fallback
+    int knn_wide_tile_rows = 0;   // tests (reid_debug_knn_wide_run): query rows per tile of the wide path instead of its 1 GiB rule; a multiple of 256
     int select_exp = 0;      // experiments only (reid_debug_select_exp, debug.hip): 1 / 2 skip phases of the fused selection (results
                              // are then incomplete), 4 prints candidate-list statistics
     int select_two_pass = 0; // REID_SELECT_TWO_PASS=1: arg-min / k-NN through the full distance matrix (A/B against dist_select.hip)
@@ -543,8 +544,12 @@ enum { REID_FAULT_RANGE = 1, REID_FAULT_NONFINITE = 2 };
 int ctx_fault_status(reid_ctx* ctx);
 // knn_wide.hip: brute-force k-NN for large problems (candidates in fp32-class arithmetic, exact fp32 refinement)
 bool knn_wide_eligible(reid_ctx* ctx, int nq, int nb, int d, int k);
+// cand_out (tests, reid_debug_knn_wide_run; may be null): device [nq][ceil256(nb)], receives the candidate matrix as rowsel_kernel and
+// refine_kernel saw it - exact_row_kernel reuses a flagged row's slot; the other stages stay in the workspaces knnw.keys / .flags / .sc
 int knn_wide_dev(reid_ctx* ctx, const float* xp, int nq, const float* yp, int nb, int ld, const float* rs, const float* cq, int k, float* d_D,
-                 int32_t* d_I);   // api.hip: REID_OK, or REID_ERR_STATE + message when the fault word is set
+                 int32_t* d_I, float* cand_out = nullptr);
+// api.hip: zero-padded copy of d_x [m][d] with rows of a multiple of `mult` floats (the operand itself when it has such rows already)
+int pad_rows_to(reid_ctx* ctx, const char* name, const float* d_x, int m, int d, int mult, const float** out, int* ld);
 // api.hip: the launcher of reid_argmin_rows_x3* / reid_knn_x3* (libreid_hip_select_x3.so, select_x3.h) on device operands; d_D may be null;
 // force_every > 0: rows whose index is a multiple of it take the exact-row kernel; stats (host, may be null): waits for the stream,
 // then {rows proven, rows recomputed, tile form, candidates per row}

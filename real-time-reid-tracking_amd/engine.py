@@ -1466,6 +1466,43 @@ class Engine:
                  int(force_fallback_every), stats))
         return dict(zip(("proven", "recomputed", "form", "kk"), (int(v) for v in stats)))
 
+    def debug_knn_wide(self, enable=1, force=0):
+        """reid_debug_knn_wide: enable = 0 sends every search through the fused fp32 kernel; force > 0 sends every row whose index is
+        a multiple of it through the exact-row fallback of the large k-NN path."""
+        fn = _ffi.debug_lib().reid_debug_knn_wide
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        check(fn(self.h, int(enable), int(force)))
+
+    def debug_knn_wide_eligible(self, nq, nb, d, k):
+        """reid_debug_knn_wide_eligible: does reid_knn_dev take the large k-NN path (csrc/knn_wide.hip) at this shape?"""
+        fn = _ffi.debug_lib().reid_debug_knn_wide_eligible
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p] + [C.c_int] * 4
+        return bool(fn(self.h, int(nq), int(nb), int(d), int(k)))
+
+    def debug_knn_wide_run(self, xq, xb, k, tile_rows=0, stages=True):
+        """reid_debug_knn_wide_run: the large k-NN path on host operands.  Returns a dict: D [nq, k], I [nq, k], guard_D / guard_I (the
+        guard rows behind them, as uint32 / int32: untouched = all bits set), nflagged, and with ``stages`` (one tile only) mat
+        [nq, ceil256(nb)], keys uint64 [nq, 32], flags int32 [nq], sc float32 [4]."""
+        xq, xb = _f32(xq), _f32(xb)
+        nq, nb, d = xq.shape[0], xb.shape[0], xq.shape[1]
+        nbpad = (nb + 255) // 256 * 256
+        D = np.empty((nq + 1, k), np.float32)
+        I = np.empty((nq + 1, k), np.int32)
+        nfl = C.c_int32(-1)
+        out = {}
+        if stages:
+            out = {"mat": np.empty((nq, nbpad), np.float32), "keys": np.empty((nq, 32), np.uint64), "flags": np.empty(nq, np.int32),
+                   "sc": np.empty(4, np.float32)}
+        fn = _ffi.debug_lib().reid_debug_knn_wide_run
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 7
+        check(fn(self.h, _ptr(xq), nq, _ptr(xb), nb, d, int(k), int(tile_rows), _ptr(D), _ptr(I),
+                 *[_ptr(out[n]) if stages else None for n in ("mat", "keys", "flags", "sc")], C.cast(C.byref(nfl), C.c_void_p)))
+        out.update(D=D[:nq], I=I[:nq], guard_D=D[nq].view(np.uint32), guard_I=I[nq], nflagged=int(nfl.value))
+        return out
+
     def descriptor_f32_nchw(self, x, flip_tta=True):
         """float32 [n,3,H,W] (normalised by the caller) -> float32 [n, 512 + num_class] retrieval descriptor; sizes as embed_f32_nchw."""
         x = _f32(x)
