@@ -406,6 +406,22 @@ int reid_ctx_set_hw_ema(reid_ctx* ctx, int on);
  *                reid_debug_stage returns the f16 taps widened to fp32, each at its own map size.
  *   Any other value is REID_ERR_ARG and changes nothing.  (256, 128) is never affected. */
 int reid_ctx_set_hw_f16(reid_ctx* ctx, int on);
+/* reid_ctx_set_hw_sib_f16(ctx, on): CARes18-IBN (reid/backbones/CARes18.py) and EMARes18-IBN (reid/backbones/EMA_Res18.py) at input sizes
+ * other than 256 x 128 in the fp16-storage arithmetic, a setting of its own because reid_ctx_set_hw_f16 1 refuses a loaded sibling and
+ * callers of that refusal keep it.
+ *   0 (default)  as above: every status, message and bit unchanged, the refusal of a sibling under reid_ctx_set_hw_f16 1 included.
+ *   1            a loaded cares18_ibn / emares18_ibn runs at another size (32 .. 512 per side) in fp16 storage with fp32 accumulation: stem,
+ *                max-pool, convolutions, IBN finish and GeM + neck of libreid_hip_anysize_f16.so, the TripletAttention / EMA block tail of
+ *                libreid_hip_anysize_sib_f16.so (csrc/anysize_sib_f16.h: fp64 statistics in a fixed order, fp32 gates, one f16 rounding at
+ *                the store) - whatever the context's mode, reid_ctx_set_hw_precision, reid_ctx_set_hw_siblings, reid_ctx_set_hw_ema and
+ *                reid_ctx_set_hw_f16 are; those keep their values and govern again once this setting is back at 0.
+ *                libreid_hip_anysize.so, libreid_hip_anysize_f16.so and libreid_hip_anysize_sib_f16.so must lie beside this library
+ *                (REID_ERR_STATE naming the missing one otherwise, before anything is queued and before a frame slot is touched).  The size
+ *                range, the pass sizes and the side indices are those of seres18_ibn; every reid_*_hw entry, the _shift entries,
+ *                reid_embed_frame_u8_hw and reid_frame_submit_hw follow (the frame entries through resize + normalise and the f16 stem).
+ *                A loaded seres18_ibn is not affected.
+ *   Any other value is REID_ERR_ARG and changes nothing.  (256, 128) is never affected. */
+int reid_ctx_set_hw_sib_f16(reid_ctx* ctx, int on);
 int reid_embed_f32_nchw_hw(reid_ctx* ctx, const float* x, int n, int h, int w, float* emb, float* logits);
 int reid_embed_f32_nchw_hw_dev(reid_ctx* ctx, const float* d_x, int n, int h, int w, float* d_emb, float* d_logits);
 int reid_embed_ragged_u8_hw(reid_ctx* ctx, const uint8_t* packed, const int64_t* offsets, const int32_t* hw, int n, int out_h, int out_w,

@@ -171,6 +171,16 @@ int reid_debug_any_se_tail_f16(reid_ctx* ctx, int n, int hw, int c, int mid, con
                                const uint16_t* shortcut, int alias, uint16_t* out, float* gate);
 int reid_debug_any_gem_f16(reid_ctx* ctx, int n, int hw, int c, float p, const uint16_t* x, const float* scale, const float* shift,
                            float* gem_out, float* emb);
+/* The TripletAttention and EMA block tails of libreid_hip_anysize_sib_f16.so (csrc/anysize_sib_f16.h; tests/test_gpu_anysize_sib_f16.py)
+ * through the launchers the any-size forward calls under reid_ctx_set_hw_sib_f16 1, on host operands: reid_debug_any_ca_tail /
+ * reid_debug_any_ema_tail above with y, shortcut and out handed over as f16 bits (uint16_t), NHWC [n][h][w][c]; prm and the shape range are
+ * theirs (anything else REID_ERR_ARG, out untouched).  out [n h w c + c] carries ONE guard pixel behind the last, preset to 0xff bytes
+ * (NaN in f16) with the rest.  maps / gates and sig / small (may be NULL) are the fp32 workspace statistics, returned with the sizes, the
+ * layouts and the guard the fp32 harnesses return them with.  Returns the context's fault status. */
+int reid_debug_any_ca_tail_f16(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const uint16_t* y, const uint16_t* shortcut,
+                               uint16_t* out, float* maps, float* gates);
+int reid_debug_any_ema_tail_f16(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const uint16_t* y, const uint16_t* shortcut,
+                                uint16_t* out, float* sig, float* small);
 /* The front end of the any-size forward from uint8 windows (tests/test_gpu_anysize_front.py) through the launcher reid_frame_submit_hw and
  * reid_embed_frame_u8_hw call, on host operands: src [src_bytes] holds n windows, window i hw[2i] x hw[2i + 1] pixels at byte offsets[i],
  * its rows one after the other (pitch 0) or `pitch` pixels apart (windows of one frame); every window must lie inside src.  They are

@@ -33,6 +33,7 @@ _SIGS = {
     "reid_ctx_set_hw_siblings": (_i, [_vp, _i]),
     "reid_ctx_set_hw_ema": (_i, [_vp, _i]),
     "reid_ctx_set_hw_f16": (_i, [_vp, _i]),
+    "reid_ctx_set_hw_sib_f16": (_i, [_vp, _i]),
     "reid_ctx_fault_peek": (_i, [_vp, C.POINTER(_i)]),
     "reid_ctx_set_side_index": (_i, [_vp, _vp, _i]),
     "reid_malloc": (_i, [_vp, _sz, C.POINTER(_vp)]),
@@ -136,7 +137,7 @@ _SIGS = {
 EXPORTS = tuple(sorted(_SIGS))
 
 DEBUG_LIB_PATH = os.path.join(_HERE, "libreid_hip_debug.so")
-DEBUG_EXPORTS = ("reid_debug_any_ca_tail", "reid_debug_any_ema_tail", "reid_debug_any_conv", "reid_debug_any_conv_f16", "reid_debug_any_gem_f16", "reid_debug_any_norm_f16", "reid_debug_any_se_tail_f16", "reid_debug_any_stem_f16", "reid_debug_any_front", "reid_debug_any_gem", "reid_debug_any_norm", "reid_debug_any_se_tail", "reid_debug_bank_cost96", "reid_debug_coissue", "reid_debug_comm_loopback", "reid_debug_conv_c64", "reid_debug_conv_c64_se", "reid_debug_conv_layer", "reid_debug_conv_layer_f16", "reid_debug_conv_split", "reid_debug_conv_diag", "reid_debug_conv_f16", "reid_debug_conv_f32", "reid_debug_descriptor", "reid_debug_dist_add_l2", "reid_debug_flip_w",
+DEBUG_EXPORTS = ("reid_debug_any_ca_tail", "reid_debug_any_ca_tail_f16", "reid_debug_any_ema_tail", "reid_debug_any_ema_tail_f16", "reid_debug_any_conv", "reid_debug_any_conv_f16", "reid_debug_any_gem_f16", "reid_debug_any_norm_f16", "reid_debug_any_se_tail_f16", "reid_debug_any_stem_f16", "reid_debug_any_front", "reid_debug_any_gem", "reid_debug_any_norm", "reid_debug_any_se_tail", "reid_debug_bank_cost96", "reid_debug_coissue", "reid_debug_comm_loopback", "reid_debug_conv_c64", "reid_debug_conv_c64_se", "reid_debug_conv_layer", "reid_debug_conv_layer_f16", "reid_debug_conv_split", "reid_debug_conv_diag", "reid_debug_conv_f16", "reid_debug_conv_f32", "reid_debug_descriptor", "reid_debug_dist_add_l2", "reid_debug_flip_w",
                  "reid_debug_feed", "reid_debug_gem_neck", "reid_debug_gem_neck_fused", "reid_debug_gemm_f16", "reid_debug_knn_merge", "reid_debug_knn_wide", "reid_debug_knn_wide_eligible", "reid_debug_knn_wide_run", "reid_debug_layernorm", "reid_debug_linear", "reid_debug_linear_rows", "reid_debug_ln_linear", "reid_debug_maxpool", "reid_debug_mfma_bare", "reid_debug_mfma_shape", "reid_debug_norm_finish", "reid_debug_pil_resize", "reid_debug_post_norm", "reid_debug_resize_norm", "reid_debug_se_tail", "reid_debug_stem", "reid_debug_sibling_tail", "reid_debug_swin_conv1", "reid_debug_swin_conv1_mirror", "reid_debug_swin_crop_front", "reid_debug_swin_crop_front_mirror", "reid_debug_swin_descriptor", "reid_debug_swin_fuse", "reid_debug_swin_linear", "reid_debug_swin_merge", "reid_debug_swin_sfe", "reid_debug_swin_tail", "reid_debug_select_exp", "reid_debug_select_x3", "reid_debug_set_switch", "reid_debug_shift_mirror", "reid_debug_get_switch", "reid_debug_two_linear", "reid_debug_two_linear_ablate", "reid_debug_two_linear_form", "reid_debug_window_attn", "reid_debug_window_attn_cos")   # include/reid_hip_debug.h
 
 _lib = None

@@ -89,7 +89,7 @@ class SERes18IBN:
     arch = "seres18_ibn"
 
     def __init__(self, num_classes=751, loss="triplet", pretrained=False, use_gpu=True, seed=0, num_cams=6, cam_factor=-1.0,
-                 precision=None, hw_precision=None, hw_siblings=False, hw_ema=False, hw_f16=False, **_):
+                 precision=None, hw_precision=None, hw_siblings=False, hw_ema=False, hw_f16=False, hw_sib_f16=False, **_):
         if loss not in ("triplet", "softmax"):
             raise NotImplementedError                      # seres18_ibn(), SERes18_IBN.py:279-285
         self._mode = _precision.resolve(precision)         # "f16x3" unless the argument or $REID_PRECISION says otherwise (precision.py)
@@ -110,6 +110,14 @@ class SERes18IBN:
         if self._hw_f16 and hw_precision is not None:
             raise ValueError("hw_f16 and hw_precision both name the arithmetic of inputs of another size: give one of them, got hw_f16=%r "
                              "and hw_precision=%r" % (hw_f16, hw_precision))
+        # cares18_ibn / emares18_ibn only: True = inputs of another size run in fp16 storage with fp32 accumulation (Engine.set_hw_sib_f16
+        # around such a call); the keyword alone is enough, hw_siblings / hw_ema need not be given
+        self._hw_sib_f16 = bool(Engine.hw_sib_f16_value(hw_sib_f16))
+        if self._hw_sib_f16 and self.arch == "seres18_ibn":
+            raise ValueError("seres18_ibn has no hw_sib_f16 argument (cares18_ibn and emares18_ibn only; seres18_ibn: hw_f16)")
+        if self._hw_sib_f16 and (hw_precision is not None or self._hw_f16):
+            raise ValueError("hw_sib_f16 names the arithmetic of inputs of another size itself: give it without hw_precision and hw_f16, got "
+                             "hw_sib_f16=%r, hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
         self._hw_call = _HwClassCall(self) if hw == 2 else None
         self.num_classes = num_classes
         self.num_cams, self.cam_factor = num_cams, float(cam_factor)   # SERes18_IBN.py:193,198: cam_bias [num_cams,512] and its factor
@@ -218,7 +226,8 @@ class SERes18IBN:
             raise ValueError("expected [N,3,H,W] input, got %s" % (tuple(x.shape),))
         size = check_hw(tuple(x.shape[2:]))
         any_size = size != (IMG_H, IMG_W)
-        if any_size and self.arch != "seres18_ibn" and not getattr(self, "_hw_siblings", False) and not getattr(self, "_hw_ema", False):
+        if any_size and self.arch != "seres18_ibn" and not getattr(self, "_hw_siblings", False) and not getattr(self, "_hw_ema", False) \
+                and not getattr(self, "_hw_sib_f16", False):
             raise ValueError("%s runs at [N,3,%d,%d] only (other sizes: seres18_ibn), got %s" % (self.arch, IMG_H, IMG_W, tuple(x.shape)))
         # another size runs the any-size forward: this CALL runs in exact fp32 (mode 0) or, with hw_precision="f16x3", in the fp32-class
         # arithmetic (reid_ctx_set_hw_precision 2 around the call); the model keeps its own mode and the engine gets its settings back
@@ -250,6 +259,14 @@ class SERes18IBN:
                     with e.hw_f16_scope(True):
                         return fn(e)
                 return inner_f16(scoped)
+        if any_size and getattr(self, "_hw_sib_f16", False):      # a sibling in fp16 storage: likewise with the engine's hw_sib_f16
+            inner_sib = run
+
+            def run(fn):
+                def scoped(e):
+                    with e.hw_sib_f16_scope(True):
+                        return fn(e)
+                return inner_sib(scoped)
         if is_torch and x.is_cuda:
             if x.device.index != self._device:
                 self.to(x.device.index)
@@ -370,7 +387,9 @@ class SwinT:
     _arch = "swin"            # precision.run: which of the shared engine's two weight sets this object owns
 
     def __init__(self, num_classes=751, loss="softmax", pretrained=False, use_gpu=True, seed=0, camera=0, sequence=0, side_info=True,
-                 side_info_coeff=1.5, precision=None, version="v1", **_):
+                 side_info_coeff=1.5, precision=None, version="v1", hw_sib_f16=False, **_):
+        if Engine.hw_sib_f16_value(hw_sib_f16):
+            raise ValueError("swin_transformer has no hw_sib_f16 argument (cares18_ibn and emares18_ibn only)")
         if version not in synth.SWIN_VERSIONS:
             raise ValueError("swin_t: version must be 'v1' or 'v2', got %r" % (version,))
         self.version = version

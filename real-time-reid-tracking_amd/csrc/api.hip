@@ -5,6 +5,7 @@
 #include "anysize.h"
 #include "anysize_x3.h"
 #include "anysize_f16.h"
+#include "anysize_sib_f16.h"
 #include "distmat_x3.h"
 #include "select_x3.h"
 #include "anysize_front.h"
@@ -244,6 +245,19 @@ extern "C" int reid_ctx_set_hw_f16(reid_ctx* ctx, int on) {
         return REID_ERR_ARG;
     }
     ctx->hw_f16 = on;
+    return REID_OK;
+}
+
+extern "C" int reid_ctx_set_hw_sib_f16(reid_ctx* ctx, int on) {
+    ARG_CHECK(ctx);
+    CTX_GUARD(ctx);
+    if (on != 0 && on != 1) {
+        reid_set_error("reid_ctx_set_hw_sib_f16: the value must be 0 (other input sizes run cares18_ibn / emares18_ibn as "
+                       "reid_ctx_set_hw_siblings, reid_ctx_set_hw_ema and reid_ctx_set_hw_precision say) or 1 (they run them in fp16 storage "
+                       "with fp32 accumulation)");
+        return REID_ERR_ARG;
+    }
+    ctx->hw_sib_f16 = on;
     return REID_OK;
 }
 
@@ -1529,6 +1543,16 @@ static struct AnysizeF16Lib : SideLib {
     SIDE_FN(gem, anysize_f16_gem);
 } anysize_f16;
 
+// ... and the TripletAttention / EMA block tails of cares18_ibn / emares18_ibn on that forward's f16 maps (reid_ctx_set_hw_sib_f16 1):
+// anysize_sib_f16.h
+static struct AnysizeSibF16Lib : SideLib {
+    AnysizeSibF16Lib() : SideLib("libreid_hip_anysize_sib_f16.so", "CARes18-IBN / EMARes18-IBN at another input size in the fp16-storage arithmetic need") {}
+    SIDE_FN(ca_ws_bytes, anysize_sib_f16_ca_workspace_bytes);
+    SIDE_FN(ca_tail, anysize_sib_f16_ca_tail);
+    SIDE_FN(ema_ws_bytes, anysize_sib_f16_ema_workspace_bytes);
+    SIDE_FN(ema_tail, anysize_sib_f16_ema_tail);
+} anysize_sib_f16;
+
 // ... and its front end from uint8 windows in one kernel (reid_frame_submit_hw, reid_embed_frame_u8_hw): anysize_front.h
 static struct AnysizeFrontLib : SideLib {
     AnysizeFrontLib() : SideLib("libreid_hip_anysize_front.so", "the frame pipeline of ResNet18-IBN-SE at another input size needs") {}
@@ -1556,6 +1580,10 @@ int se_any_pass(const reid_ctx* ctx, int h, int w) {
     return (int)(p < 1 ? 1 : (p > 4096 ? 4096 : p));
 }
 
+// the any-size forward runs in fp16 storage: reid_ctx_set_hw_f16 1 with seres18_ibn loaded (with a sibling loaded se_any_ready refuses the
+// call), or reid_ctx_set_hw_sib_f16 1 with a sibling loaded
+static bool any_f16_route(const reid_ctx* ctx) { return ctx->se18.arch == 0 ? ctx->hw_f16 != 0 : (ctx->hw_sib_f16 != 0 || ctx->hw_f16 != 0); }
+
 int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
     if (h < 32 || h > 512 || w < 32 || w > 512) {
         reid_set_error("%s: input size %d x %d, height and width must each be in [32, 512]", who, h, w);
@@ -1568,6 +1596,11 @@ int se_any_ready(reid_ctx* ctx, int h, int w, const char* who) {
         return REID_ERR_STATE;
     }
     static const char* const kArch[3] = {"seres18_ibn", "cares18_ibn", "emares18_ibn"};
+    if (wt.arch != 0 && ctx->hw_sib_f16) {   // the siblings' setting names the arithmetic itself: no other setting is looked at
+        REID_TRY(anysize.open());
+        REID_TRY(anysize_f16.open());
+        return anysize_sib_f16.open();
+    }
     if (ctx->hw_f16) {   // the setting names the arithmetic itself: neither the mode nor hw_precision is looked at
         if (wt.arch != 0) {
             reid_set_error("%s: input size %d x %d with reid_ctx_set_hw_f16 1: loaded architecture %s; the fp16-storage any-size forward serves "
@@ -1607,7 +1640,7 @@ int se_any_front_ready(reid_ctx* ctx, int h, int w, const float** mean_std6, con
         }
         return REID_OK;
     }
-    if (ctx->hw_f16) return REID_OK;   // its passes go through resize + normalise and the f16 stem: the fused fp32 front end is not needed
+    if (any_f16_route(ctx)) return REID_OK;   // its passes go through resize + normalise and the f16 stem: the fused fp32 front end is not needed
     return anysize_front_lib.open();
 }
 
@@ -1806,6 +1839,47 @@ int launch_any_se_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc,
     return anysize_f16.status(e, anysize_f16.se_tail);
 }
 
+int launch_any_ca_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int H, int W, int C, const float* prm, _Float16* out,
+                           const float** maps_out, const float** gates_out) {
+    REID_TRY(anysize_sib_f16.open());
+    const size_t bytes = anysize_sib_f16.ca_ws_bytes(n, H, W, C);
+    if (!bytes) {
+        reid_set_error("%s: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", anysize_sib_f16.file, H, W,
+                       C, n);
+        return REID_ERR_ARG;
+    }
+    void* ws;
+    REID_TRY(ctx_ws(ctx, "any.ca", bytes, &ws));
+    prof_begin(ctx, REID_K_ELEMENTWISE, 0, (double)n * H * W * C * 10.0);
+    const hipError_t e = anysize_sib_f16.ca_tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
+    prof_end(ctx);
+    REID_TRY(anysize_sib_f16.status(e, anysize_sib_f16.ca_tail));
+    if (maps_out) *maps_out = (const float*)ws;
+    if (gates_out) *gates_out = (const float*)ws + (size_t)n * 2 * ((size_t)H * W + (size_t)C * W + (size_t)H * C);
+    return REID_OK;
+}
+
+int launch_any_ema_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int H, int W, int C, const float* prm, _Float16* out,
+                            const float** sig_out, const float** small_out) {
+    REID_TRY(anysize_sib_f16.open());
+    const size_t bytes = anysize_sib_f16.ema_ws_bytes(n, H, W, C);
+    if (!bytes) {
+        reid_set_error("%s: a map of %d x %d x %d (%d images) is outside 2 .. 128 per side, c in {64, 128, 256, 512}", anysize_sib_f16.file, H, W,
+                       C, n);
+        return REID_ERR_ARG;
+    }
+    void* ws;
+    REID_TRY(ctx_ws(ctx, "any.ema", bytes, &ws));
+    prof_begin(ctx, REID_K_ELEMENTWISE, (double)n * H * W * C * C / 32.0 * 36.0, (double)n * H * W * C * 10.0);
+    const hipError_t e = anysize_sib_f16.ema_tail(ctx->stream, y, sc, n, H, W, C, prm, ws, out);
+    prof_end(ctx);
+    REID_TRY(anysize_sib_f16.status(e, anysize_sib_f16.ema_tail));
+    const float* sig = (const float*)((const double*)ws + (size_t)n * anysize_ema_slabs(H, W, C) * 3 * C);
+    if (sig_out) *sig_out = sig;
+    if (small_out) *small_out = sig + (size_t)n * (H + W) * C;
+    return REID_OK;
+}
+
 int launch_any_gem_f16(reid_ctx* ctx, const _Float16* x, int n, int hw, int c, const float* p, const float* scale, const float* shift,
                        float* gem_out, float* emb) {
     REID_TRY(anysize_f16.open());
@@ -1860,6 +1934,9 @@ struct AnyF16 {
         return launch_any_norm_f16(ctx, x, n, hw, c, half, in_gamma, in_beta);
     }
     int tail(reid_ctx* ctx, const Se18Block& k, const T* y, const T* shortcut, int n, int Ho, int Wo, T* out) const {
+        const int arch = ctx->se18.arch;   // the siblings: reid_ctx_set_hw_sib_f16 1 (se_any_ready), tails of libreid_hip_anysize_sib_f16.so
+        if (arch == 1) return launch_any_ca_tail_f16(ctx, y, shortcut, n, Ho, Wo, k.c, k.ta, out);
+        if (arch == 2) return launch_any_ema_tail_f16(ctx, y, shortcut, n, Ho, Wo, k.c, k.ema, out);
         return launch_any_se_tail_f16(ctx, y, shortcut, n, Ho * Wo, k.c, k.mid, k.se_w1, k.se_w2, out, nullptr);
     }
     int gem(reid_ctx* ctx, const T* x, int n, int hw, int c, const float* p, const float* scale, const float* shift, float* gem_out, float* emb) const {
@@ -1970,8 +2047,8 @@ static int seres18_trunk_any(reid_ctx* ctx, const AnyBufs<float>& b, int n, floa
 // x: fp32 NHWC [n][h][w][3] on the device
 static int seres18_forward_any(reid_ctx* ctx, const float* x, int n, int h, int w, float* d_emb, float* d_logits) {
     const Se18Weights& wt = ctx->se18;
-    if (ctx->hw_f16) {   // stem and max-pool from libreid_hip_anysize_f16.so too, then the walk of seres18_trunk_any
-        ARG_CHECK(wt.arch == 0);
+    if (any_f16_route(ctx)) {   // stem and max-pool from libreid_hip_anysize_f16.so too, then the walk of seres18_trunk_any
+        ARG_CHECK(wt.arch == 0 || ctx->hw_sib_f16);
         AnyBufs<_Float16> b;
         REID_TRY(any_bufs<AnyF16>(ctx, n, h, w, true, b));
         REID_TRY(launch_any_stem_f16(ctx, x, n, h, w, wt.h(wt.stem_w), wt.stem_scale, wt.stem_shift, b.stem));
@@ -2004,8 +2081,8 @@ constexpr long long ANY_FRONT_MAX_STEM_PIXELS = 65536;
 static int se_any_run_windows(reid_ctx* ctx, const RaggedSrc& src, int i, int m, int h, int w, const float* mean_std6, float* d_emb, float* d_log,
                               bool front = false) {
     const bool small = (long long)m * ((h - 1) / 2 + 1) * ((w - 1) / 2 + 1) <= ANY_FRONT_MAX_STEM_PIXELS;
-    // reid_ctx_set_hw_f16 1: the fused kernel's pooled map is fp32, so such a pass takes resize + normalise and the f16 stem
-    if (front && !ctx->hw_f16 && (ctx->any_front == 1 || (ctx->any_front == 2 && small)) && !ctx->debug_keep) {
+    // fp16 storage (any_f16_route): the fused kernel's pooled map is fp32, so such a pass takes resize + normalise and the f16 stem
+    if (front && !any_f16_route(ctx) && (ctx->any_front == 1 || (ctx->any_front == 2 && small)) && !ctx->debug_keep) {
         const Se18Weights& wt = ctx->se18;
         AnyBufs<float> b;
         REID_TRY(any_bufs<AnyF32>(ctx, m, h, w, false, b));

@@ -980,6 +980,56 @@ extern "C" int reid_debug_any_se_tail_f16(reid_ctx* ctx, int n, int hw, int c, i
     return ctx_fault_status(ctx);
 }
 
+// The TripletAttention / EMA tails of libreid_hip_anysize_sib_f16.so (anysize_sib_f16.h; tests/test_gpu_anysize_sib_f16.py) through
+// launch_any_ca_tail_f16 / launch_any_ema_tail_f16, the functions the any-size forward calls under reid_ctx_set_hw_sib_f16 1.  The workspace
+// is set to 0xff bytes with one guard pixel behind it before the launch, as out is; the statistics come back as the fp32 harnesses
+// (reid_debug_any_ca_tail, reid_debug_any_ema_tail) return them.
+extern "C" int reid_debug_any_ca_tail_f16(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const uint16_t* y,
+                                          const uint16_t* shortcut, uint16_t* out, float* maps, float* gates) {
+    ARG_CHECK(ctx && n >= 1 && h >= 1 && w >= 1 && c >= 64 && prm && y && shortcut && out);
+    CTX_ENTER(ctx);
+    const size_t ny = (size_t)n * h * w * c, per = (size_t)h * w + (size_t)c * w + (size_t)h * c;
+    float *dprm, *dws;
+    uint16_t *dy, *dsc, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", prm, (size_t)300, &dprm));
+    REID_TRY(dbg_upload(ctx, "dbgh.x", y, ny, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgh.res", shortcut, ny, &dsc));
+    REID_TRY(dbg_output(ctx, "dbgh.out", ny + c, &dout));
+    REID_TRY(dbg_output(ctx, "any.ca", (size_t)n * 3 * per + c, &dws));   // the workspace launch_any_ca_tail_f16 takes: grown first, so it is this one
+    const float *dmaps, *dgates;
+    REID_TRY(launch_any_ca_tail_f16(ctx, (const _Float16*)dy, (const _Float16*)dsc, n, h, w, c, dprm, (_Float16*)dout, &dmaps, &dgates));
+    ARG_CHECK(dmaps == dws && dgates == dws + (size_t)n * 2 * per);
+    REID_TRY(dbg_download(ctx, out, dout, ny + c));
+    REID_TRY(dbg_download(ctx, maps, dmaps, (size_t)n * 2 * per));
+    REID_TRY(dbg_download(ctx, gates, dgates, (size_t)n * per + c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
+extern "C" int reid_debug_any_ema_tail_f16(reid_ctx* ctx, int n, int h, int w, int c, const float* prm, const uint16_t* y,
+                                           const uint16_t* shortcut, uint16_t* out, float* sig, float* small) {
+    ARG_CHECK(ctx && n >= 1 && h >= 1 && w >= 1 && c >= 64 && c <= 512 && c % 32 == 0 && prm && y && shortcut && out);
+    CTX_ENTER(ctx);
+    const int cg = c / 32;
+    const size_t ny = (size_t)n * h * w * c, nsig = (size_t)n * (h + w) * c, nsmall = (size_t)n * 4 * c;
+    const size_t npart = (size_t)n * anysize_ema_slabs(h, w, c) * 3 * c;   // doubles
+    float *dprm, *dws;
+    uint16_t *dy, *dsc, *dout;
+    REID_TRY(dbg_upload(ctx, "dbgt.w1", prm, (size_t)cg * cg * 10 + 4 * cg, &dprm));
+    REID_TRY(dbg_upload(ctx, "dbgh.x", y, ny, &dy));
+    REID_TRY(dbg_upload(ctx, "dbgh.res", shortcut, ny, &dsc));
+    REID_TRY(dbg_output(ctx, "dbgh.out", ny + c, &dout));
+    REID_TRY(dbg_output(ctx, "any.ema", 2 * npart + nsig + nsmall + c, &dws));   // the workspace launch_any_ema_tail_f16 takes: grown first, so it is this one
+    const float *dsig, *dsmall;
+    REID_TRY(launch_any_ema_tail_f16(ctx, (const _Float16*)dy, (const _Float16*)dsc, n, h, w, c, dprm, (_Float16*)dout, &dsig, &dsmall));
+    ARG_CHECK(dsig == dws + 2 * npart && dsmall == dsig + nsig);
+    REID_TRY(dbg_download(ctx, out, dout, ny + c));
+    REID_TRY(dbg_download(ctx, sig, dsig, nsig));
+    REID_TRY(dbg_download(ctx, small, dsmall, nsmall + c));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx_fault_status(ctx);
+}
+
 extern "C" int reid_debug_any_gem_f16(reid_ctx* ctx, int n, int hw, int c, float p, const uint16_t* x, const float* scale, const float* shift,
                                       float* gem_out, float* emb) {
     ARG_CHECK(ctx && n >= 1 && hw >= 1 && c >= 64 && x && scale && shift && emb);

@@ -519,6 +519,8 @@ struct reid_ctx {
     int hw_ema = 0;          // reid_ctx_set_hw_ema: 1 = a loaded emares18_ibn runs at other sizes too (libreid_hip_anysize_ema.so)
     int hw_f16 = 0;          // reid_ctx_set_hw_f16: 1 = a loaded seres18_ibn runs at other sizes in fp16 storage with fp32 accumulation, whatever
                              // the mode and hw_precision (libreid_hip_anysize_f16.so)
+    int hw_sib_f16 = 0;      // reid_ctx_set_hw_sib_f16: 1 = a loaded cares18_ibn / emares18_ibn runs at other sizes in fp16 storage with fp32
+                             // accumulation, whatever the mode and the other hw_* settings (libreid_hip_anysize_f16.so + ..._anysize_sib_f16.so)
     int any_f16_form = 0;    // the tile form the last fp16-storage any-size convolution launched (anysize_f16.h), written on the host only
     int any_ema = 1;         // libreid_hip_debug.so switch: the EMA tail of the any-size trunk: 1 = libreid_hip_anysize_ema.so, 0 =
                              // launch_ema_tail (attention_f32.hip; refuses a map whose slab does not fit LDS), for A/B timing in one process
@@ -833,7 +835,8 @@ struct SideFn<R (*)(A...)> : SideSym {
 // a precision mode other than 0 while reid_ctx_set_hw_precision is -1 (REID_ERR_ARG naming both), libreid_hip_anysize.so and, at
 // hw_precision 2, libreid_hip_anysize_x3.so (REID_ERR_STATE).  With reid_ctx_set_hw_f16 1 instead: an architecture other than seres18_ibn
 // (REID_ERR_ARG naming it, whatever hw_siblings / hw_ema), libreid_hip_anysize.so and libreid_hip_anysize_f16.so (REID_ERR_STATE); the mode
-// and hw_precision are not looked at.  se_any_pass: images per pass, the
+// and hw_precision are not looked at.  With reid_ctx_set_hw_sib_f16 1 and a sibling loaded, before all of these: libreid_hip_anysize.so,
+// libreid_hip_anysize_f16.so and libreid_hip_anysize_sib_f16.so (REID_ERR_STATE), no other setting is looked at.  se_any_pass: images per pass, the
 // context's chunk scaled by 256 * 128 / (h * w) and clamped to 1 .. 4096.  se_any_run_nchw: one pass from fp32 NCHW [m][3][h][w] on the
 // device (mirror: the horizontally flipped view); se_any_run_windows: from uploaded uint8 windows through the cv2-style resize.
 struct RaggedSrc;
@@ -889,6 +892,14 @@ int launch_any_se_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc,
                            const float* w2t, _Float16* out, float* gate_out);
 int launch_any_gem_f16(reid_ctx* ctx, const _Float16* x, int n, int hw, int c, const float* p, const float* scale, const float* shift,
                        float* gem_out, float* emb);
+// the TripletAttention / EMA tails of the any-size trunk on f16 maps (cares18_ibn / emares18_ibn with reid_ctx_set_hw_sib_f16 1;
+// anysize_sib_f16.h): launch_any_ca_tail / launch_any_ema_tail with f16 y, shortcut and out; the workspaces keep their names ("any.ca",
+// "any.ema"), sizes and layouts, so maps_out / gates_out and sig_out / small_out mean what they mean there.  The forward and the
+// reid_debug_any_ca_tail_f16 / reid_debug_any_ema_tail_f16 harnesses call these functions.
+int launch_any_ca_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int H, int W, int C, const float* prm, _Float16* out,
+                           const float** maps_out = nullptr, const float** gates_out = nullptr);
+int launch_any_ema_tail_f16(reid_ctx* ctx, const _Float16* y, const _Float16* sc, int n, int H, int W, int C, const float* prm, _Float16* out,
+                            const float** sig_out = nullptr, const float** small_out = nullptr);
 void prof_begin(reid_ctx* ctx, int kind, double flops, double bytes);
 void prof_end(reid_ctx* ctx);
 

@@ -332,6 +332,46 @@ class Engine:
                     self.set_hw_f16(prev)
         return scope()
 
+    @staticmethod
+    def hw_sib_f16_value(v):
+        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_sib_f16); ValueError otherwise, before any device call."""
+        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+            return int(v)
+        raise ValueError("hw_sib_f16 must be False / 0 (other input sizes run cares18_ibn / emares18_ibn as hw_siblings, hw_ema and "
+                         "hw_precision say) or True / 1 (they run them in fp16 storage), got %r" % (v,))
+
+    def set_hw_sib_f16(self, on):
+        """cares18_ibn / emares18_ibn at input sizes other than 256 x 128 in fp16 storage with fp32 accumulation
+        (reid_ctx_set_hw_sib_f16): False (default) = set_hw_siblings, set_hw_ema, set_hw_precision and the mode decide (and set_hw_f16
+        refuses them), True = such inputs run through libreid_hip_anysize_f16.so with the block tails of libreid_hip_anysize_sib_f16.so
+        whatever those settings are; they keep their values.  seres18_ibn and 256 x 128 are not affected."""
+        v = Engine.hw_sib_f16_value(on)
+        check(self.lib.reid_ctx_set_hw_sib_f16(self.h, v))
+        self._hw_sib_f16 = bool(v)
+
+    @property
+    def hw_sib_f16(self):
+        """What set_hw_sib_f16 set last (the library's default is False)."""
+        return getattr(self, "_hw_sib_f16", False)
+
+    def hw_sib_f16_scope(self, on):
+        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            if on is None:
+                yield self
+                return
+            prev = self.hw_sib_f16
+            self.set_hw_sib_f16(on)
+            try:
+                yield self
+            finally:
+                if self.hw_sib_f16 != prev:
+                    self.set_hw_sib_f16(prev)
+        return scope()
+
     def set_side_index(self, index):
         """Camera (ResNet18-IBN-SE: SERes18_IBN.py:269-270) or view (Swin: swin_transformer.py:301-302) index of every image of
         the following embed call; ``None`` / empty clears."""
@@ -1716,6 +1756,39 @@ class Engine:
         check(_ffi.debug_lib().reid_debug_any_se_tail_f16(self.h, n, hw, c, w1.shape[0], _ptr(w1), _ptr(w2t), _ptr(y), _ptr(shortcut),
                                                           int(bool(alias)), _ptr(out), _ptr(gate)))
         return out, gate
+
+    def debug_any_ca_tail_f16(self, y, shortcut, prm, out=None):
+        """The TripletAttention tail of libreid_hip_anysize_sib_f16.so through the any-size forward's launcher
+        (reid_debug_any_ca_tail_f16): y, shortcut float16 [n, h, w, c], prm [3, 100].  Returns (out float16 [n h w c + c], maps [n, 2 per],
+        gates [n per + c]) as debug_any_ca_tail does, guards included.  ``out``: a float16 buffer of that size to write into."""
+        y, shortcut, prm = _f16(y), _f16(shortcut), _f32(prm)
+        n, h, w, c = y.shape
+        if shortcut.shape != y.shape or prm.size != 300 or (out is not None and (out.dtype != np.float16 or out.size != y.size + c)):
+            raise ValueError("debug_any_ca_tail_f16: operand shapes")
+        per = h * w + c * w + h * c
+        out = np.empty(y.size + c, np.float16) if out is None else out
+        maps = np.empty((n, 2 * per), np.float32)
+        gates = np.empty(n * per + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_ca_tail_f16(self.h, n, h, w, c, _ptr(prm), _ptr(y), _ptr(shortcut), _ptr(out), _ptr(maps),
+                                                          _ptr(gates)))
+        return out, maps, gates
+
+    def debug_any_ema_tail_f16(self, y, shortcut, prm, out=None):
+        """The EMA tail of libreid_hip_anysize_sib_f16.so through the any-size forward's launcher (reid_debug_any_ema_tail_f16): y,
+        shortcut float16 [n, h, w, c], prm as debug_any_ema_tail takes it.  Returns (out float16 [n h w c + c], sig [n, h + w, c], small
+        [n 4 c + c]) as debug_any_ema_tail does, guards included.  ``out``: a float16 buffer of that size to write into."""
+        y, shortcut, prm = _f16(y), _f16(shortcut), _f32(prm)
+        n, h, w, c = y.shape
+        cg = c // 32
+        if shortcut.shape != y.shape or c % 32 or prm.size != cg * cg * 10 + 4 * cg or \
+                (out is not None and (out.dtype != np.float16 or out.size != y.size + c)):
+            raise ValueError("debug_any_ema_tail_f16: operand shapes")
+        out = np.empty(y.size + c, np.float16) if out is None else out
+        sig = np.empty((n, h + w, c), np.float32)
+        small = np.empty(n * 4 * c + c, np.float32)
+        check(_ffi.debug_lib().reid_debug_any_ema_tail_f16(self.h, n, h, w, c, _ptr(prm), _ptr(y), _ptr(shortcut), _ptr(out), _ptr(sig),
+                                                           _ptr(small)))
+        return out, sig, small
 
     def debug_any_gem_f16(self, x, p, scale, shift):
         x, scale, shift = _f16(x), _f32(scale), _f32(shift)

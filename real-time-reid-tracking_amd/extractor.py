@@ -35,7 +35,7 @@ def pack_checkpoint(state_dict):
 
 
 class Extractor(object):
-    def __init__(self, model_path, use_cuda=True, device=0, precision=None, size=None, hw_siblings=False, hw_ema=False, hw_f16=False):
+    def __init__(self, model_path, use_cuda=True, device=0, precision=None, size=None, hw_siblings=False, hw_ema=False, hw_f16=False, hw_sib_f16=False):
         """``Extractor(model_path, use_cuda=True)`` as feature_extractor.py:15-29.  ``precision`` (keyword, not in the reference):
         "f16x3" (default; $REID_PRECISION overrides the default) / "f32" / "f16" - see precision.py; a checkpoint the fp32-class
         arithmetic cannot represent runs in exact fp32, with one log line.  ``size`` (keyword, (W, H) like ``self.size``): the size
@@ -49,7 +49,9 @@ class Extractor(object):
         around every call (the EMA tail of libreid_hip_anysize_ema.so); without it emares18_ibn has no other size.  ``hw_f16=True``
         (keyword, seres18_ibn checkpoints only): at such a size the crops run in fp16 storage with fp32 accumulation -
         Engine.set_hw_f16(True) around every call (libreid_hip_anysize_f16.so); it names the arithmetic itself, so ``precision`` need not
-        be given, and whatever ``precision`` is applies at (128, 256) only."""
+        be given, and whatever ``precision`` is applies at (128, 256) only.  ``hw_sib_f16=True`` (keyword, cares18_ibn / emares18_ibn
+        checkpoints only, without ``hw_f16``): the same for the siblings - Engine.set_hw_sib_f16(True) around every call
+        (libreid_hip_anysize_sib_f16.so); the keyword alone is enough, ``hw_siblings`` / ``hw_ema`` and ``precision`` need not be given."""
         if not use_cuda:
             raise RuntimeError("Extractor: the MI355X engine has no CPU path (use_cuda=False is not supported)")
         self.device = "cuda"
@@ -58,6 +60,10 @@ class Extractor(object):
         self._hw_siblings = bool(_Engine.hw_siblings_value(hw_siblings))      # a bad value raises here, before any device call
         self._hw_ema = bool(_Engine.hw_ema_value(hw_ema))
         self._hw_f16 = bool(_Engine.hw_f16_value(hw_f16))
+        self._hw_sib_f16 = bool(_Engine.hw_sib_f16_value(hw_sib_f16))
+        if self._hw_sib_f16 and self._hw_f16:
+            raise ValueError("Extractor: hw_sib_f16 and hw_f16 name the fp16-storage arithmetic of different checkpoints: give one of them, "
+                             "got hw_sib_f16=%r and hw_f16=%r" % (hw_sib_f16, hw_f16))
         if isinstance(model_path, dict):
             state_dict = model_path            # already-loaded state_dict (tests, benchmarks)
         else:
@@ -73,6 +79,9 @@ class Extractor(object):
         if self._hw_f16 and (self._arch == "swin" or self.info.get("arch") != "seres18_ibn"):
             raise ValueError("Extractor: hw_f16 belongs to seres18_ibn checkpoints (the fp16-storage any-size forward serves them only), "
                              "got %s" % ("swin" if self._arch == "swin" else self.info.get("arch"),))
+        if self._hw_sib_f16 and (self._arch == "swin" or self.info.get("arch") not in ("cares18_ibn", "emares18_ibn")):
+            raise ValueError("Extractor: hw_sib_f16 belongs to cares18_ibn / emares18_ibn checkpoints (seres18_ibn: hw_f16), got %s"
+                             % ("swin" if self._arch == "swin" else self.info.get("arch"),))
         if self._arch == "swin":
             self.size = tuple(int(v) for v in (size or (224, 224)))           # (W, H)
             Engine._swin_crop_args(self.size[::-1], None)
@@ -84,8 +93,8 @@ class Extractor(object):
                 sized = ("seres18_ibn", "cares18_ibn") if self._hw_siblings else ("seres18_ibn",)
                 if self._hw_ema:
                     sized = sized + ("emares18_ibn",)
-                if self._hw_f16:
-                    pass                       # seres18_ibn (checked above), and the keyword names the arithmetic of this size itself
+                if self._hw_f16 or self._hw_sib_f16:
+                    pass                       # the architecture was checked above, and the keyword names the arithmetic of this size itself
                 elif self.info.get("arch") not in sized or precision is None or self._mode == _precision.F16:
                     raise ValueError("Extractor: at a size other than (W, H) = (128, 256) the ResNet18-IBN family runs seres18_ibn "
                                      "checkpoints in exact fp32 (precision=\"f32\") or fp32-class (precision=\"f16x3\"), asked for by "
@@ -100,7 +109,7 @@ class Extractor(object):
         where = model_path if not isinstance(model_path, dict) else "<state_dict>"
         if self._arch != "swin" and self.size != (128, 256):
             logger.info("Loading weights from {}... Done! (size (W, H) = {}: {})".format(
-                where, self.size, "fp16 storage" if self._hw_f16 else
+                where, self.size, "fp16 storage" if self._hw_f16 or self._hw_sib_f16 else
                 "fp32-class f16x3" if self._mode == _precision.F32_CLASS else "exact fp32"))
         else:
             logger.info("Loading weights from {}... Done!".format(where))
@@ -135,9 +144,10 @@ class Extractor(object):
             def scoped(eng):
                 sib = True if self._hw_siblings and self.info.get("arch") == "cares18_ibn" else None
                 ema = True if self._hw_ema and self.info.get("arch") == "emares18_ibn" else None
-                x3 = 2 if self._mode == _precision.F32_CLASS and not self._hw_f16 else None
+                x3 = 2 if self._mode == _precision.F32_CLASS and not self._hw_f16 and not self._hw_sib_f16 else None
                 with eng.hw_precision_scope(x3), eng.hw_siblings_scope(sib), eng.hw_ema_scope(ema), \
-                        (eng.hw_f16_scope(True) if self._hw_f16 else contextlib.nullcontext()):
+                        (eng.hw_f16_scope(True) if self._hw_f16 else contextlib.nullcontext()), \
+                        (eng.hw_sib_f16_scope(True) if self._hw_sib_f16 else contextlib.nullcontext()):
                     return fn(eng)
             return _precision.run(self, self.net, "Extractor", scoped)
         return _precision.run(self, self.net, "Extractor", fn)

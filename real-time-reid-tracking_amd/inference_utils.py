@@ -39,13 +39,15 @@ def smooth_tracklets(embeddings, seqs, indices_valid, device=0):
     return out
 
 
-def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=None, strong_offsets=None, pad=10, hw_f16=False):
+def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=None, strong_offsets=None, pad=10, hw_f16=False, hw_sib_f16=False):
     """float [n,3,H,W] after the caller's transform ((256, 128), or sides in 32 .. 512 for seres18_ibn weights in exact fp32), or a list
     of uint8 [h,w,3] images of any sizes, which the device resizes as PIL does - to ``size`` = (H, W), default (256, 128); the script's
     VeRi geometry is (224, int(ratio * 224)) - and normalises with the ImageNet values (Engine.descriptor_images_u8).
     ``hw_precision``: the arithmetic of another size for this call (Engine.set_hw_precision: "f32" / "f16x3"), restored afterwards; None
     leaves the engine's setting alone.  ``hw_f16=True`` instead (both together are a ValueError naming them): another size runs
-    seres18_ibn in fp16 storage with fp32 accumulation for this call (Engine.set_hw_f16), restored afterwards.
+    seres18_ibn in fp16 storage with fp32 accumulation for this call (Engine.set_hw_f16), restored afterwards.  ``hw_sib_f16=True``
+    (without ``hw_precision`` and ``hw_f16``: a ValueError naming them otherwise): the same for loaded cares18_ibn / emares18_ibn weights
+    (Engine.set_hw_sib_f16), restored afterwards.
     ``strong_offsets``: int [n, 2] of (top, left) per image (data_transforms.strong_inference_offsets) - the second view becomes the
     script's strong_inference one, the mirror shifted by (top - pad, left - pad) over a black border (reid/data_transforms.py:130-191;
     Engine.descriptor_f32_nchw_shift / descriptor_images_u8_shift; needs ``flip``).  None is today's call and bits."""
@@ -57,6 +59,12 @@ def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=Non
             raise ValueError("strong_offsets shift the mirrored view: flip must be on")
         strong_offsets, pad = Engine.check_shift(strong_offsets, len(images), pad)   # a bad value raises here, before any device call
     from .engine import Engine as _Engine
+    if _Engine.hw_sib_f16_value(hw_sib_f16):         # a bad value raises here, before any device call
+        if hw_precision is not None or _Engine.hw_f16_value(hw_f16):
+            raise ValueError("hw_sib_f16 names the arithmetic of another size itself: give it without hw_precision and hw_f16, got "
+                             "hw_sib_f16=%r, hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
+        with get_engine(device).hw_sib_f16_scope(True):
+            return extract_descriptors(images, flip, device, size, strong_offsets=strong_offsets, pad=pad)
     if _Engine.hw_f16_value(hw_f16):                 # a bad value raises here, before any device call
         if hw_precision is not None:
             raise ValueError("hw_f16 and hw_precision both name the arithmetic of another size: give one of them, got hw_f16=%r and "

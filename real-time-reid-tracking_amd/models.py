@@ -18,7 +18,7 @@ def show_avai_models():
     print(list(__model_factory.keys()))
 
 
-def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True, precision=None, version=None, hw_precision=None, hw_siblings=None, hw_ema=None, hw_f16=None):
+def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True, precision=None, version=None, hw_precision=None, hw_siblings=None, hw_ema=None, hw_f16=None, hw_sib_f16=None):
     """Same signature, same ``KeyError`` text as models/__init__.py:93-121; constructors are called with
     (num_classes, loss, pretrained, use_gpu).  ``precision`` (keyword, this engine's addition): the arithmetic the model runs
     in - None = $REID_PRECISION, else "f16x3", the mode bench.py reports (precision.py).  ``version`` (keyword): "v1" / "v2" of
@@ -28,7 +28,9 @@ def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True
     ``hw_siblings`` (keyword): True lets 'cares18_ibn' take inputs other than 256 x 128 too (backbone.CARes18IBN, Engine.set_hw_siblings);
     every other name takes none.  ``hw_ema`` (keyword): the same for 'emares18_ibn' (backbone.EMARes18IBN, Engine.set_hw_ema).
     ``hw_f16`` (keyword): True runs 'seres18_ibn' at inputs other than 256 x 128 in fp16 storage with fp32 accumulation (backbone.SERes18IBN,
-    Engine.set_hw_f16); every other name takes none."""
+    Engine.set_hw_f16); every other name takes none.  ``hw_sib_f16`` (keyword): True runs 'cares18_ibn' / 'emares18_ibn' at inputs other than
+    256 x 128 in fp16 storage with fp32 accumulation (Engine.set_hw_sib_f16; the keyword alone is enough, and it goes without ``hw_precision``
+    and ``hw_f16``); every other name takes none."""
     avai_models = list(__model_factory.keys())
     if name not in avai_models:
         raise KeyError('Unknown model: {}. Must be one of {}'.format(name, avai_models))
@@ -53,4 +55,8 @@ def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True
         if name != 'seres18_ibn':
             raise ValueError("model '{}' has no hw_f16 argument".format(name))
         extra['hw_f16'] = hw_f16
+    if hw_sib_f16 is not None:
+        if name not in ('cares18_ibn', 'emares18_ibn'):
+            raise ValueError("model '{}' has no hw_sib_f16 argument".format(name))
+        extra['hw_sib_f16'] = hw_sib_f16
     return __model_factory[name](num_classes=num_classes, loss=loss, pretrained=pretrained, use_gpu=use_gpu, precision=precision, **extra)

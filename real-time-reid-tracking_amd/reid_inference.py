@@ -72,6 +72,19 @@ def _f16_gate(arch, hw_f16, hw_precision):
     return on
 
 
+def _sib_f16_gate(arch, hw_sib_f16, hw_precision, hw_f16):
+    """The keyword hw_sib_f16=True belongs to arch="cares18_hw" / "emares18_hw" and goes without hw_precision and hw_f16 (ValueError, before
+    any device call).  Returns it as a bool."""
+    from .engine import Engine
+    on = bool(Engine.hw_sib_f16_value(hw_sib_f16))
+    if on and arch not in ("cares18_hw", EMA_ARCH):
+        raise ValueError("hw_sib_f16 belongs to arch='cares18_hw' / 'emares18_hw' (arch='seres18_hw': hw_f16); arch=%r takes none" % (arch,))
+    if on and (hw_precision is not None or Engine.hw_f16_value(hw_f16)):
+        raise ValueError("hw_sib_f16 names the arithmetic of the call itself: give it without hw_precision and hw_f16, got hw_sib_f16=%r, "
+                         "hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
+    return on
+
+
 def _ema_gate(arch, hw_ema):
     """arch="emares18_hw" and the keyword hw_ema=True come together or not at all (ValueError, before any device call)."""
     from .engine import Engine
@@ -177,7 +190,7 @@ def _check_strong(arch, flip, strong_offsets, n, pad):
 
 
 def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18", view_index=None, size=None, hw_precision=None,
-                        strong_offsets=None, pad=10, hw_ema=False, hw_f16=False):
+                        strong_offsets=None, pad=10, hw_ema=False, hw_f16=False, hw_sib_f16=False):
     """Descriptors of ``images`` (float32 [n,3,256,128], host) into the device rows ``d_out`` (pointer to [n, 512 + num_class]
     fp32): upload in batches of ``bs`` images, one ``reid_descriptor_f32_nchw_dev`` per batch.  Unlike the reference function
     (:78-135) the plain / mirrored halves are averaged and renormalised here already (:252-253).
@@ -205,8 +218,11 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     script gives the Swin the plain mirror.  None is today's call and bits.
 
     ``hw_f16=True`` (``arch="seres18_hw"`` only, and instead of ``hw_precision``: both together are a ValueError): the any-size forward runs
-    in fp16 storage with fp32 accumulation - ``Engine.set_hw_f16(True)`` for this call and restored after it."""
+    in fp16 storage with fp32 accumulation - ``Engine.set_hw_f16(True)`` for this call and restored after it.  ``hw_sib_f16=True``
+    (``arch="cares18_hw"`` / ``"emares18_hw"`` only - the latter still with ``hw_ema=True`` -, without ``hw_precision`` and ``hw_f16``): the
+    same for the siblings, ``Engine.set_hw_sib_f16(True)`` for this call and restored after it."""
     _ema_gate(arch, hw_ema)
+    sib_f16 = _sib_f16_gate(arch, hw_sib_f16, hw_precision, hw_f16)
     f16 = _f16_gate(arch, hw_f16, hw_precision)
     if hw_precision is not None:
         from .engine import Engine
@@ -236,7 +252,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
         view_index = view_index.astype(np.int32)
     if hw_precision is not None or f16 or arch in ("cares18_hw", EMA_ARCH):   # every argument is checked: the settings go on for the device work and off after it
         with engine.hw_precision_scope(hw_precision), engine.hw_siblings_scope(True if arch == "cares18_hw" else None), \
-                engine.hw_ema_scope(True if arch == EMA_ARCH else None), (engine.hw_f16_scope(True) if f16 else contextlib.nullcontext()):
+                engine.hw_ema_scope(True if arch == EMA_ARCH else None), (engine.hw_f16_scope(True) if f16 else contextlib.nullcontext()), \
+                (engine.hw_sib_f16_scope(True) if sib_f16 else contextlib.nullcontext()):
             return inference_efficient(engine, images, d_out, flip, bs, "seres18_hw", view_index, size if u8 else None,
                                        strong_offsets=strong_offsets, pad=pad)
     if u8:
@@ -269,7 +286,7 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
 def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, query_images, query_labels, query_cams,
                   query_seqs, num_gallery_cams=None, eps=0.5, la=0.05, k1=20, k2=6, flip=True, cluster_fn=None, taps=None,
                   verbose=True, device=0, engine=None, arch="seres18", use_side=False, size=None, hw_precision=None,
-                  strong_inference=False, strong_offsets=None, attribute_dist=None, pad=10, hw_ema=False, hw_f16=False):
+                  strong_inference=False, strong_offsets=None, attribute_dist=None, pad=10, hw_ema=False, hw_f16=False, hw_sib_f16=False):
     """(CMC float32 [ng], mAP float) of the script's chain for one gallery / query pair; weights must be loaded on the engine
     (``Engine.load_seres18`` / ``build_model``).  ``taps`` (a dict) receives host copies of the intermediates the
     reference-generated fixture holds: "desc", "debiased", "jaccard", "pseudo_labels", "smoothed".
@@ -292,8 +309,11 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     euclidean_dist(rows, rows) is added to the device Jaccard matrix (``reid_distmat_add_l2_dev``) before its download.
     ``taps["jaccard"]`` stays the matrix before the add; ``taps["dists"]`` is the one handed to DBSCAN / ``cluster_fn``.  With these
     keywords left out the call and its bits are what they were.  ``hw_f16=True`` (``arch="seres18_hw"`` only, instead of ``hw_precision``):
-    the descriptors come from the fp16-storage any-size forward, ``Engine.set_hw_f16(True)`` for the call."""
+    the descriptors come from the fp16-storage any-size forward, ``Engine.set_hw_f16(True)`` for the call.  ``hw_sib_f16=True``
+    (``arch="cares18_hw"`` / ``"emares18_hw"`` only, without ``hw_precision`` and ``hw_f16``): the same for the siblings,
+    ``Engine.set_hw_sib_f16(True)`` for the call."""
     _ema_gate(arch, hw_ema)
+    _sib_f16_gate(arch, hw_sib_f16, hw_precision, hw_f16)
     _f16_gate(arch, hw_f16, hw_precision)
     if strong_inference or strong_offsets is not None:
         n_all = len(gallery_labels) + len(query_labels)
@@ -339,9 +359,9 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     try:
         strong = {} if strong_offsets is None else {"pad": pad}
         inference_efficient(eng, gallery_images, merged.ptr, flip, arch=arch, view_index=gc if use_side else None, size=size if u8[0] else None,
-                            hw_precision=hw_precision, hw_ema=hw_ema, hw_f16=hw_f16, **(strong and dict(strong, strong_offsets=strong_offsets[:ng])))
+                            hw_precision=hw_precision, hw_ema=hw_ema, hw_f16=hw_f16, hw_sib_f16=hw_sib_f16, **(strong and dict(strong, strong_offsets=strong_offsets[:ng])))
         inference_efficient(eng, query_images, merged.row_ptr(ng), flip, arch=arch, view_index=qc if use_side else None,
-                            size=size if u8[1] else None, hw_precision=hw_precision, hw_ema=hw_ema, hw_f16=hw_f16,
+                            size=size if u8[1] else None, hw_precision=hw_precision, hw_ema=hw_ema, hw_f16=hw_f16, hw_sib_f16=hw_sib_f16,
                             **(strong and dict(strong, strong_offsets=strong_offsets[ng:])))
         if taps is not None:
             taps["desc"] = merged.numpy()

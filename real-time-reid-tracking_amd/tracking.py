@@ -36,9 +36,15 @@ EMA_ARCH = "emares18_hw"                  # accepted only together with the keyw
 HW_ARCHS = ("seres18_hw", "cares18_hw", EMA_ARCH)
 
 
-def _check_arch(arch, size, mean_std, hw_precision=None, hw_ema=False, hw_f16=False):
+def _check_arch(arch, size, mean_std, hw_precision=None, hw_ema=False, hw_f16=False, hw_sib_f16=False):
     """`arch`, `size`, `mean_std`, `hw_precision`, `hw_ema`, `hw_f16` of the stream classes, checked before any device call (ValueError)."""
     on = bool(Engine.hw_ema_value(hw_ema))
+    if Engine.hw_sib_f16_value(hw_sib_f16):
+        if arch not in ("cares18_hw", EMA_ARCH):
+            raise ValueError("hw_sib_f16 belongs to arch='cares18_hw' / %r (arch='seres18_hw': hw_f16), got arch %r" % (EMA_ARCH, arch))
+        if hw_precision is not None or Engine.hw_f16_value(hw_f16):
+            raise ValueError("hw_sib_f16 names the arithmetic of the stream's crops itself: give it without hw_precision and hw_f16, got "
+                             "hw_sib_f16=%r, hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
     if Engine.hw_f16_value(hw_f16):
         if arch != "seres18_hw":
             raise ValueError("hw_f16 belongs to arch='seres18_hw' (the fp16-storage any-size forward serves seres18_ibn only), got arch %r"
@@ -65,7 +71,7 @@ def _check_arch(arch, size, mean_std, hw_precision=None, hw_ema=False, hw_f16=Fa
     Engine.hw_precision_value(hw_precision)
 
 
-def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_precision=None, hw_ema=False, hw_f16=False):
+def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_precision=None, hw_ema=False, hw_f16=False, hw_sib_f16=False):
     """`arch` of the stream classes: "seres18" (default) loads a ResNet18-SE family checkpoint, frames are 512 wide; "swin" - the
     reference's swin_transformer tracker model, modification_tracking/models/__init__.py:80 - loads with `Engine.load_swin`, every crop
     is resized to ``size`` = (H, W) multiples of 224 and normalised with ``mean_std`` (None: ImageNet), and the embeddings, the bank
@@ -74,7 +80,9 @@ def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_prec
     and runs the any-size forward in the arithmetic ``hw_precision`` names (`Engine.set_hw_precision`); frames are 512 wide; "cares18_hw" - the same with a CARes18-IBN (cares18_ibn) checkpoint: the context's
     `Engine.set_hw_siblings` is switched on, and stays on for the stream's life; "emares18_hw" with ``hw_ema=True`` - the same with an
     EMARes18-IBN (emares18_ibn) checkpoint and `Engine.set_hw_ema`.  ``hw_f16=True`` with "seres18_hw" (and no ``hw_precision``): the
-    crops run in fp16 storage with fp32 accumulation, `Engine.set_hw_f16` switched on for the stream's life."""
+    crops run in fp16 storage with fp32 accumulation, `Engine.set_hw_f16` switched on for the stream's life.  ``hw_sib_f16=True`` with
+    "cares18_hw" / "emares18_hw" (and neither ``hw_precision`` nor ``hw_f16``): the same for the siblings, `Engine.set_hw_sib_f16` kept on
+    the stream's engine."""
     if arch == "swin":
         stream.eng.load_swin(weights_blob, manifest)
     else:
@@ -88,6 +96,9 @@ def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_prec
     f16 = bool(Engine.hw_f16_value(hw_f16))
     if arch in HW_ARCHS and (f16 or getattr(stream.eng, "hw_f16", False)):      # on for this stream, or left on by an earlier user of a shared context
         stream.eng.set_hw_f16(f16)
+    sib_f16 = bool(Engine.hw_sib_f16_value(hw_sib_f16))
+    if arch in HW_ARCHS and (sib_f16 or getattr(stream.eng, "hw_sib_f16", False)):   # likewise
+        stream.eng.set_hw_sib_f16(sib_f16)
     stream.arch, stream.size, stream.mean_std = arch, size, mean_std
 
 
@@ -107,11 +118,11 @@ def _one_stream_again(stream):
 
 class CameraStream:
     def __init__(self, weights_blob, manifest, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0, own_context=True,
-                 max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_f16=False, hw_precision=None):
-        _check_arch(arch, size, mean_std, hw_precision, hw_ema, hw_f16)
+                 max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_f16=False, hw_sib_f16=False, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision, hw_ema, hw_f16, hw_sib_f16)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema, hw_f16)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema, hw_f16, hw_sib_f16)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -164,11 +175,11 @@ class MultiCameraStream:
     with one list entry per camera everywhere; one host thread, one wait per frame time."""
 
     def __init__(self, weights_blob, manifest, cameras, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_f16=False, hw_precision=None):
-        _check_arch(arch, size, mean_std, hw_precision, hw_ema, hw_f16)
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_f16=False, hw_sib_f16=False, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision, hw_ema, hw_f16, hw_sib_f16)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema, hw_f16)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema, hw_f16, hw_sib_f16)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
@@ -253,11 +264,11 @@ class LookaheadCameraStream:
     """
 
     def __init__(self, weights_blob, manifest, frames_per_pass=2, precision=0, max_dist=0.15, budget=100, metric="cosine", device=0,
-                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_f16=False, hw_precision=None):
-        _check_arch(arch, size, mean_std, hw_precision, hw_ema, hw_f16)
+                 own_context=True, max_tracks=4096, match_stream=True, arch="seres18", size=(224, 224), mean_std=None, hw_ema=False, hw_f16=False, hw_sib_f16=False, hw_precision=None):
+        _check_arch(arch, size, mean_std, hw_precision, hw_ema, hw_f16, hw_sib_f16)
         self._own = bool(own_context)
         self.eng = Engine(device) if own_context else get_engine(device)
-        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema, hw_f16)
+        _load_backbone(self, arch, weights_blob, manifest, size, mean_std, hw_precision, hw_ema, hw_f16, hw_sib_f16)
         self.eng.set_precision(precision)
         _two_streams(self, match_stream)
         self.max_dist = max_dist
