@@ -11,7 +11,7 @@ import numpy as np
 
 from . import precision as _precision
 from . import synth, weights
-from .engine import IMG_H, IMG_W, Engine, check_hw, get_engine
+from .engine import IMG_H, IMG_W, Engine, check_hw, get_engine, hw_f16_gate, hw_sib_f16_gate
 
 
 def _device_index(device):
@@ -104,20 +104,13 @@ class SERes18IBN:
         if self._hw_ema and self.arch != "emares18_ibn":
             raise ValueError("%s has no hw_ema argument (emares18_ibn only)" % self.arch)
         # seres18_ibn only: True = inputs of another size run in fp16 storage with fp32 accumulation (Engine.set_hw_f16 around such a call)
-        self._hw_f16 = bool(Engine.hw_f16_value(hw_f16))
-        if self._hw_f16 and self.arch != "seres18_ibn":
-            raise ValueError("%s has no hw_f16 argument (seres18_ibn only)" % self.arch)
-        if self._hw_f16 and hw_precision is not None:
-            raise ValueError("hw_f16 and hw_precision both name the arithmetic of inputs of another size: give one of them, got hw_f16=%r "
-                             "and hw_precision=%r" % (hw_f16, hw_precision))
+        self._hw_f16 = hw_f16_gate(hw_f16, hw_precision, self.arch == "seres18_ibn", "%s has no hw_f16 argument (seres18_ibn only)" % self.arch,
+                                   "inputs of another size")
         # cares18_ibn / emares18_ibn only: True = inputs of another size run in fp16 storage with fp32 accumulation (Engine.set_hw_sib_f16
         # around such a call); the keyword alone is enough, hw_siblings / hw_ema need not be given
-        self._hw_sib_f16 = bool(Engine.hw_sib_f16_value(hw_sib_f16))
-        if self._hw_sib_f16 and self.arch == "seres18_ibn":
-            raise ValueError("seres18_ibn has no hw_sib_f16 argument (cares18_ibn and emares18_ibn only; seres18_ibn: hw_f16)")
-        if self._hw_sib_f16 and (hw_precision is not None or self._hw_f16):
-            raise ValueError("hw_sib_f16 names the arithmetic of inputs of another size itself: give it without hw_precision and hw_f16, got "
-                             "hw_sib_f16=%r, hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
+        self._hw_sib_f16 = hw_sib_f16_gate(hw_sib_f16, hw_precision, hw_f16, self.arch != "seres18_ibn",
+                                           "seres18_ibn has no hw_sib_f16 argument (cares18_ibn and emares18_ibn only; seres18_ibn: hw_f16)",
+                                           "inputs of another size")
         self._hw_call = _HwClassCall(self) if hw == 2 else None
         self.num_classes = num_classes
         self.num_cams, self.cam_factor = num_cams, float(cam_factor)   # SERes18_IBN.py:193,198: cam_bias [num_cams,512] and its factor
@@ -226,47 +219,21 @@ class SERes18IBN:
             raise ValueError("expected [N,3,H,W] input, got %s" % (tuple(x.shape),))
         size = check_hw(tuple(x.shape[2:]))
         any_size = size != (IMG_H, IMG_W)
-        if any_size and self.arch != "seres18_ibn" and not getattr(self, "_hw_siblings", False) and not getattr(self, "_hw_ema", False) \
-                and not getattr(self, "_hw_sib_f16", False):
+        if any_size and self.arch != "seres18_ibn" and not (self._hw_siblings or self._hw_ema or self._hw_sib_f16):
             raise ValueError("%s runs at [N,3,%d,%d] only (other sizes: seres18_ibn), got %s" % (self.arch, IMG_H, IMG_W, tuple(x.shape)))
         # another size runs the any-size forward: this CALL runs in exact fp32 (mode 0) or, with hw_precision="f16x3", in the fp32-class
         # arithmetic (reid_ctx_set_hw_precision 2 around the call); the model keeps its own mode and the engine gets its settings back
-        if any_size and self._hw_call is not None:
-            run = self._hw_call.run
+        if not any_size:
+            run = self._run
         else:
-            run = (lambda fn: _precision.run(_ExactCall(self), get_engine(self._device), self.arch, fn)) if any_size else self._run
-        if any_size and getattr(self, "_hw_siblings", False):     # cares18_ibn: the engine's setting goes on for this call and off after it
-            inner = run
+            call = self._hw_call or _ExactCall(self)
 
-            def run(fn):
+            def run(fn):       # the model's keywords go on inside what `call` sets up, for this call, and off after it
                 def scoped(e):
-                    with e.hw_siblings_scope(True):
+                    with Engine.hw_scope(e, siblings=self._hw_siblings or None, ema=self._hw_ema or None, f16=self._hw_f16 or None,
+                                    sib_f16=self._hw_sib_f16 or None):
                         return fn(e)
-                return inner(scoped)
-        if any_size and getattr(self, "_hw_ema", False):          # emares18_ibn: likewise with the engine's hw_ema
-            inner_ema = run
-
-            def run(fn):
-                def scoped(e):
-                    with e.hw_ema_scope(True):
-                        return fn(e)
-                return inner_ema(scoped)
-        if any_size and getattr(self, "_hw_f16", False):          # seres18_ibn in fp16 storage: likewise with the engine's hw_f16
-            inner_f16 = run
-
-            def run(fn):
-                def scoped(e):
-                    with e.hw_f16_scope(True):
-                        return fn(e)
-                return inner_f16(scoped)
-        if any_size and getattr(self, "_hw_sib_f16", False):      # a sibling in fp16 storage: likewise with the engine's hw_sib_f16
-            inner_sib = run
-
-            def run(fn):
-                def scoped(e):
-                    with e.hw_sib_f16_scope(True):
-                        return fn(e)
-                return inner_sib(scoped)
+                return call.run(scoped)
         if is_torch and x.is_cuda:
             if x.device.index != self._device:
                 self.to(x.device.index)
@@ -316,6 +283,9 @@ class _ExactCall(object):
     def _do_bind(self, eng):
         self._owner._do_bind(eng)
 
+    def run(self, fn):
+        return _precision.run(self, get_engine(self._owner._device), self._owner.arch, fn)
+
 
 class _HwClassCall(_ExactCall):
     """precision.run owner for the calls of a model at another input size in the fp32-class arithmetic (hw_precision="f16x3"): the context
@@ -328,12 +298,10 @@ class _HwClassCall(_ExactCall):
         self._mode = _precision.F32_CLASS
 
     def run(self, fn):
-        eng = get_engine(self._owner._device)
-
         def scoped(e):
             with e.hw_precision_scope(2 if self._mode == _precision.F32_CLASS else None):
                 return fn(e)
-        return _precision.run(self, eng, self._owner.arch, scoped)
+        return _ExactCall.run(self, scoped)
 
 
 def seres18_ibn(num_classes=751, loss="triplet", pretrained=False, use_gpu=True, **kwargs):

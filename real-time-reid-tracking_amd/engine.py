@@ -3,6 +3,8 @@
 Nothing here computes: every method marshals numpy arrays (or raw device
 pointers) into the C ABI and returns what the HIP kernels produced.
 """
+import collections
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -61,7 +63,156 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
-class Engine:
+def _hw_precision_c(v):
+    if v is None:
+        return -1
+    if isinstance(v, str):
+        return HW_PRECISION_NAMES.get(v.strip().lower())
+    if not isinstance(v, bool) and isinstance(v, (int, np.integer)) and int(v) in (-1, 0, 2):
+        return int(v)
+    return None
+
+
+def _hw_flag_c(v):
+    if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
+        return int(v)
+    return None
+
+
+# The settings of the any-size forward, each stated once: name, C setter, the library's default as the property reports it (an int keeps
+# the C value, a bool its truth), value -> C value (None: refused), the ValueError text, the exceptions a restoring scope lets pass, and
+# the docstrings of set_hw_X and - where they are not the flag form's - of hw_X_value and hw_X.  Engine.hw_X_value, set_hw_X, hw_X and
+# hw_X_scope are built from a row; Engine.hw_scope enters the scopes in this order.
+HwSetting = collections.namedtuple("HwSetting", "name setter default c_value error restore_may_fail set_doc value_doc get_doc")
+HW_SETTINGS = (
+    HwSetting("hw_precision", "reid_ctx_set_hw_precision", -1, _hw_precision_c,
+              "hw_precision must be None / -1 (other input sizes need mode 0), \"f32\" / 0 or \"f16x3\" / 2, got %r",
+              (_ffi.ReidHipError,),      # `prev` was 2 and the weights bound meanwhile cannot be split: stay
+              """The arithmetic of the any-size forward of seres18_ibn (reid_ctx_set_hw_precision): None / -1 = another size needs the context
+        in mode 0 (default), "f32" / 0 = other sizes run exact fp32 whatever the mode, "f16x3" / 2 = they run fp32-class whatever the mode
+        (libreid_hip_anysize_x3.so).  256 x 128 is not affected.""",
+              """None / -1 -> -1, "f32" / 0 -> 0, "f16x3" / 2 -> 2 (the values of reid_ctx_set_hw_precision); ValueError otherwise, before any
+        device call - the fp16-storage arithmetic of the any-size forward is a setting of its own (set_hw_f16), every other value has none.""",
+              "-1, 0 or 2: what set_hw_precision set last (the library's default is -1)."),
+    HwSetting("hw_siblings", "reid_ctx_set_hw_siblings", False, _hw_flag_c,
+              "hw_siblings must be False / 0 (other input sizes run seres18_ibn only) or True / 1 (cares18_ibn too), got %r", (),
+              """CARes18-IBN at input sizes other than 256 x 128 (reid_ctx_set_hw_siblings): False (default) = the reid_*_hw entries refuse a
+        loaded cares18_ibn at another size, True = it runs there with the TripletAttention tail of libreid_hip_anysize_ca.so, under the
+        size, precision and pass-size rules of seres18_ibn.  emares18_ibn stays refused; 256 x 128 is not affected.""", None, None),
+    HwSetting("hw_ema", "reid_ctx_set_hw_ema", False, _hw_flag_c,
+              "hw_ema must be False / 0 (other input sizes refuse emares18_ibn) or True / 1 (they run it), got %r", (),
+              """EMARes18-IBN at input sizes other than 256 x 128 (reid_ctx_set_hw_ema): False (default) = the reid_*_hw entries refuse a
+        loaded emares18_ibn at another size, True = it runs there with the EMA tail of libreid_hip_anysize_ema.so, under the size,
+        precision and pass-size rules of seres18_ibn and whatever set_hw_siblings is.  cares18_ibn still needs set_hw_siblings; 256 x 128 is
+        not affected.""", None, None),
+    HwSetting("hw_f16", "reid_ctx_set_hw_f16", False, _hw_flag_c,
+              "hw_f16 must be False / 0 (other input sizes run in the arithmetic hw_precision names) or True / 1 (they run "
+              "seres18_ibn in fp16 storage), got %r", (),
+              """seres18_ibn at input sizes other than 256 x 128 in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16): False (default) =
+        set_hw_precision and the mode decide, True = such inputs run through libreid_hip_anysize_f16.so whatever the mode and
+        hw_precision, which keeps its value.  cares18_ibn / emares18_ibn are refused there; 256 x 128 is not affected.""", None, None),
+    HwSetting("hw_sib_f16", "reid_ctx_set_hw_sib_f16", False, _hw_flag_c,
+              "hw_sib_f16 must be False / 0 (other input sizes run cares18_ibn / emares18_ibn as hw_siblings, hw_ema and "
+              "hw_precision say) or True / 1 (they run them in fp16 storage), got %r", (),
+              """cares18_ibn / emares18_ibn at input sizes other than 256 x 128 in fp16 storage with fp32 accumulation
+        (reid_ctx_set_hw_sib_f16): False (default) = set_hw_siblings, set_hw_ema, set_hw_precision and the mode decide (and set_hw_f16
+        refuses them), True = such inputs run through libreid_hip_anysize_f16.so with the block tails of libreid_hip_anysize_sib_f16.so
+        whatever those settings are; they keep their values.  seres18_ibn and 256 x 128 are not affected.""", None, None),
+)
+
+
+class _HwSettings:
+    """Engine's share of the any-size settings: hw_X_value, set_hw_X, hw_X and hw_X_scope per row of HW_SETTINGS (_hw_members, below
+    the class), and hw_scope over all of them.  The scopes go through ``self.hw_X`` and ``self.set_hw_X`` only, so they serve any object
+    that has those two (the host tests' stand-ins)."""
+
+    @contextlib.contextmanager
+    def hw_scope(self, precision=None, siblings=None, ema=None, f16=None, sib_f16=None):
+        """Context manager over the five single scopes, entered in the order of HW_SETTINGS - precision, siblings, ema, f16, sib_f16 - and
+        left in reverse: a value of None leaves that setting alone, every other one is set inside and what it was before comes back
+        outside (hw_X_scope).  The package calls it as ``Engine.hw_scope(eng, ...)``, which asks of ``eng`` only the attribute and the
+        setter of each setting that is not None."""
+        with contextlib.ExitStack() as stack:
+            for s, v in zip(HW_SETTINGS, (precision, siblings, ema, f16, sib_f16)):
+                if v is not None:
+                    stack.enter_context(getattr(_HwSettings, s.name + "_scope")(self, v))
+            yield self
+
+
+def _hw_members(s):
+    """(hw_X_value, set_hw_X, hw_X, hw_X_scope) of one row of HW_SETTINGS."""
+    attr, kept, flag = "_" + s.name, type(s.default), s.c_value is _hw_flag_c
+
+    def value(v):
+        c = s.c_value(v)
+        if c is None:
+            raise ValueError(s.error % (v,))
+        return c
+
+    def setter(self, v):
+        c = value(v)
+        check(getattr(self.lib, s.setter)(self.h, c))
+        setattr(self, attr, kept(c))
+
+    def getter(self):
+        return getattr(self, attr, s.default)
+
+    @contextlib.contextmanager
+    def scope(self, v):
+        if v is None:
+            yield self
+            return
+        prev = getattr(self, s.name)
+        getattr(self, "set_" + s.name)(v)
+        try:
+            yield self
+        finally:
+            if getattr(self, s.name) != prev:
+                try:
+                    getattr(self, "set_" + s.name)(prev)
+                except s.restore_may_fail:
+                    pass
+    value.__doc__ = "False / 0 -> 0, True / 1 -> 1 (the values of %s); ValueError otherwise, before any device call." % s.setter if flag else s.value_doc
+    setter.__doc__ = s.set_doc
+    getter.__doc__ = "What set_%s set last (the library's default is False)." % s.name if flag else s.get_doc
+    scope.__doc__ = ("Context manager: ``%s`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."
+                     % ("on" if flag else "v"))
+    for fn, name in ((value, s.name + "_value"), (setter, "set_" + s.name), (scope, s.name + "_scope")):
+        fn.__name__, fn.__qualname__ = name, "Engine." + name
+    return staticmethod(value), setter, property(getter), scope
+
+
+for _s in HW_SETTINGS:
+    for _name, _member in zip((_s.name + "_value", "set_" + _s.name, _s.name, _s.name + "_scope"), _hw_members(_s)):
+        setattr(_HwSettings, _name, _member)
+
+
+def hw_f16_gate(hw_f16, hw_precision, fits, belongs, of):
+    """The keyword hw_f16 at one call site: it belongs to seres18_ibn - ``fits`` is the site's test of its architecture, ``belongs`` the
+    site's words when it fails - and replaces hw_precision as the name of the arithmetic of ``of`` (the site's words).  ValueError, before
+    any device call; returns the keyword as a bool."""
+    on = bool(Engine.hw_f16_value(hw_f16))
+    if on and not fits:
+        raise ValueError(belongs)
+    if on and hw_precision is not None:
+        raise ValueError("hw_f16 and hw_precision both name the arithmetic of %s: give one of them, got hw_f16=%r and hw_precision=%r"
+                         % (of, hw_f16, hw_precision))
+    return on
+
+
+def hw_sib_f16_gate(hw_sib_f16, hw_precision, hw_f16, fits, belongs, of):
+    """The keyword hw_sib_f16 at one call site: it belongs to cares18_ibn / emares18_ibn (``fits``, ``belongs`` as in hw_f16_gate) and goes
+    without hw_precision and hw_f16, naming the arithmetic of ``of`` itself.  ValueError, before any device call; returns it as a bool."""
+    on = bool(Engine.hw_sib_f16_value(hw_sib_f16))
+    if on and not fits:
+        raise ValueError(belongs)
+    if on and (hw_precision is not None or Engine.hw_f16_value(hw_f16)):
+        raise ValueError("hw_sib_f16 names the arithmetic of %s itself: give it without hw_precision and hw_f16, got hw_sib_f16=%r, "
+                         "hw_precision=%r, hw_f16=%r" % (of, hw_sib_f16, hw_precision, hw_f16))
+    return on
+
+
+class Engine(_HwSettings):
     def __init__(self, device=0):
         self.lib = _ffi.lib()
         h = C.c_void_p()
@@ -167,210 +318,6 @@ class Engine:
     def precision(self):
         """The arithmetic mode this context is in (the library's default is 0)."""
         return getattr(self, "_precision", 0)
-
-    @staticmethod
-    def hw_precision_value(v):
-        """None / -1 -> -1, "f32" / 0 -> 0, "f16x3" / 2 -> 2 (the values of reid_ctx_set_hw_precision); ValueError otherwise, before any
-        device call - the fp16-storage arithmetic of the any-size forward is a setting of its own (set_hw_f16), every other value has none."""
-        if v is None:
-            return -1
-        if isinstance(v, str):
-            key = v.strip().lower()
-            if key in HW_PRECISION_NAMES:
-                return HW_PRECISION_NAMES[key]
-        elif not isinstance(v, bool) and isinstance(v, (int, np.integer)) and int(v) in (-1, 0, 2):
-            return int(v)
-        raise ValueError("hw_precision must be None / -1 (other input sizes need mode 0), \"f32\" / 0 or \"f16x3\" / 2, got %r" % (v,))
-
-    def set_hw_precision(self, v):
-        """The arithmetic of the any-size forward of seres18_ibn (reid_ctx_set_hw_precision): None / -1 = another size needs the context
-        in mode 0 (default), "f32" / 0 = other sizes run exact fp32 whatever the mode, "f16x3" / 2 = they run fp32-class whatever the mode
-        (libreid_hip_anysize_x3.so).  256 x 128 is not affected."""
-        v = Engine.hw_precision_value(v)
-        check(self.lib.reid_ctx_set_hw_precision(self.h, v))
-        self._hw_precision = v
-
-    @property
-    def hw_precision(self):
-        """-1, 0 or 2: what set_hw_precision set last (the library's default is -1)."""
-        return getattr(self, "_hw_precision", -1)
-
-    def hw_precision_scope(self, v):
-        """Context manager: ``v`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def scope():
-            if v is None:
-                yield self
-                return
-            prev = self.hw_precision
-            self.set_hw_precision(v)
-            try:
-                yield self
-            finally:
-                if self.hw_precision != prev:
-                    try:
-                        self.set_hw_precision(prev)
-                    except _ffi.ReidHipError:      # `prev` was 2 and the weights bound meanwhile cannot be split: stay
-                        pass
-        return scope()
-
-    @staticmethod
-    def hw_siblings_value(v):
-        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_siblings); ValueError otherwise, before any device call."""
-        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
-            return int(v)
-        raise ValueError("hw_siblings must be False / 0 (other input sizes run seres18_ibn only) or True / 1 (cares18_ibn too), got %r" % (v,))
-
-    def set_hw_siblings(self, on):
-        """CARes18-IBN at input sizes other than 256 x 128 (reid_ctx_set_hw_siblings): False (default) = the reid_*_hw entries refuse a
-        loaded cares18_ibn at another size, True = it runs there with the TripletAttention tail of libreid_hip_anysize_ca.so, under the
-        size, precision and pass-size rules of seres18_ibn.  emares18_ibn stays refused; 256 x 128 is not affected."""
-        v = Engine.hw_siblings_value(on)
-        check(self.lib.reid_ctx_set_hw_siblings(self.h, v))
-        self._hw_siblings = bool(v)
-
-    @property
-    def hw_siblings(self):
-        """What set_hw_siblings set last (the library's default is False)."""
-        return getattr(self, "_hw_siblings", False)
-
-    def hw_siblings_scope(self, on):
-        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def scope():
-            if on is None:
-                yield self
-                return
-            prev = self.hw_siblings
-            self.set_hw_siblings(on)
-            try:
-                yield self
-            finally:
-                if self.hw_siblings != prev:
-                    self.set_hw_siblings(prev)
-        return scope()
-
-    @staticmethod
-    def hw_ema_value(v):
-        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_ema); ValueError otherwise, before any device call."""
-        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
-            return int(v)
-        raise ValueError("hw_ema must be False / 0 (other input sizes refuse emares18_ibn) or True / 1 (they run it), got %r" % (v,))
-
-    def set_hw_ema(self, on):
-        """EMARes18-IBN at input sizes other than 256 x 128 (reid_ctx_set_hw_ema): False (default) = the reid_*_hw entries refuse a
-        loaded emares18_ibn at another size, True = it runs there with the EMA tail of libreid_hip_anysize_ema.so, under the size,
-        precision and pass-size rules of seres18_ibn and whatever set_hw_siblings is.  cares18_ibn still needs set_hw_siblings; 256 x 128 is
-        not affected."""
-        v = Engine.hw_ema_value(on)
-        check(self.lib.reid_ctx_set_hw_ema(self.h, v))
-        self._hw_ema = bool(v)
-
-    @property
-    def hw_ema(self):
-        """What set_hw_ema set last (the library's default is False)."""
-        return getattr(self, "_hw_ema", False)
-
-    def hw_ema_scope(self, on):
-        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def scope():
-            if on is None:
-                yield self
-                return
-            prev = self.hw_ema
-            self.set_hw_ema(on)
-            try:
-                yield self
-            finally:
-                if self.hw_ema != prev:
-                    self.set_hw_ema(prev)
-        return scope()
-
-    @staticmethod
-    def hw_f16_value(v):
-        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_f16); ValueError otherwise, before any device call."""
-        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
-            return int(v)
-        raise ValueError("hw_f16 must be False / 0 (other input sizes run in the arithmetic hw_precision names) or True / 1 (they run "
-                         "seres18_ibn in fp16 storage), got %r" % (v,))
-
-    def set_hw_f16(self, on):
-        """seres18_ibn at input sizes other than 256 x 128 in fp16 storage with fp32 accumulation (reid_ctx_set_hw_f16): False (default) =
-        set_hw_precision and the mode decide, True = such inputs run through libreid_hip_anysize_f16.so whatever the mode and
-        hw_precision, which keeps its value.  cares18_ibn / emares18_ibn are refused there; 256 x 128 is not affected."""
-        v = Engine.hw_f16_value(on)
-        check(self.lib.reid_ctx_set_hw_f16(self.h, v))
-        self._hw_f16 = bool(v)
-
-    @property
-    def hw_f16(self):
-        """What set_hw_f16 set last (the library's default is False)."""
-        return getattr(self, "_hw_f16", False)
-
-    def hw_f16_scope(self, on):
-        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def scope():
-            if on is None:
-                yield self
-                return
-            prev = self.hw_f16
-            self.set_hw_f16(on)
-            try:
-                yield self
-            finally:
-                if self.hw_f16 != prev:
-                    self.set_hw_f16(prev)
-        return scope()
-
-    @staticmethod
-    def hw_sib_f16_value(v):
-        """False / 0 -> 0, True / 1 -> 1 (the values of reid_ctx_set_hw_sib_f16); ValueError otherwise, before any device call."""
-        if isinstance(v, (bool, np.bool_)) or (isinstance(v, (int, np.integer)) and int(v) in (0, 1)):
-            return int(v)
-        raise ValueError("hw_sib_f16 must be False / 0 (other input sizes run cares18_ibn / emares18_ibn as hw_siblings, hw_ema and "
-                         "hw_precision say) or True / 1 (they run them in fp16 storage), got %r" % (v,))
-
-    def set_hw_sib_f16(self, on):
-        """cares18_ibn / emares18_ibn at input sizes other than 256 x 128 in fp16 storage with fp32 accumulation
-        (reid_ctx_set_hw_sib_f16): False (default) = set_hw_siblings, set_hw_ema, set_hw_precision and the mode decide (and set_hw_f16
-        refuses them), True = such inputs run through libreid_hip_anysize_f16.so with the block tails of libreid_hip_anysize_sib_f16.so
-        whatever those settings are; they keep their values.  seres18_ibn and 256 x 128 are not affected."""
-        v = Engine.hw_sib_f16_value(on)
-        check(self.lib.reid_ctx_set_hw_sib_f16(self.h, v))
-        self._hw_sib_f16 = bool(v)
-
-    @property
-    def hw_sib_f16(self):
-        """What set_hw_sib_f16 set last (the library's default is False)."""
-        return getattr(self, "_hw_sib_f16", False)
-
-    def hw_sib_f16_scope(self, on):
-        """Context manager: ``on`` None leaves the setting alone; otherwise it is set inside and what it was before comes back outside."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def scope():
-            if on is None:
-                yield self
-                return
-            prev = self.hw_sib_f16
-            self.set_hw_sib_f16(on)
-            try:
-                yield self
-            finally:
-                if self.hw_sib_f16 != prev:
-                    self.set_hw_sib_f16(prev)
-        return scope()
 
     def set_side_index(self, index):
         """Camera (ResNet18-IBN-SE: SERes18_IBN.py:269-270) or view (Swin: swin_transformer.py:301-302) index of every image of

@@ -16,7 +16,6 @@ Deviations, all forced by defects of the reference file itself (SURVEY.md sectio
   Q2  it never calls .eval(); the only well-defined semantics, used here, is eval mode (running-stat BN).
   Q3  embedding = BNNeck output (512-d), the first element of the eval-mode tuple (SERes18_IBN.py:274-275).
 """
-import contextlib
 import logging
 
 import numpy as np
@@ -72,16 +71,15 @@ class Extractor(object):
             # loads two and aborts in the exit handlers - DESIGN.md section 6, the rule parallel.RcclComm.from_env enforces)
             import torch
             state_dict = torch.load(model_path, map_location="cpu")   # {"state_dict": ...} / "module." prefixes: weights.pack_seres18
-        from .engine import Engine, get_engine
+        from .engine import Engine, get_engine, hw_f16_gate, hw_sib_f16_gate
         self._arch, blob, manifest, self.info = pack_checkpoint(state_dict)
         if self._hw_ema and self.info.get("arch") != "emares18_ibn":
             raise ValueError("Extractor: hw_ema belongs to emares18_ibn checkpoints, got %s" % (self.info.get("arch"),))
-        if self._hw_f16 and (self._arch == "swin" or self.info.get("arch") != "seres18_ibn"):
-            raise ValueError("Extractor: hw_f16 belongs to seres18_ibn checkpoints (the fp16-storage any-size forward serves them only), "
-                             "got %s" % ("swin" if self._arch == "swin" else self.info.get("arch"),))
-        if self._hw_sib_f16 and (self._arch == "swin" or self.info.get("arch") not in ("cares18_ibn", "emares18_ibn")):
-            raise ValueError("Extractor: hw_sib_f16 belongs to cares18_ibn / emares18_ibn checkpoints (seres18_ibn: hw_f16), got %s"
-                             % ("swin" if self._arch == "swin" else self.info.get("arch"),))
+        got = "swin" if self._arch == "swin" else self.info.get("arch")       # no hw_precision here: `precision` names that arithmetic
+        hw_f16_gate(hw_f16, None, got == "seres18_ibn", "Extractor: hw_f16 belongs to seres18_ibn checkpoints (the fp16-storage any-size "
+                    "forward serves them only), got %s" % (got,), None)
+        hw_sib_f16_gate(hw_sib_f16, None, False, got in ("cares18_ibn", "emares18_ibn"), "Extractor: hw_sib_f16 belongs to cares18_ibn / "
+                        "emares18_ibn checkpoints (seres18_ibn: hw_f16), got %s" % (got,), None)
         if self._arch == "swin":
             self.size = tuple(int(v) for v in (size or (224, 224)))           # (W, H)
             Engine._swin_crop_args(self.size[::-1], None)
@@ -141,13 +139,13 @@ class Extractor(object):
         if self._arch != "swin" and self.size != (128, 256):
             # another size: the fp32-class arithmetic is the any-size forward's own setting, put on for the call and taken off after it; after
             # a fall back (precision.run) the object is exact fp32 and the setting stays as the engine has it
+            from .engine import Engine
+
             def scoped(eng):
                 sib = True if self._hw_siblings and self.info.get("arch") == "cares18_ibn" else None
                 ema = True if self._hw_ema and self.info.get("arch") == "emares18_ibn" else None
                 x3 = 2 if self._mode == _precision.F32_CLASS and not self._hw_f16 and not self._hw_sib_f16 else None
-                with eng.hw_precision_scope(x3), eng.hw_siblings_scope(sib), eng.hw_ema_scope(ema), \
-                        (eng.hw_f16_scope(True) if self._hw_f16 else contextlib.nullcontext()), \
-                        (eng.hw_sib_f16_scope(True) if self._hw_sib_f16 else contextlib.nullcontext()):
+                with Engine.hw_scope(eng, precision=x3, siblings=sib, ema=ema, f16=self._hw_f16 or None, sib_f16=self._hw_sib_f16 or None):
                     return fn(eng)
             return _precision.run(self, self.net, "Extractor", scoped)
         return _precision.run(self, self.net, "Extractor", fn)

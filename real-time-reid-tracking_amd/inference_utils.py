@@ -9,7 +9,7 @@
 """
 import numpy as np
 
-from .engine import check_hw, get_engine
+from .engine import Engine, check_hw, get_engine, hw_f16_gate, hw_sib_f16_gate
 
 
 def _np(a):
@@ -54,27 +54,16 @@ def extract_descriptors(images, flip=True, device=0, size=None, hw_precision=Non
     if size is not None:
         size = check_hw(size)
     if strong_offsets is not None:
-        from .engine import Engine
         if not flip:
             raise ValueError("strong_offsets shift the mirrored view: flip must be on")
         strong_offsets, pad = Engine.check_shift(strong_offsets, len(images), pad)   # a bad value raises here, before any device call
-    from .engine import Engine as _Engine
-    if _Engine.hw_sib_f16_value(hw_sib_f16):         # a bad value raises here, before any device call
-        if hw_precision is not None or _Engine.hw_f16_value(hw_f16):
-            raise ValueError("hw_sib_f16 names the arithmetic of another size itself: give it without hw_precision and hw_f16, got "
-                             "hw_sib_f16=%r, hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
-        with get_engine(device).hw_sib_f16_scope(True):
-            return extract_descriptors(images, flip, device, size, strong_offsets=strong_offsets, pad=pad)
-    if _Engine.hw_f16_value(hw_f16):                 # a bad value raises here, before any device call
-        if hw_precision is not None:
-            raise ValueError("hw_f16 and hw_precision both name the arithmetic of another size: give one of them, got hw_f16=%r and "
-                             "hw_precision=%r" % (hw_f16, hw_precision))
-        with get_engine(device).hw_f16_scope(True):
-            return extract_descriptors(images, flip, device, size, strong_offsets=strong_offsets, pad=pad)
+    # no architecture to test here (the weights are whatever the engine holds); a bad value raises here, before any device call
+    sib_f16 = hw_sib_f16_gate(hw_sib_f16, hw_precision, hw_f16, True, None, "another size")
+    f16 = hw_f16_gate(hw_f16, hw_precision, True, None, "another size")
     if hw_precision is not None:
-        from .engine import Engine
-        Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
-        with get_engine(device).hw_precision_scope(hw_precision):
+        Engine.hw_precision_value(hw_precision)
+    if hw_precision is not None or f16 or sib_f16:      # the setting goes on for the rest of the call and off after it
+        with Engine.hw_scope(get_engine(device), precision=hw_precision, f16=f16 or None, sib_f16=sib_f16 or None):
             return extract_descriptors(images, flip, device, size, strong_offsets=strong_offsets, pad=pad)
     if isinstance(images, (list, tuple)) and len(images) and all(getattr(im, "dtype", None) == np.uint8 for im in images):
         if strong_offsets is not None:

@@ -12,6 +12,15 @@ __model_factory = {
     'emares18_ibn': emares18_ibn,
     'swin_transformer': swin_t,          # the reference's own addition (models/__init__.py:80)
 }
+# build_model's own keywords -> the names that take them; every other name refuses a value other than None
+__keyword_models = {
+    'version': ('swin_transformer',),
+    'hw_precision': ('seres18_ibn', 'cares18_ibn', 'emares18_ibn'),
+    'hw_siblings': ('cares18_ibn',),
+    'hw_ema': ('emares18_ibn',),
+    'hw_f16': ('seres18_ibn',),
+    'hw_sib_f16': ('cares18_ibn', 'emares18_ibn'),
+}
 
 
 def show_avai_models():
@@ -35,28 +44,11 @@ def build_model(name, num_classes, loss='softmax', pretrained=True, use_gpu=True
     if name not in avai_models:
         raise KeyError('Unknown model: {}. Must be one of {}'.format(name, avai_models))
     extra = {}
-    if version is not None:
-        if name != 'swin_transformer':
-            raise ValueError("model '{}' has no version argument".format(name))
-        extra['version'] = version
-    if hw_precision is not None:
-        if name == 'swin_transformer':
-            raise ValueError("model '{}' has no hw_precision argument".format(name))
-        extra['hw_precision'] = hw_precision
-    if hw_siblings is not None:
-        if name != 'cares18_ibn':
-            raise ValueError("model '{}' has no hw_siblings argument".format(name))
-        extra['hw_siblings'] = hw_siblings
-    if hw_ema is not None:
-        if name != 'emares18_ibn':
-            raise ValueError("model '{}' has no hw_ema argument".format(name))
-        extra['hw_ema'] = hw_ema
-    if hw_f16 is not None:
-        if name != 'seres18_ibn':
-            raise ValueError("model '{}' has no hw_f16 argument".format(name))
-        extra['hw_f16'] = hw_f16
-    if hw_sib_f16 is not None:
-        if name not in ('cares18_ibn', 'emares18_ibn'):
-            raise ValueError("model '{}' has no hw_sib_f16 argument".format(name))
-        extra['hw_sib_f16'] = hw_sib_f16
+    given = (('version', version), ('hw_precision', hw_precision), ('hw_siblings', hw_siblings), ('hw_ema', hw_ema), ('hw_f16', hw_f16),
+             ('hw_sib_f16', hw_sib_f16))
+    for keyword, value in given:
+        if value is not None:
+            if name not in __keyword_models[keyword]:
+                raise ValueError("model '{}' has no {} argument".format(name, keyword))
+            extra[keyword] = value
     return __model_factory[name](num_classes=num_classes, loss=loss, pretrained=pretrained, use_gpu=use_gpu, precision=precision, **extra)

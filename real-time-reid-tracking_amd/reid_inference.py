@@ -32,12 +32,11 @@ the second view of the ResNet family the shifted mirror of get_inference_transfo
 ``reid_descriptor_images_u8_shift``), and ``attribute_dist`` adds the attribute distance (:276-289, tricks.py) to the device Jaccard
 matrix before its one download (``reid_distmat_add_l2_dev``).
 """
-import contextlib
 import os
 
 import numpy as np
 
-from .engine import IMG_H, IMG_W, check_hw, get_engine
+from .engine import IMG_H, IMG_W, Engine, check_hw, get_engine, hw_f16_gate, hw_sib_f16_gate
 from .parallel import DevArray
 
 
@@ -55,50 +54,37 @@ HW_ARCHS = ("seres18_hw", "cares18_hw", EMA_ARCH)
 # Float images carry the size, uint8 images are resized to ``size`` (required); seres18_ibn weights, exact fp32 (reid_*_hw).  The default
 # "seres18" stays fixed at 256 x 128, every architecture of the family and every precision mode.
 # "cares18_hw": the same with cares18_ibn weights (the script's --backbone cares18): Engine.set_hw_siblings(True) for the call, restored after it.
-# "emares18_hw": the same with emares18_ibn weights, accepted only together with the keyword hw_ema=True (_ema_gate): Engine.set_hw_ema(True)
+# "emares18_hw": the same with emares18_ibn weights, accepted only together with the keyword hw_ema=True (_keyword_gates): Engine.set_hw_ema(True)
 # for the call, restored after it.  Without the keyword the name is refused like any unknown one, so it is not in ARCHS.
 
 
-def _f16_gate(arch, hw_f16, hw_precision):
-    """The keyword hw_f16=True belongs to arch="seres18_hw" and replaces hw_precision (ValueError, before any device call).  Returns it as a bool."""
-    from .engine import Engine
-    on = bool(Engine.hw_f16_value(hw_f16))
-    if on and arch != "seres18_hw":
-        raise ValueError("hw_f16 belongs to arch='seres18_hw' (the fp16-storage any-size forward serves seres18_ibn only); arch=%r takes none"
-                         % (arch,))
-    if on and hw_precision is not None:
-        raise ValueError("hw_f16 and hw_precision both name the arithmetic of arch='seres18_hw': give one of them, got hw_f16=%r and "
-                         "hw_precision=%r" % (hw_f16, hw_precision))
-    return on
-
-
-def _sib_f16_gate(arch, hw_sib_f16, hw_precision, hw_f16):
-    """The keyword hw_sib_f16=True belongs to arch="cares18_hw" / "emares18_hw" and goes without hw_precision and hw_f16 (ValueError, before
-    any device call).  Returns it as a bool."""
-    from .engine import Engine
-    on = bool(Engine.hw_sib_f16_value(hw_sib_f16))
-    if on and arch not in ("cares18_hw", EMA_ARCH):
-        raise ValueError("hw_sib_f16 belongs to arch='cares18_hw' / 'emares18_hw' (arch='seres18_hw': hw_f16); arch=%r takes none" % (arch,))
-    if on and (hw_precision is not None or Engine.hw_f16_value(hw_f16)):
-        raise ValueError("hw_sib_f16 names the arithmetic of the call itself: give it without hw_precision and hw_f16, got hw_sib_f16=%r, "
-                         "hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
-    return on
-
-
-def _ema_gate(arch, hw_ema):
-    """arch="emares18_hw" and the keyword hw_ema=True come together or not at all (ValueError, before any device call)."""
-    from .engine import Engine
+def _keyword_gates(arch, hw_ema, hw_sib_f16, hw_f16, hw_precision):
+    """The any-size keywords of one call against ``arch`` (ValueError, before any device call): arch="emares18_hw" and hw_ema=True come
+    together or not at all; hw_sib_f16=True belongs to arch="cares18_hw" / "emares18_hw" and goes without hw_precision and hw_f16;
+    hw_f16=True belongs to arch="seres18_hw" and replaces hw_precision.  Returns (hw_sib_f16, hw_f16) as bools."""
     on = bool(Engine.hw_ema_value(hw_ema))
     if arch == EMA_ARCH and not on:
         raise ValueError("arch must be one of %s, got %r (the keyword hw_ema=True enables arch=%r)" % (ARCHS, arch, EMA_ARCH))
     if on and arch != EMA_ARCH:
         raise ValueError("hw_ema belongs to arch=%r; arch=%r takes none" % (EMA_ARCH, arch))
-    return on
+    sib_f16 = hw_sib_f16_gate(hw_sib_f16, hw_precision, hw_f16, arch in ("cares18_hw", EMA_ARCH), "hw_sib_f16 belongs to arch='cares18_hw' / "
+                              "'emares18_hw' (arch='seres18_hw': hw_f16); arch=%r takes none" % (arch,), "the call")
+    f16 = hw_f16_gate(hw_f16, hw_precision, arch == "seres18_hw", "hw_f16 belongs to arch='seres18_hw' (the fp16-storage any-size forward "
+                      "serves seres18_ibn only); arch=%r takes none" % (arch,), "arch='seres18_hw'")
+    return sib_f16, f16
+
+
+def _check_hw_precision(arch, hw_precision):
+    """The keyword hw_precision belongs to the *_hw archs and takes Engine.set_hw_precision's values (ValueError, before any device call)."""
+    if hw_precision is not None:
+        if arch not in HW_ARCHS:
+            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw' / 'emares18_hw'; arch=%r takes none" % (arch,))
+        Engine.hw_precision_value(hw_precision)
 
 
 def _descriptor_width(engine, arch):
     """Width of a descriptor row of ``arch`` on this engine; ValueError for an unknown arch or weights without a classifier."""
-    if arch not in ARCHS and arch != EMA_ARCH:              # "emares18_hw" has passed _ema_gate where this is reached
+    if arch not in ARCHS and arch != EMA_ARCH:              # "emares18_hw" has passed _keyword_gates where this is reached
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
     if arch == "swin":
         nc, dim = getattr(engine, "swin_num_class", 0), getattr(engine, "swin_dim", 0)
@@ -135,7 +121,6 @@ def is_u8_images(images):
 
 def _check_u8_images(images, arch, size):
     """uint8 HWC images of any sizes and the (H, W) they are resized to -> (list of arrays, (H, W)); ValueError before any device call."""
-    from .engine import Engine
     if arch == "swin":
         h, w, _ = Engine._swin_crop_args((448, 224) if size is None else size, None)
     elif arch in HW_ARCHS:
@@ -181,7 +166,6 @@ def _inference_u8(engine, images, d_out, flip, bs, arch, view_index, size, width
 def _check_strong(arch, flip, strong_offsets, n, pad):
     """The strong_inference keywords, checked before any device call: the ResNet family only (the script gives the Swin the plain
     mirror), with the mirrored view on, pad in 0 .. 32 and every (top, left) in [0, 2 pad] -> (int32 [n, 2], pad)."""
-    from .engine import Engine
     if arch == "swin":
         raise ValueError("strong_inference / strong_offsets are the ResNet family's second view; the script gives arch='swin' the plain mirror")
     if not flip:
@@ -221,14 +205,8 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
     in fp16 storage with fp32 accumulation - ``Engine.set_hw_f16(True)`` for this call and restored after it.  ``hw_sib_f16=True``
     (``arch="cares18_hw"`` / ``"emares18_hw"`` only - the latter still with ``hw_ema=True`` -, without ``hw_precision`` and ``hw_f16``): the
     same for the siblings, ``Engine.set_hw_sib_f16(True)`` for this call and restored after it."""
-    _ema_gate(arch, hw_ema)
-    sib_f16 = _sib_f16_gate(arch, hw_sib_f16, hw_precision, hw_f16)
-    f16 = _f16_gate(arch, hw_f16, hw_precision)
-    if hw_precision is not None:
-        from .engine import Engine
-        if arch not in HW_ARCHS:
-            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw' / 'emares18_hw'; arch=%r takes none" % (arch,))
-        Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
+    sib_f16, f16 = _keyword_gates(arch, hw_ema, hw_sib_f16, hw_f16, hw_precision)
+    _check_hw_precision(arch, hw_precision)
     if strong_offsets is not None:
         strong_offsets, pad = _check_strong(arch, flip, strong_offsets, len(images), pad)
     width = _descriptor_width(engine, arch)
@@ -251,16 +229,14 @@ def inference_efficient(engine, images, d_out, flip=True, bs=1024, arch="seres18
             raise ValueError("view_index must hold one non-negative index per image (%d), got %d" % (n, view_index.shape[0]))
         view_index = view_index.astype(np.int32)
     if hw_precision is not None or f16 or arch in ("cares18_hw", EMA_ARCH):   # every argument is checked: the settings go on for the device work and off after it
-        with engine.hw_precision_scope(hw_precision), engine.hw_siblings_scope(True if arch == "cares18_hw" else None), \
-                engine.hw_ema_scope(True if arch == EMA_ARCH else None), (engine.hw_f16_scope(True) if f16 else contextlib.nullcontext()), \
-                (engine.hw_sib_f16_scope(True) if sib_f16 else contextlib.nullcontext()):
+        with Engine.hw_scope(engine, precision=hw_precision, siblings=True if arch == "cares18_hw" else None, ema=True if arch == EMA_ARCH else None,
+                             f16=f16 or None, sib_f16=sib_f16 or None):
             return inference_efficient(engine, images, d_out, flip, bs, "seres18_hw", view_index, size if u8 else None,
                                        strong_offsets=strong_offsets, pad=pad)
     if u8:
         return _inference_u8(engine, images, d_out, flip, int(bs), arch, view_index, size, width, strong_offsets, pad)
     fill = None
     if strong_offsets is not None:
-        from .engine import Engine
         fill = Engine.normalised_zero_fill()
     stage = DevArray(engine, (min(bs, max(n, 1)),) + images.shape[1:], np.float32)
     try:
@@ -312,9 +288,7 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
     the descriptors come from the fp16-storage any-size forward, ``Engine.set_hw_f16(True)`` for the call.  ``hw_sib_f16=True``
     (``arch="cares18_hw"`` / ``"emares18_hw"`` only, without ``hw_precision`` and ``hw_f16``): the same for the siblings,
     ``Engine.set_hw_sib_f16(True)`` for the call."""
-    _ema_gate(arch, hw_ema)
-    _sib_f16_gate(arch, hw_sib_f16, hw_precision, hw_f16)
-    _f16_gate(arch, hw_f16, hw_precision)
+    _keyword_gates(arch, hw_ema, hw_sib_f16, hw_f16, hw_precision)
     if strong_inference or strong_offsets is not None:
         n_all = len(gallery_labels) + len(query_labels)
         if strong_offsets is None:
@@ -333,11 +307,7 @@ def evaluate_reid(gallery_images, gallery_labels, gallery_cams, gallery_seqs, qu
             raise ValueError("attribute_dist must give one row of 1 .. 32 attributes per image (%d, gallery first), got %s"
                              % (len(gallery_labels) + len(query_labels), attr_rows.shape))
         attr_rows = tricks.normalize_rows(attr_rows)
-    if hw_precision is not None:
-        from .engine import Engine
-        if arch not in HW_ARCHS:
-            raise ValueError("hw_precision is the arithmetic of arch='seres18_hw' / 'cares18_hw' / 'emares18_hw'; arch=%r takes none" % (arch,))
-        Engine.hw_precision_value(hw_precision)      # a bad value raises here, before any device call
+    _check_hw_precision(arch, hw_precision)
     if arch not in ARCHS and arch != EMA_ARCH:
         raise ValueError("arch must be one of %s, got %r" % (ARCHS, arch))
     if use_side and arch != "swin":

@@ -14,7 +14,7 @@ most of its launches, so several camera streams driven from several host threads
 """
 import numpy as np
 
-from .engine import Engine, get_engine
+from .engine import Engine, get_engine, hw_f16_gate, hw_sib_f16_gate
 from .nn_matching import NearestNeighborDistanceMetric
 
 
@@ -39,19 +39,11 @@ HW_ARCHS = ("seres18_hw", "cares18_hw", EMA_ARCH)
 def _check_arch(arch, size, mean_std, hw_precision=None, hw_ema=False, hw_f16=False, hw_sib_f16=False):
     """`arch`, `size`, `mean_std`, `hw_precision`, `hw_ema`, `hw_f16` of the stream classes, checked before any device call (ValueError)."""
     on = bool(Engine.hw_ema_value(hw_ema))
-    if Engine.hw_sib_f16_value(hw_sib_f16):
-        if arch not in ("cares18_hw", EMA_ARCH):
-            raise ValueError("hw_sib_f16 belongs to arch='cares18_hw' / %r (arch='seres18_hw': hw_f16), got arch %r" % (EMA_ARCH, arch))
-        if hw_precision is not None or Engine.hw_f16_value(hw_f16):
-            raise ValueError("hw_sib_f16 names the arithmetic of the stream's crops itself: give it without hw_precision and hw_f16, got "
-                             "hw_sib_f16=%r, hw_precision=%r, hw_f16=%r" % (hw_sib_f16, hw_precision, hw_f16))
-    if Engine.hw_f16_value(hw_f16):
-        if arch != "seres18_hw":
-            raise ValueError("hw_f16 belongs to arch='seres18_hw' (the fp16-storage any-size forward serves seres18_ibn only), got arch %r"
-                             % (arch,))
-        if hw_precision is not None:
-            raise ValueError("hw_f16 and hw_precision both name the arithmetic of arch='seres18_hw': give one of them, got hw_f16=%r and "
-                             "hw_precision=%r" % (hw_f16, hw_precision))
+    hw_sib_f16_gate(hw_sib_f16, hw_precision, hw_f16, arch in ("cares18_hw", EMA_ARCH),
+                    "hw_sib_f16 belongs to arch='cares18_hw' / %r (arch='seres18_hw': hw_f16), got arch %r" % (EMA_ARCH, arch), "the stream's crops")
+    hw_f16_gate(hw_f16, hw_precision, arch == "seres18_hw",
+                "hw_f16 belongs to arch='seres18_hw' (the fp16-storage any-size forward serves seres18_ibn only), got arch %r" % (arch,),
+                "arch='seres18_hw'")
     if arch == EMA_ARCH and not on:
         raise ValueError("arch must be 'seres18', 'seres18_hw', 'cares18_hw' or 'swin', got %r (the keyword hw_ema=True enables arch=%r)"
                          % (arch, EMA_ARCH))
@@ -93,12 +85,11 @@ def _load_backbone(stream, arch, weights_blob, manifest, size, mean_std, hw_prec
         stream.eng.set_hw_siblings(True)
     if arch == EMA_ARCH:
         stream.eng.set_hw_ema(True)
-    f16 = bool(Engine.hw_f16_value(hw_f16))
-    if arch in HW_ARCHS and (f16 or getattr(stream.eng, "hw_f16", False)):      # on for this stream, or left on by an earlier user of a shared context
-        stream.eng.set_hw_f16(f16)
-    sib_f16 = bool(Engine.hw_sib_f16_value(hw_sib_f16))
-    if arch in HW_ARCHS and (sib_f16 or getattr(stream.eng, "hw_sib_f16", False)):   # likewise
-        stream.eng.set_hw_sib_f16(sib_f16)
+    if arch in HW_ARCHS:
+        for name, on in (("hw_f16", hw_f16), ("hw_sib_f16", hw_sib_f16)):
+            on = bool(getattr(Engine, name + "_value")(on))
+            if on or getattr(stream.eng, name, False):      # on for this stream, or left on by an earlier user of a shared context
+                getattr(stream.eng, "set_" + name)(on)
     stream.arch, stream.size, stream.mean_std = arch, size, mean_std
 
 
